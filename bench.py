@@ -7,9 +7,19 @@
 
 One "step" = one forward of the layer over one batch of synthetic maps already resident in HBM
 (headline workload: nside=1024 full sphere, K=5, Fin=Fout=64, batch 4, fp32).  Prints ONE JSON
-line on rank 0: throughput in Mpix*channels/s (= N*M*Fout / t), the HBM-roofline figures of the
-kernel(s) of one forward measured with HIP events, and a CPU baseline (the oracle's fp32 port
-of the reference op sequence on a bounded sample, host cores counted).
+line on rank 0: throughput in Mpix*channels/s (= N*M*Fout / t) and the HBM-roofline figures of the
+kernel(s) of one forward measured with HIP events around the timed steps.
+
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full
+
+--full adds what takes runs or checks of its own: the timed output against the float64 oracle,
+the same forward in the other contraction arithmetics, with bias + ReLU and as a training step,
+the issue bounds replayed from the stored counters, and a CPU baseline (the oracle's fp32 port of
+the reference op sequence on a bounded sample, host cores counted).
+
+--dump-outputs DIR writes the output of the last timed step as DIR/<name>.npy (float32): the whole
+output when it fits in 48 MB, else a fixed, seeded sample of its pixel rows (every map, every
+channel; the rows as DIR/y_rows.npy).  Inputs are seeded, so two builds can be compared file for file.
 
 With N > 1 the map is sharded over the ranks by contiguous NEST pixel ranges (base pixels and
 their quarters) and the (K-1)-ring halo of x is exchanged over RCCL inside every timed step:
@@ -124,7 +134,8 @@ def cpu_baseline(K, Fin, Fout, device, budget_s, nside_headline=1024):
 
     from oracle import cheb_cpu_baseline as cb
 
-    cores = os.cpu_count() or 1
+    # the cores this process may use: OMP_NUM_THREADS where the host sets it, else the CPU affinity mask (not the machine's count)
+    cores = int(os.environ.get("OMP_NUM_THREADS", "0") or 0) or len(os.sched_getaffinity(0)) or 1
     avail_gb = psutil.virtual_memory().available / 2 ** 30
     nside_s = nside_headline if avail_gb > 96 else (512 if avail_gb > 28 else 256)
     N_s = 1
@@ -267,6 +278,28 @@ def timed_ms(run, steps, warm=3):
     return float(np.mean([a.elapsed_time(b) for a, b in ev]))
 
 
+DUMP_BYTES = 48 * 2 ** 20  # --dump-outputs: at most this many bytes of output in all (a dump stays under 64 MB)
+DUMP_SEED = 2024
+
+
+def dump_outputs(y, out_dir, rank=0, world=1):
+    """Write the output y (N, rows, Fout) of the last timed step to out_dir: whole as y.npy when it fits in this rank's share of
+    DUMP_BYTES, else every map and channel of a fixed, seeded set of rows (sorted) as y.npy and the row indices as y_rows.npy
+    (float64, exact).  A sharded run writes each rank's own rows as y_rank<r>.npy / y_rows_rank<r>.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    N, R, F = y.shape
+    budget = DUMP_BYTES // world
+    suffix = "" if world == 1 else f"_rank{rank}"
+    if N * R * F * 4 <= budget:
+        np.save(os.path.join(out_dir, f"y{suffix}.npy"), y.detach().float().cpu().numpy())
+        return
+    n_rows = budget // (N * F * 4 + 8)
+    rows = np.sort(np.random.default_rng(DUMP_SEED + rank).choice(R, size=n_rows, replace=False))
+    sample = y.detach()[:, torch.as_tensor(rows, device=y.device)].float().cpu().numpy()
+    np.save(os.path.join(out_dir, f"y{suffix}.npy"), sample)
+    np.save(os.path.join(out_dir, f"y_rows{suffix}.npy"), rows.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -288,7 +321,12 @@ def main():
                     help="plan option DSPH_OPT_STRUCT (off: every tile on the breadth-first tile kernel)")
     ap.add_argument("--fork", default="on", choices=["on", "off"],
                     help="plan option DSPH_OPT_FORK (the BFS-tile launch beside the structured ones, on the plan's side stream)")
-    ap.add_argument("--quick", action="store_true", help="the headline leg only: no side legs in the other arithmetics, no CPU baseline")
+    ap.add_argument("--full", action="store_true",
+                    help="also check the timed output against the oracle and run the side legs (other arithmetics, bias + ReLU, "
+                         "training step, issue bounds, CPU baseline); off: set-up, warm-up, the timed steps and the result line only")
+    ap.add_argument("--quick", action="store_true", help="with --full: the oracle check only, no side legs and no CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the output of the last timed step (or a fixed, seeded sample of its rows) to DIR/*.npy")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="process-group backend for --gpus > 1: nccl = RCCL over xGMI (one rank per GPU); gloo = halo rows "
                          "staged through the host, ranks dealt round-robin over the visible GPUs (debugging on a 1-GPU box)")
@@ -465,6 +503,8 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t_start
     per_fwd_ms = [a.elapsed_time(b) / (1 if per_step_events else args.steps) for a, b in ev]
+    if args.dump_outputs:
+        dump_outputs(y_timed, args.dump_outputs, rank, world)
 
     el = torch.tensor([elapsed], dtype=torch.float64, device=device if args.backend == "nccl" else "cpu")
     if dist is not None:
@@ -480,7 +520,8 @@ def main():
         achieved = b_alg / (dev_ms * 1e-3) / 1e9
         traffic = None
         err_note = ""
-        if world == 1 and not os.environ.get("DSPH_BENCH_NO_CHECK"):
+        side_legs = args.full and not args.quick  # (a plain run: the headline line only)
+        if world == 1 and args.full and not os.environ.get("DSPH_BENCH_NO_CHECK"):
             # the oracle as the checker of what was just timed (after the timed region): max error over the patches
             try:
                 e_rel, n_pts = measured_error(cols, vals, x, y_timed, w_np, K, nside)
@@ -555,7 +596,7 @@ def main():
                 "min_max_forward_ms_hip_events": [round(float(np.min(per_fwd_ms)), 4), round(float(np.max(per_fwd_ms)), 4)],
             },
         }
-        if world == 1 and not args.quick:
+        if world == 1 and side_legs:
             # the same forward in the other contraction arithmetics, for the record (HIP events over `steps` forwards each).
             # Each leg's roofline is the largest of its lower bounds: algorithmic bytes at 8 TB/s, and the dense flops at the
             # peak of the pipe the arithmetic really runs on -- fp32 MFMA 157.3 TF/s; bf16 MFMA 2500 TF/s, counted three / six
@@ -607,21 +648,21 @@ def main():
                                          "flops": f_d, "hbm_frac": round(b_alg / (msq * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}}
                 del yq
             layer.precision = args.precision
-        if world == 1 and not args.quick:
+        if world == 1 and side_legs:
             # one run with bias + ReLU fused into the kernel epilogue
             layer.precision = args.precision
             layer.use_bias = True
             layer.bias = torch.nn.Parameter(torch.randn(1, 1, Fout, device=device))
             layer.activation, layer._act_code = gnn_layers._resolve_activation("relu")
             out["bias_relu"] = {"ms_per_step": round(timed_ms(run, max(args.steps, 20)), 4)}
-        if world == 1 and not args.quick and K <= 5:  # (K > 5: the weight gradient goes through planes in memory: tens of GB at c4)
+        if world == 1 and side_legs and K <= 5:  # (K > 5: the weight gradient goes through planes in memory: tens of GB at c4)
             # SURVEY 8 (f1), for the record: the layer's training step through autograd -- dx on the forward kernels, dkernel by
             # dsph_cheb_backward_weights (K = 5, 64 -> 64 j: the quad-strip weight-gradient kernel) -- HIP events, not the metric
             try:
                 out["training_step"] = training_step_leg(cols, vals, K, lmax, Fout, device, args, plan_options, w_np, x, max(3, min(args.steps, 10)))
             except Exception as exc:  # noqa: BLE001  (a side leg must not take the headline down: out of memory on a small box)
                 out["training_step"] = {"error": repr(exc)[:200]}
-        if world == 1 and args.cpu_budget > 0 and not args.quick:
+        if world == 1 and args.cpu_budget > 0 and side_legs:
             out["cpu_baseline"] = cpu_baseline(K, Fin, Fout, device, args.cpu_budget)
         print(json.dumps(out), flush=True)
     if dist is not None:

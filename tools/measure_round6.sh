@@ -5,12 +5,12 @@
 # over tools/run_forward.py.  Small files into gpurun_out/measure6/; tools/fold_round6.py folds them into profiles/.
 cd /tmp && export TMPDIR=/tmp; cd "$GRAFT_REPO_ROOT" || exit 1
 O=gpurun_out/measure6; mkdir -p $O
-python3 bench.py --steps 20 --warmup 5 2>/dev/null | tail -1 > $O/bench_c3.json
-python3 bench.py --steps 20 --warmup 5 --quick --strip-form pairs 2>/dev/null | tail -1 > $O/bench_c3_pairs.json
-python3 bench.py --steps 20 --warmup 5 --quick --precision f16x3 2>/dev/null | tail -1 > $O/bench_c3_f16x3.json
+python3 bench.py --full --steps 20 --warmup 5 2>/dev/null | tail -1 > $O/bench_c3.json
+python3 bench.py --full --steps 20 --warmup 5 --quick --strip-form pairs 2>/dev/null | tail -1 > $O/bench_c3_pairs.json
+python3 bench.py --full --steps 20 --warmup 5 --quick --precision f16x3 2>/dev/null | tail -1 > $O/bench_c3_f16x3.json
 if [ -z "$R6_C3_ONLY" ]; then
-  for c in c1 c2 k10 in1 knn8 knn20; do python3 bench.py --config $c --steps 100 --warmup 20 --cpu-budget 0 2>/dev/null | tail -1 > $O/bench_$c.json; done
-  for c in c4 c5 knn8h; do python3 bench.py --config $c --steps 10 --warmup 3 --cpu-budget 0 2>/dev/null | tail -1 > $O/bench_$c.json; done
+  for c in c1 c2 k10 in1 knn8 knn20; do python3 bench.py --full --config $c --steps 100 --warmup 20 --cpu-budget 0 2>/dev/null | tail -1 > $O/bench_$c.json; done
+  for c in c4 c5 knn8h; do python3 bench.py --full --config $c --steps 10 --warmup 3 --cpu-budget 0 2>/dev/null | tail -1 > $O/bench_$c.json; done
   python3 tools/bench_backward.py > $O/bench_backward_c3.json 2>/dev/null
   python3 tools/bench_backward.py c5 > $O/bench_backward_c5.json 2>/dev/null
   python3 tools/bench_net.py 8 > $O/bench_net.json 2>/dev/null
