@@ -30,136 +30,11 @@
 #include <string.h>
 
 #include <algorithm>
-#include <map>
-#include <mutex>
-#include <unordered_map>
-#include <vector>
 
-#include "cheb_fused_kernel.h"
 #include "cheb_istrip_kernel.h"
-#include "cheb_qstrip8_kernel.h"
-#include "cheb_qstrip_kernel.h"
-#include "cheb_strip_kernel.h"
-#include "cheb_struct_kernel.h"
+#include "cheb_tiles.h"
 
 namespace dsph {
-
-
-struct FusedTiles {
-  int D = 0;
-  int width = 0;     // ELL width of the tile-local table (template width, >= plan width)
-  int ntiles = 0;
-  int rmax = 0;      // largest region (rows), rounded up to a multiple of 16, >= FUSED_P
-  int emax = 0;      // largest number of rows that carry an ELL row
-  bool ok = false;
-  int32_t* d_tile_off = nullptr;
-  int32_t* d_ring_end = nullptr;   // [ntiles][DMAX+1]
-  int64_t* d_ell_off = nullptr;    // [ntiles] in rows
-  int32_t* d_region = nullptr;
-  uint16_t* d_lcols = nullptr;
-  float* d_lvals = nullptr;
-  // tiles whose whole region lies in the plan's output rows ("interior": on a sharded plan they need no halo row
-  // of another rank) and the rest ("boundary"); positions [0, n_interior) and [n_interior, ntiles) of d_part
-  int32_t* d_part = nullptr;
-  int n_interior = 0;
-  int n_part = 0;      // entries of d_part: all tiles of a full table, the class-G tiles otherwise
-  // class-R tiles (cheb_struct_kernel.h), interior ones first; empty in a full table
-  int32_t* d_rlist = nullptr;
-  int n_r = 0, n_r_interior = 0;
-  // class-T tiles (structured kernel with per-tile tables, embed_tile below), interior ones first
-  int32_t* d_tlist = nullptr;
-  int32_t* d_tabrow = nullptr;  // [n_t][ST_CELLS] row of every plane cell
-  float* d_tabvals = nullptr;   // [n_t][ST_CELLS][ST_TABV] diagonal + eight directions of L~ per cell, in the tile's frame
-  int n_t = 0, n_t_interior = 0;
-  // strip kernel (cheb_strip_kernel.h): rectangles of interior class-R tiles cut into strip pairs, and the class-R tiles
-  // they leave over (interior ones first).  Built next to d_rlist; which of the two sets a forward uses depends on its shape.
-  StripPair* d_pairs = nullptr;
-  int n_pairs = 0;
-  int64_t n_strip_tiles = 0;
-  std::vector<int32_t> strip_steps;        // per pair, in list order: rows + run-in = strip steps of one map
-  std::vector<StripPair> h_pairs;          // host copy of d_pairs (dsph_plan_strip_pairs: what the seam tests read)
-  mutable std::map<int64_t, int64_t> strip_span;  // batch N -> steps of the busiest workgroup (strip_makespan; under FusedPlan::mu)
-  bool strip_forced = false;               // DSPH_OPT_STRIPS = 1 when the tables were built: the cost gate is off
-  // quad-strip kernel (cheb_qstrip_kernel.h): the same rectangles, merged side by side and cut into 64-column strips
-  QStrip* d_qstrips = nullptr;             // uncut along y: the kernel cuts the tape of their rows evenly over its workgroups
-  int32_t* d_qprefix = nullptr;            // [n_qstrips + 1] rows before each strip
-  int n_qstrips = 0;
-  int64_t qtape_rows = 0;
-  std::vector<QStrip> h_qstrips;
-  // ... addressed through tables of tile bases (round 6, build_qtstrips): the rectangles of the quad strips are found on the
-  // LOGICAL tile grid -- class-R tiles and the class-T tiles whose eight neighbour tiles continue the pixel grid by a pure
-  // translation (base-pixel borders between an equatorial and a polar face, superpixel borders of a compacted partial-sky
-  // map) -- and a strip looks its rows up as tab[tile row][tile column] + morton(x & 15, y & 15).
-  int32_t* d_qtab = nullptr;               // tile-base tables of all rectangles, back to back (row numbers)
-  std::vector<int32_t> h_qtab;
-  int64_t n_qstrip_tiles = 0;              // tiles the quad strips take
-  // K = 8 quad strips (cheb_qstrip8_kernel.h; the tables of depth 7 only): rectangles of the tiles whose 7-ring region is a regular
-  // square of the Morton plane, and the tiles they leave to the breadth-first tile kernel (interior first, the order of d_part)
-  QStrip* d_q8strips = nullptr;
-  int32_t* d_q8prefix = nullptr;
-  int32_t* d_q8tab = nullptr;
-  int32_t* d_q8rest = nullptr;
-  int n_q8strips = 0, n_q8rest = 0, n_q8rest_interior = 0;  // (the rest list: interior tiles first, like d_part)
-  int64_t q8tape_rows = 0, n_q8_tiles = 0;
-  std::vector<QStrip> h_q8strips;
-  std::vector<int32_t> h_q8tab;
-  // what the quad strips leave to the structured kernel: class-R tiles (interior first) and class-T tiles with their tables
-  int32_t* d_qrrest = nullptr;
-  int n_qrrest = 0, n_qrrest_interior = 0;
-  int32_t* d_qtlist = nullptr;
-  int32_t* d_qtabrow = nullptr;
-  float* d_qtabvals = nullptr;
-  int n_qt = 0, n_qt_interior = 0;
-  // input-side strip kernel (cheb_istrip_kernel.h): the same rectangles, uncut along y (the kernel cuts every strip into the
-  // number of row segments that istrip_segments picks for the batch)
-  StripPair* d_ipairs = nullptr;
-  int n_ipairs = 0;
-  std::vector<int32_t> ipair_h;             // rows of every pair
-  std::vector<unsigned char> ipair_second;  // whether its second strip exists
-  mutable std::map<int64_t, int> iseg;      // 2 * batch N + narrow -> row segments per strip (under FusedPlan::mu)
-  // every tile of the plan, the interior ones first (d_all[0 .. n_all_interior)): what a two-part launch with a deferred
-  // activation finishes per part (launch_struct_act_tiles)
-  int32_t* d_all = nullptr;
-  int n_all = 0, n_all_interior = 0;
-  int32_t* d_rrest = nullptr;
-  int n_rrest = 0, n_rrest_interior = 0;
-  // every tile the strips leave over, whatever its class (class R rest, T, G): what the BFS-tile kernel's weight-gradient mode
-  // runs next to the quad-strip weight gradient (cheb_qwgrad.hip)
-  int32_t* d_nonq = nullptr;
-  int n_nonq = 0;
-};
-
-struct FusedPlan {
-  std::vector<int32_t> h_cols;  // host copy of the ELL (needed to build tiles for a new K)
-  std::vector<float> h_vals;
-  std::mutex mu;
-  std::map<int, FusedTiles> by_depth;  // key: 2 * depth + (1: BFS tables of every tile, 0: of the class-G tiles only)
-  int num_cu = 256;
-  // direction-ordered copy of L~ and the per-row regularity flags (cheb_struct.hip), built on first use
-  float* d_gvals8 = nullptr;
-  float* d_gdiag = nullptr;
-  unsigned char* d_rowflag = nullptr;
-  bool rows_tried = false;
-  bool host_released = false;  // DSPH_PREPARE_RELEASE_HOST: no tables for further depths
-  int symmetric = -1;          // L~ == L~^T entry for entry (fused_symmetric; -1: not looked at yet)
-  bool wide = false;           // ELL wider than the fused kernels' templates: only the depth-1 tables of the tiled step exist
-  // The BFS-tile launch of a forward writes tiles of y that the structured launches do not touch: it runs on this side stream,
-  // forked from and joined back into the caller's stream by the two events (a few dozen face-corner tiles would otherwise
-  // hold the whole device for the latency of one tile: 14 of the 44 us of BASELINE configs[0], 57 of 544 us of configs[1]).
-  // Created by dsph_plan_prepare on plans whose tables call for a fork (side_stream_ready) -- a prepared forward allocates
-  // nothing; fork_mu keeps two host threads that share a plan from interleaving their record / wait pairs.  Capturable: the side stream joins the capture through the fork event and leaves it at the join.
-  hipStream_t side = nullptr;
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  bool side_failed = false;
-  std::mutex fork_mu;
-  // DSPH_FWD_KEEP_WEIGHTS: the caller vouches for the weight VALUES; WHICH images a workspace block holds is the library's
-  // own business -- it depends on per-call choices (strips or tiles by the batch, maps packed or not) the caller cannot see.
-  // Per workspace block: the shape key the images were packed for and the set of images packed since (IMG_* bits).  A kept
-  // call packs what the set lacks; a call that does not keep starts an empty set.
-  struct Images { uint64_t key = 0; uint32_t mask = 0; };
-  std::mutex img_mu;
-  std::unordered_map<const void*, Images> images;
-};
 
 void fused_images_begin(const dsph_plan* plan, const void* ws, uint64_t key, bool keep) {
   FusedPlan* fp = plan->fused;
@@ -193,56 +68,6 @@ uint64_t fused_images_key(int32_t Fin, int32_t Fin_w, int32_t Fout, int32_t K, i
          ((uint64_t)pack << 58) | (1ull << 63);
 }
 
-static int template_width(int w) {
-  if (w <= 9) return 9;
-  if (w <= 12) return 12;
-  return 0;
-}
-
-static void free_tiles(FusedTiles& ft) {
-  if (ft.d_tile_off) (void)hipFree(ft.d_tile_off);
-  if (ft.d_ring_end) (void)hipFree(ft.d_ring_end);
-  if (ft.d_ell_off) (void)hipFree(ft.d_ell_off);
-  if (ft.d_region) (void)hipFree(ft.d_region);
-  if (ft.d_lcols) (void)hipFree(ft.d_lcols);
-  if (ft.d_lvals) (void)hipFree(ft.d_lvals);
-  if (ft.d_part) (void)hipFree(ft.d_part);
-  if (ft.d_rlist) (void)hipFree(ft.d_rlist);
-  if (ft.d_tlist) (void)hipFree(ft.d_tlist);
-  if (ft.d_tabrow) (void)hipFree(ft.d_tabrow);
-  if (ft.d_tabvals) (void)hipFree(ft.d_tabvals);
-  if (ft.d_pairs) (void)hipFree(ft.d_pairs);
-  if (ft.d_qstrips) (void)hipFree(ft.d_qstrips);
-  if (ft.d_qprefix) (void)hipFree(ft.d_qprefix);
-  if (ft.d_qtab) (void)hipFree(ft.d_qtab);
-  if (ft.d_q8strips) (void)hipFree(ft.d_q8strips);
-  if (ft.d_q8prefix) (void)hipFree(ft.d_q8prefix);
-  if (ft.d_q8tab) (void)hipFree(ft.d_q8tab);
-  if (ft.d_q8rest) (void)hipFree(ft.d_q8rest);
-  if (ft.d_qrrest) (void)hipFree(ft.d_qrrest);
-  if (ft.d_qtlist) (void)hipFree(ft.d_qtlist);
-  if (ft.d_qtabrow) (void)hipFree(ft.d_qtabrow);
-  if (ft.d_qtabvals) (void)hipFree(ft.d_qtabvals);
-  if (ft.d_rrest) (void)hipFree(ft.d_rrest);
-  if (ft.d_nonq) (void)hipFree(ft.d_nonq);
-  if (ft.d_all) (void)hipFree(ft.d_all);
-  if (ft.d_ipairs) (void)hipFree(ft.d_ipairs);
-  ft = FusedTiles();
-}
-
-FusedPlan* fused_plan_build(const dsph_plan* plan, const int32_t* h_cols, const float* h_vals) {
-  if (template_width(plan->width) == 0 && tstep_width(plan->width) == 0) return nullptr;
-  FusedPlan* fp = new FusedPlan();
-  fp->wide = template_width(plan->width) == 0;
-  const size_t nnz = (size_t)plan->n_rows * plan->width;
-  fp->h_cols.assign(h_cols, h_cols + nnz);
-  fp->h_vals.assign(h_vals, h_vals + nnz);
-  hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, plan->device) == hipSuccess && prop.multiProcessorCount > 0)
-    fp->num_cu = prop.multiProcessorCount;
-  return fp;
-}
-
 // The side stream and its two events exist only on plans that fork (a network holds dozens of plans, most of which
 // never do): created by dsph_plan_prepare when the prepared tables call for it, or by the first forward that wants to fork --
 // unless that forward is being captured into a graph, in which case it runs on the one stream.  Under fork_mu.
@@ -268,1085 +93,6 @@ static bool side_stream_ready(const dsph_plan* plan, FusedPlan* fp, hipStream_t 
   fp->ev_join = e1;
   fp->side = st;
   return true;
-}
-
-void fused_plan_destroy(FusedPlan* fp) {
-  if (!fp) return;
-  for (auto& kv : fp->by_depth) free_tiles(kv.second);
-  if (fp->d_gvals8) (void)hipFree(fp->d_gvals8);
-  if (fp->d_gdiag) (void)hipFree(fp->d_gdiag);
-  if (fp->d_rowflag) (void)hipFree(fp->d_rowflag);
-  if (fp->side) {
-    (void)hipStreamSynchronize(fp->side);
-    (void)hipEventDestroy(fp->ev_fork);
-    (void)hipEventDestroy(fp->ev_join);
-    (void)hipStreamDestroy(fp->side);
-  }
-  delete fp;
-}
-
-bool fused_host_released(FusedPlan* fp) {
-  std::lock_guard<std::mutex> lock(fp->mu);
-  return fp->host_released;
-}
-
-// The tile tables depend on which rows are outputs (dsph_plan_set_levels): drop the cached ones.
-void fused_plan_invalidate(FusedPlan* fp) {
-  if (!fp) return;
-  std::lock_guard<std::mutex> lock(fp->mu);
-  for (auto& kv : fp->by_depth) free_tiles(kv.second);
-  fp->by_depth.clear();
-}
-
-// Class-T tiles: a tile whose own 256 rows are a 16x16 Morton square and whose D-ring region can be laid out as a
-// (16+2D)^2 square of a 9-point stencil although the ROW NUMBERS of the halo are not a Morton continuation (the next base
-// pixel of the sphere, possibly rotated; the halo rows of a sharded plan, numbered by hop distance).  The layout is
-// found from the graph alone, ring by ring: a new cell is the one row that all of its already-placed neighbours have in
-// common and that is not placed yet.  It is then VERIFIED, not trusted: every row that a step evaluates (rings 0..D-1)
-// must have each non-zero of L~ on itself or on one of its eight neighbouring cells; only then do the tables exist.
-// Anything else (the eight 7-neighbour corners of the sphere, mask edges, ragged tiles, k-NN graphs) stays class G.
-// row: [ST_CELLS] row of every plane cell (plane-cell order, pads and cells outside the region: the tile's first row);
-// val: [ST_CELLS][ST_TABV] diagonal, then the directions in the order of kDirX / kDirY.
-static bool embed_tile(const dsph_plan* plan, const int32_t* cols, const float* vals, int W, int t, int D, int64_t out_rows,
-                       int32_t* row, float* val, bool* interior, std::vector<int32_t>& key, std::vector<int32_t>& slot) {
-  const int64_t r0 = (int64_t)t * FUSED_P;
-  if (r0 + FUSED_P > out_rows) return false;  // ragged last tile
-  constexpr int S = ST_S;
-  int32_t A[S][S];
-  for (int y = 0; y < S; ++y)
-    for (int x = 0; x < S; ++x) A[x][y] = -1;
-  // open-addressing map row -> cell (x + S * y); 2048 slots for at most 576 entries
-  constexpr int HN = 2048;
-  key.assign(HN, -1);
-  slot.assign(HN, 0);
-  auto hput = [&](int32_t r, int cell) {
-    unsigned h = ((unsigned)r * 2654435761u) >> 21;
-    while (key[h] != -1) h = (h + 1) & (HN - 1);
-    key[h] = r;
-    slot[h] = cell;
-  };
-  auto hget = [&](int32_t r) -> int {
-    unsigned h = ((unsigned)r * 2654435761u) >> 21;
-    while (key[h] != -1) {
-      if (key[h] == r) return slot[h];
-      h = (h + 1) & (HN - 1);
-    }
-    return -1;
-  };
-  for (unsigned y = 0; y < 16; ++y)
-    for (unsigned x = 0; x < 16; ++x) {
-      const int32_t r = (int32_t)(r0 + st_morton(x, y));
-      A[ST_DMAX + x][ST_DMAX + y] = r;
-      hput(r, (ST_DMAX + x) + S * (ST_DMAX + y));
-    }
-  // the one unplaced row adjacent to every placed neighbour of cell (x, y); -1 if there is none or more than one
-  auto propose = [&](int x, int y) -> int32_t {
-    int32_t cand[16];
-    int nc = -1;  // -1: no anchor seen yet
-    for (int dy = -1; dy <= 1; ++dy)
-      for (int dx = -1; dx <= 1; ++dx) {
-        const int ax = x + dx, ay = y + dy;
-        if ((dx == 0 && dy == 0) || ax < 0 || ay < 0 || ax >= S || ay >= S || A[ax][ay] < 0) continue;
-        const int32_t ar = A[ax][ay];
-        if (ar >= plan->n_rows) continue;  // an input-only row has no list of neighbours: not an anchor
-        const int32_t* c = cols + (size_t)ar * W;
-        const float* v = vals + (size_t)ar * W;
-        if (nc < 0) {
-          nc = 0;
-          for (int j = 0; j < W; ++j)
-            if (v[j] != 0.f && c[j] != ar && hget(c[j]) < 0 && nc < 16) cand[nc++] = c[j];
-        } else {
-          int m = 0;
-          for (int i = 0; i < nc; ++i) {
-            bool in = false;
-            for (int j = 0; j < W && !in; ++j) in = v[j] != 0.f && c[j] == cand[i];
-            if (in) cand[m++] = cand[i];
-          }
-          nc = m;
-        }
-      }
-    return nc == 1 ? cand[0] : (nc > 1 ? -1 : -2);  // -1: ambiguous; -2: no row belongs here
-  };
-  // A cell no row belongs to is a HOLE (round 6: the edge of a survey mask -- the pixel beyond it does not exist): it stays
-  // negative in A (never an anchor), its table entry is the tile's first row with nine zeros -- what a step computes there is
-  // finite and no row of the map has a non-zero towards it.  Nothing is taken on trust: the verification below still demands
-  // that every non-zero of every evaluated row lands on a placed cell at one of the eight offsets, so a row left out by
-  // mistake (or a vertex where three base pixels meet, whose far seam is not a 3 x 3 neighbourhood) fails the tile as before.
-  auto place = [&](int x, int y) -> bool {
-    const int32_t r = propose(x, y);
-    if (r == -1) return false;
-    if (r == -2) { A[x][y] = -2; return true; }
-    A[x][y] = r;
-    hput(r, x + S * y);
-    return true;
-  };
-  for (int rho = 1; rho <= D; ++rho) {
-    const int lo = ST_DMAX - rho, hi = ST_DMAX + ST_TILE - 1 + rho;
-    // the four sides without their corners, from the middle outwards (so that each new cell has placed neighbours on
-    // the inner ring and, after the first, on its own side), then the corners
-    const int mid = (lo + hi) / 2;
-    for (int k = 0; k <= hi - lo; ++k) {
-      const int off = (k + 1) / 2 * ((k & 1) ? 1 : -1);  // 0, +1, -1, +2, -2, ...
-      const int u = mid + off;
-      if (u <= lo || u >= hi) continue;
-      if (!place(u, hi) || !place(u, lo) || !place(lo, u) || !place(hi, u)) return false;
-    }
-    if (!place(lo, lo) || !place(hi, lo) || !place(lo, hi) || !place(hi, hi)) return false;
-  }
-  // tables + verification
-  const int blo = ST_DMAX - D, bhi = ST_DMAX + ST_TILE - 1 + D;
-  for (int p = 0; p < ST_CELLS; ++p) {
-    row[p] = (int32_t)r0;
-    for (int j = 0; j < ST_TABV; ++j) val[(size_t)p * ST_TABV + j] = 0.f;
-  }
-  *interior = true;
-  for (int y = blo; y <= bhi; ++y)
-    for (int x = blo; x <= bhi; ++x) {
-      const int32_t r = A[x][y];
-      const unsigned p = st_cell_off((unsigned)x, (unsigned)y) / 64u;
-      if (r < 0) continue;  // a hole: the tile's first row, all zeros (set above)
-      row[p] = r;
-      if (r >= out_rows) *interior = false;
-      if (x == blo || x == bhi || y == blo || y == bhi) continue;  // outermost ring: input only
-      if (r >= plan->n_rows) return false;  // a row that a step evaluates has no row of L~
-      const int32_t* c = cols + (size_t)r * W;
-      const float* v = vals + (size_t)r * W;
-      float* o = val + (size_t)p * ST_TABV;
-      unsigned seen = 0;
-      for (int j = 0; j < W; ++j) {
-        if (v[j] == 0.f) continue;
-        int d = -1;
-        if (c[j] == r) d = 0;
-        else {
-          const int cell = hget(c[j]);
-          if (cell < 0) return false;
-          const int dx = cell % S - x, dy = cell / S - y;
-          static const int ddx[8] = {-1, -1, 0, 1, 1, 1, 0, -1}, ddy[8] = {0, 1, 1, 1, 0, -1, -1, -1};  // = kDirX / kDirY
-          for (int q = 0; q < 8; ++q)
-            if (ddx[q] == dx && ddy[q] == dy) d = q + 1;
-          if (d < 0) return false;  // a non-zero that is not on one of the eight neighbouring cells
-        }
-        if (seen & (1u << d)) return false;
-        seen |= 1u << d;
-        o[d] = v[j];
-      }
-    }
-  return true;
-}
-
-// Steps of the busiest workgroup when the strip kernel deals `steps.size()` pairs x N maps the way cheb_strip5_kernel does:
-// items q = pair * N + map, a contiguous eighth of them per XCD, dealt to the XCD's workgroups in turn.
-static int strip_grid(int num_cu, int64_t n_items) { return (int)std::max<int64_t>(8, std::min<int64_t>(num_cu, (n_items + 7) / 8 * 8)); }
-static int64_t strip_makespan(const std::vector<int32_t>& steps, int64_t N, int num_cu) {
-  const int64_t Q = (int64_t)steps.size() * N;
-  const int G = strip_grid(num_cu, Q);
-  int64_t worst = 0;
-  std::vector<int64_t> load;
-  for (int xcd = 0; xcd < 8; ++xcd) {
-    const int nslots = (G + 7 - xcd) / 8;
-    const int64_t q0 = Q * xcd / 8, q1 = Q * (xcd + 1) / 8;
-    if (nslots <= 0 || q1 <= q0) continue;
-    load.assign((size_t)nslots, 0);
-    for (int64_t q = q0; q < q1; ++q) load[(size_t)((q - q0) % nslots)] += steps[(size_t)(q / N)];
-    for (int64_t v : load) worst = std::max(worst, v);
-  }
-  return worst;
-}
-
-constexpr int SMALL_MAP_TILES = 512;  // structured tiles up to which a plan without strips runs them in ONE launch (class-R tiles with tables)
-// Strip kernel: which class-R tiles it takes, and in what pieces.  The interior class-R tiles are covered by rectangles (in
-// the virtual Morton plane of the tile indices: tile t sits at (compress(t), compress(t >> 1))) of 3 to 5 tile columns and at
-// least 4 tile rows; a rectangle is cut into 32-column strips with 24 output columns each, two strips per workgroup item,
-// and into row segments sized so that the items fill the CUs evenly.  The other tiles stay with the tile kernels (`rest`).
-static void build_strips(const std::vector<int32_t>& r_interior, int D, int num_cu, const PlanOptions& opt,
-                         std::vector<StripPair>& pairs, std::vector<int32_t>& rest, int64_t* n_taken, std::vector<int32_t>& steps,
-                         std::vector<StripPair>& whole,  // whole: the same strips uncut along y (input-side strip kernel)
-                         std::vector<QStrip>* qstrips = nullptr) {  // quad-strip kernel
-  if (qstrips) qstrips->clear();
-  steps.clear();
-  pairs.clear();
-  whole.clear();
-  rest.clear();
-  *n_taken = 0;
-  struct Rect { int tx, ty, wt, ht; };
-  // columns of the tile plane and their vertical runs of class-R tiles
-  std::vector<uint64_t> keys(r_interior.size());  // (tx, ty)
-  for (size_t i = 0; i < r_interior.size(); ++i) {
-    const unsigned t = (unsigned)r_interior[i];
-    keys[i] = ((uint64_t)st_compress(t) << 32) | st_compress(t >> 1);
-  }
-  std::sort(keys.begin(), keys.end());
-  struct Run { int tx, y0, y1; bool used; };
-  std::vector<Run> runs;
-  for (size_t i = 0; i < keys.size();) {
-    const int tx = (int)(keys[i] >> 32), y0 = (int)(keys[i] & 0xffffffffu);
-    size_t j = i + 1;
-    while (j < keys.size() && (int)(keys[j] >> 32) == tx && (int)(keys[j] & 0xffffffffu) == y0 + (int)(j - i)) ++j;
-    runs.push_back({tx, y0, y0 + (int)(j - i), false});
-    i = j;
-  }
-  // Groups of 3 (at the end of a stretch: 4 or 5) adjacent columns whose runs share at least 4 rows: one rectangle each, of the
-  // shared rows.  (Three tile columns = 48 pixels = one pair of strips; tall rather than wide, the strips run along y.  On a
-  // full base pixel every column has the same run and nothing is left over; on a mask the rows a group does not share, and
-  // stretches of fewer than 3 columns, stay with the tile kernels.)
-  auto overlap = [](int a0, int a1, int b0, int b1, int* o0, int* o1) { *o0 = std::max(a0, b0); *o1 = std::min(a1, b1); return *o1 - *o0; };
-  const int min_rows = std::max(4, opt.strip_min_rows);  // (tuning, DSPH_OPT_STRIP_MINROWS: least height of a rectangle, in tiles)
-  std::vector<Rect> take;
-  for (size_t i = 0; i < runs.size(); ++i) {
-    if (runs[i].used) continue;
-    // how many adjacent columns continue this run with at least 4 shared rows (at most 6 looked at)
-    std::vector<size_t> chain{i};
-    int y0 = runs[i].y0, y1 = runs[i].y1;
-    while (chain.size() < 6) {
-      const int want = runs[chain.back()].tx + 1;
-      size_t best = runs.size();
-      int by0 = 0, by1 = 0;
-      for (size_t j = chain.back() + 1; j < runs.size() && runs[j].tx <= want; ++j) {
-        int o0, o1;
-        if (runs[j].tx == want && !runs[j].used && overlap(y0, y1, runs[j].y0, runs[j].y1, &o0, &o1) >= min_rows &&
-            (best == runs.size() || o1 - o0 > by1 - by0)) { best = j; by0 = o0; by1 = o1; }
-      }
-      if (best == runs.size()) break;
-      if (chain.size() < 5) { y0 = by0; y1 = by1; }  // (the sixth only says "the stretch goes on")
-      chain.push_back(best);
-    }
-    const int avail = (int)chain.size();
-    if (avail < 3 || y1 - y0 < min_rows) continue;  // stays with the tile kernels
-    const int w = avail >= 6 ? 3 : std::min(avail, 5);
-    // the shared rows of the w columns actually taken
-    y0 = runs[chain[0]].y0; y1 = runs[chain[0]].y1;
-    for (int c = 1; c < w; ++c) { int o0, o1; overlap(y0, y1, runs[chain[c]].y0, runs[chain[c]].y1, &o0, &o1); y0 = o0; y1 = o1; }
-    if (y1 - y0 < min_rows) continue;
-    take.push_back({runs[chain[0]].tx, y0, w, y1 - y0});
-    *n_taken += (int64_t)w * (y1 - y0);
-    for (int c = 0; c < w; ++c) {
-      Run& r = runs[chain[c]];
-      // what the rectangle leaves of the run: above / below stay as (used) leftovers for the tile kernels
-      for (int y = r.y0; y < r.y1; ++y)
-        if (y < y0 || y >= y1) rest.push_back((int32_t)st_morton((unsigned)r.tx, (unsigned)y));
-      r.used = true;
-    }
-  }
-  for (const Run& r : runs)
-    if (!r.used)
-      for (int y = r.y0; y < r.y1; ++y) rest.push_back((int32_t)st_morton((unsigned)r.tx, (unsigned)y));
-  std::sort(rest.begin(), rest.end());
-#ifdef DSPH_ABLATE  // (diagnostic build only: the shipped library reads no environment variable)
-  if (getenv("DSPH_STRIP_DEBUG")) {
-    long a3 = 0, a45 = 0;
-    int hmin = 1 << 30, hmax = 0;
-    for (const Rect& r : take) { (r.wt == 3 ? a3 : a45) += (long)r.wt * r.ht; hmin = std::min(hmin, r.ht); hmax = std::max(hmax, r.ht); }
-    fprintf(stderr, "build_strips: %zu rectangles (3 wide: %ld tiles, 4-5 wide: %ld tiles, heights %d..%d), %zu tiles left over\n",
-            take.size(), a3, a45, take.empty() ? 0 : hmin, hmax, rest.size());
-  }
-#endif
-  if (take.empty()) return;
-  // Segment height: every segment pays 2 D + 1 run-in rows, every workgroup should get the same number of steps.  Candidates
-  // from the whole rectangle down to 256 rows (measured on the partial sky of BASELINE configs[4], batch 16, strips forced:
-  // 23.0 ms with 64-row segments, 21.6 with 128, 21.3 with 256 and 512, 21.6 unsegmented; the tile kernels: 21.8); the one whose busiest workgroup has the fewest steps
-  // for ONE map wins -- a batch only evens things out further, items being (pair, map).
-  auto cut = [&](int h, std::vector<StripPair>& out) {
-    out.clear();
-    for (const Rect& r : take) {
-      const int X0 = 16 * r.tx, X1 = 16 * (r.tx + r.wt), Y0 = 16 * r.ty, Y1 = 16 * (r.ty + r.ht);
-      const int ns = (X1 - X0 + SP_USE - 1) / SP_USE;
-      const int H = Y1 - Y0, nseg = (H + h - 1) / h;
-      for (int sg = 0; sg < nseg; ++sg) {
-        const int ya = Y0 + (int)((int64_t)H * sg / nseg), yb = Y0 + (int)((int64_t)H * (sg + 1) / nseg);
-        for (int s0 = 0; s0 < ns; s0 += 2) {
-          StripPair p;
-          for (int e = 0; e < 2; ++e) {
-            const int s = s0 + e;
-            if (s < ns) {
-              p.x0[e] = X0 + SP_USE * s;
-              p.w[e] = std::min(SP_USE, X1 - p.x0[e]);
-            } else {
-              p.x0[e] = p.x0[0];
-              p.w[e] = 0;
-            }
-          }
-          p.y0 = ya;
-          p.y1 = yb;
-          p.xlo = X0 - D;
-          p.xhi = X1 - 1 + D;
-          for (int e = 0; e < 2; ++e)  // lane 0 of the strip: D columns left of the first output column, but never past the halo
-            p.xs[e] = std::min(p.x0[e] - D, p.xhi + 1 - SP_PX);
-          p.ylo = Y0 - D;
-          p.yhi = Y1 - 1 + D;
-          out.push_back(p);
-        }
-      }
-    }
-    // Items of unequal height (ragged masks): tallest first, then dealt over the eight XCD ranges of the kernel (a range is a
-    // contiguous eighth of the list), so that every XCD -- and, the kernel dealing a range to its workgroups in turn, every
-    // workgroup -- gets its share of tall and short ones.  Equal heights (a full sphere): the order of the cut stays,
-    // neighbours in x next to each other.
-    bool ragged = false;
-    for (const StripPair& p : out) ragged = ragged || (p.y1 - p.y0 != out[0].y1 - out[0].y0);
-    if (ragged) {
-      std::stable_sort(out.begin(), out.end(), [](const StripPair& a, const StripPair& b) { return a.y1 - a.y0 > b.y1 - b.y0; });
-      std::vector<StripPair> dealt;
-      dealt.reserve(out.size());
-      for (size_t x = 0; x < 8; ++x)
-        for (size_t i2 = x; i2 < out.size(); i2 += 8) dealt.push_back(out[i2]);
-      out.swap(dealt);
-    }
-  };
-  auto steps_of = [&](const std::vector<StripPair>& v, std::vector<int32_t>& st) {
-    st.resize(v.size());
-    for (size_t i2 = 0; i2 < v.size(); ++i2) st[i2] = (v[i2].y1 - v[i2].y0) + 2 * D + 1;
-  };
-  const int cand[] = {4096, 2048, 1024, 512, 384, 256};
-  int64_t best_span = -1;
-  int best_h = 256;
-  {
-    std::vector<StripPair> trial;
-    std::vector<int32_t> st;
-    for (int h : cand) {
-      cut(h, trial);
-      steps_of(trial, st);
-      const int64_t span = strip_makespan(st, 1, num_cu);
-      if (best_span < 0 || span < best_span) { best_span = span; best_h = h; }
-    }
-  }
-  if (opt.strip_seg > 0) best_h = std::max(16, opt.strip_seg);  // (tuning, DSPH_OPT_STRIP_SEG: the segment height, in rows)
-  cut(best_h, pairs);
-  steps_of(pairs, steps);
-  cut(1 << 30, whole);
-  // The quad strips: rectangles that stand side by side over the same rows become one (a full base pixel: one rectangle of all
-  // its interior columns), cut into strips of 56 output columns (the last one narrower), uncut along y.
-  if (qstrips && D == QS_D) {
-    std::vector<Rect> wide(take);
-    std::sort(wide.begin(), wide.end(), [](const Rect& a, const Rect& b) { return a.ty != b.ty ? a.ty < b.ty : (a.ht != b.ht ? a.ht < b.ht : a.tx < b.tx); });
-    std::vector<Rect> merged;
-    for (const Rect& r : wide) {
-      if (!merged.empty() && merged.back().ty == r.ty && merged.back().ht == r.ht && merged.back().tx + merged.back().wt == r.tx) merged.back().wt += r.wt;
-      else merged.push_back(r);
-    }
-    for (const Rect& r : merged) {
-      const int X0 = 16 * r.tx, X1 = 16 * (r.tx + r.wt), Y0 = 16 * r.ty, Y1 = 16 * (r.ty + r.ht);
-      for (int x0 = X0; x0 < X1; x0 += QS_USE) {
-        QStrip q{};
-        q.x0 = x0; q.w = std::min(QS_USE, X1 - x0); q.xs = x0 - D;
-        q.y0 = Y0; q.y1 = Y1;
-        q.xlo = X0 - D; q.xhi = X1 - 1 + D; q.ylo = Y0 - D; q.yhi = Y1 - 1 + D;
-        qstrips->push_back(q);
-      }
-    }
-  }
-#ifdef DSPH_ABLATE
-  if (getenv("DSPH_STRIP_DEBUG"))
-    fprintf(stderr, "build_strips: segments of %d rows, %zu pairs, busiest workgroup %ld / %ld / %ld steps for 1 / 4 / 16 maps; tile cost "
-            "per map in the same unit %ld\n", best_h, pairs.size(), (long)strip_makespan(steps, 1, num_cu), (long)strip_makespan(steps, 4, num_cu),
-            (long)strip_makespan(steps, 16, num_cu), (long)(*n_taken * 187 / (30 * num_cu)));
-#endif
-}
-
-
-// ---- table-addressed quad strips (round 6) ----------------------------------------------------------------------------------
-// A candidate tile of the logical grid: its eight neighbour TILES by direction (kDirX / kDirY order: W NW N NE E SE S SW), each
-// verified to continue this tile's own 16 x 16 Morton square by a pure translation over the D rows / columns a strip's halo
-// reaches into it.  Class R: the neighbours of the virtual Morton plane (what the classification verified).  Class T: read off
-// the embedding embed_tile() found and verified (row[] = the row of every plane cell).
-struct QCand {
-  int32_t tile;
-  int32_t nbr[8];
-  int32_t tix;       // position in the class-T list (tables), -1 for a class-R tile
-  int32_t sheet, u, v;
-  bool taken;
-  bool barred;       // stays with the tile kernels whatever the rectangles would gain (a cell no rectangle may cover)
-};
-
-static bool links_from_table(const int32_t* row, int D, int32_t ntiles, int32_t nbr[8]) {
-  static const int ddx[8] = {-1, -1, 0, 1, 1, 1, 0, -1}, ddy[8] = {0, 1, 1, 1, 0, -1, -1, -1};
-  for (int d = 0; d < 8; ++d) {
-    const int xa = ddx[d] < 0 ? ST_DMAX - D : (ddx[d] == 0 ? ST_DMAX : ST_DMAX + ST_TILE);
-    const int xb = ddx[d] < 0 ? ST_DMAX : (ddx[d] == 0 ? ST_DMAX + ST_TILE : ST_DMAX + ST_TILE + D);
-    const int ya = ddy[d] < 0 ? ST_DMAX - D : (ddy[d] == 0 ? ST_DMAX : ST_DMAX + ST_TILE);
-    const int yb = ddy[d] < 0 ? ST_DMAX : (ddy[d] == 0 ? ST_DMAX + ST_TILE : ST_DMAX + ST_TILE + D);
-    int64_t base = -1;
-    for (int y = ya; y < yb; ++y)
-      for (int x = xa; x < xb; ++x) {
-        const int64_t r = row[st_cell_off((unsigned)x, (unsigned)y) / 64u];
-        const int64_t b = r - (int64_t)st_morton((unsigned)(x - ST_DMAX) & 15u, (unsigned)(y - ST_DMAX) & 15u);
-        if (b < 0 || (b & (FUSED_P - 1)) != 0 || (base >= 0 && b != base)) return false;
-        base = b;
-      }
-    if (base < 0 || base / FUSED_P >= ntiles) return false;
-    nbr[d] = (int32_t)(base / FUSED_P);
-  }
-  return true;
-}
-
-// What a rectangle of w x h tiles saves against the tile kernels, in units of 0.1 us of one CU and one map (the constants of
-// strips_apply: 18.7 us per tile, 2.8 us per strip step): strips of 56 output columns, 2 D + 1 run-in steps each.
-// (the K = 8 strips -- cheb_qstrip8_kernel.h, D = 7 -- have 50 output columns, 16 run-in steps, ~2.6 us a step, against 27.5 us
-// per tile on the breadth-first tile kernel with its 7-ring halo)
-static int64_t qt_gain(int w, int h, int D) {
-  const int use = D == Q8_D ? Q8_USE : QS_PX - 2 * D;
-  const int64_t ns = (16 * (int64_t)w + use - 1) / use;
-  if (D == Q8_D) return (int64_t)w * h * 275 - ns * (16 * (int64_t)h + Q8_RUNIN) * 26;
-  // (a run of rows costs more than its 2 D + 1 run-in steps: two barriers and a waited-for first row before the loop, the step
-  // count rounded up to a multiple of three -- measured at the headline map, 254 strips against 216: about 14 steps a run)
-  return (int64_t)w * h * 187 - ns * (16 * (int64_t)h + 2 * D + 6) * 28;
-}
-
-// Rectangles of candidate tiles on the logical grid and their strips.  cands: every interior class-R tile and every eligible
-// interior class-T tile.  Out: strips (coordinates relative to the rectangle's table: the rectangle's first pixel is (16, 16)),
-// the tables, `taken` set in cands.
-static void build_qtstrips(std::vector<QCand>& cands, int32_t ntiles, int D, std::vector<QStrip>& strips, std::vector<int32_t>& tab,
-                           int64_t* n_taken) {
-  strips.clear();
-  tab.clear();
-  *n_taken = 0;
-  const int n = (int)cands.size();
-  if (n == 0) return;
-  std::vector<int32_t> cand_of((size_t)ntiles, -1);
-  for (int i = 0; i < n; ++i) cand_of[(size_t)cands[i].tile] = i;
-  static const int ddx[8] = {-1, -1, 0, 1, 1, 1, 0, -1}, ddy[8] = {0, 1, 1, 1, 0, -1, -1, -1};
-  auto cand_at = [&](int32_t tile) -> int { return tile >= 0 && tile < ntiles ? cand_of[(size_t)tile] : -1; };
-  // sheets: logical coordinates by breadth-first search over the four axis links that both ends agree on
-  std::unordered_map<uint64_t, int32_t> at;  // (sheet, u, v) -> candidate
-  constexpr int64_t OFF = 1 << 20;
-  auto key_of = [&](int32_t sheet, int64_t u, int64_t v) { return ((uint64_t)sheet << 44) | ((uint64_t)(u + OFF) << 22) | (uint64_t)(v + OFF); };
-  int32_t nsheets = 0;
-  std::vector<int32_t> queue;
-  for (int i = 0; i < n; ++i) cands[i].sheet = -1;
-  for (int i0 = 0; i0 < n; ++i0) {
-    if (cands[i0].sheet >= 0) continue;
-    if (nsheets >= (1 << 19)) break;
-    const int32_t sh = nsheets++;
-    cands[i0].sheet = sh; cands[i0].u = 0; cands[i0].v = 0;
-    at[key_of(sh, 0, 0)] = i0;
-    queue.assign(1, i0);
-    for (size_t h = 0; h < queue.size(); ++h) {
-      const QCand a = cands[(size_t)queue[h]];
-      for (int d = 0; d < 8; d += 2) {
-        const int b = cand_at(a.nbr[d]);
-        if (b < 0 || cands[(size_t)b].sheet >= 0 || cands[(size_t)b].nbr[(d + 4) & 7] != a.tile) continue;
-        const int64_t u = (int64_t)a.u + ddx[d], v = (int64_t)a.v + ddy[d];
-        if (u <= -OFF + 2 || u >= OFF - 2 || v <= -OFF + 2 || v >= OFF - 2) continue;
-        const uint64_t k = key_of(sh, u, v);
-        if (at.find(k) != at.end()) continue;  // (a sphere unrolled onto the plane meets itself again: the place is taken)
-        cands[(size_t)b].sheet = sh; cands[(size_t)b].u = (int32_t)u; cands[(size_t)b].v = (int32_t)v;
-        at[k] = b;
-        queue.push_back(b);
-      }
-    }
-  }
-  // per sheet: occupancy grid over the bounding box, greedy extraction of the rectangle with the largest gain
-  std::vector<std::vector<int32_t>> members((size_t)nsheets);
-  for (int i = 0; i < n; ++i)
-    if (cands[i].sheet >= 0) members[(size_t)cands[i].sheet].push_back(i);
-  for (int32_t sh = 0; sh < nsheets; ++sh) {
-    const std::vector<int32_t>& mem = members[(size_t)sh];
-    if (mem.size() < 6) continue;
-    int u0 = 1 << 30, u1 = -(1 << 30), v0 = 1 << 30, v1 = -(1 << 30);
-    for (int32_t i : mem) { u0 = std::min(u0, cands[(size_t)i].u); u1 = std::max(u1, cands[(size_t)i].u); v0 = std::min(v0, cands[(size_t)i].v); v1 = std::max(v1, cands[(size_t)i].v); }
-    const int64_t GW = (int64_t)u1 - u0 + 1, GH = (int64_t)v1 - v0 + 1;
-    if (GW * GH > (1ll << 26)) continue;  // (a sheet that sprawls: left to the tile kernels)
-    std::vector<int32_t> grid((size_t)(GW * GH), -1);  // candidate index, -1 empty, -2 blocked
-    for (int32_t i : mem) grid[(size_t)((cands[(size_t)i].v - v0) * GW + (cands[(size_t)i].u - u0))] = cands[(size_t)i].barred ? -2 : i;
-    std::vector<int32_t> hgt((size_t)GW);
-    std::vector<std::pair<int, int>> stack;  // (start column, height)
-    // (every extraction sweeps the sheet once: a budget of sweeps bounds the set-up time on ragged masks -- what is not taken
-    // by then stays with the tile kernels)
-    for (int64_t sweeps = 0; sweeps * GW * GH < (3ll << 28) && sweeps < 8192; ++sweeps) {
-      // the best (gain) rectangle of free cells: histogram of free runs along v, one sweep per row
-      int64_t best = 0;
-      int bu = 0, bv = 0, bw = 0, bh = 0;
-      std::fill(hgt.begin(), hgt.end(), 0);
-      for (int64_t y = 0; y < GH; ++y) {
-        for (int64_t x = 0; x < GW; ++x) hgt[(size_t)x] = grid[(size_t)(y * GW + x)] >= 0 ? hgt[(size_t)x] + 1 : 0;
-        stack.clear();
-        for (int64_t x = 0; x <= GW; ++x) {
-          const int hx = x < GW ? hgt[(size_t)x] : 0;
-          int start = (int)x;
-          while (!stack.empty() && stack.back().second > hx) {
-            const int s0 = stack.back().first, hh = stack.back().second;
-            stack.pop_back();
-            const int wmax = (int)x - s0;
-            // the widest rectangle of this height, or one a few columns narrower where the last strip would be nearly empty
-            for (int w = std::min(wmax, 1000); w >= std::max(1, std::min(wmax, 1000) - 3); --w) {  // (1,000: the kernels keep a tile column in ten bits)
-              const int64_t g = qt_gain(w, hh, D);
-              if (g > best) { best = g; bu = s0; bv = (int)y - hh + 1; bw = w; bh = hh; }
-            }
-            start = s0;
-          }
-          if (hx > 0 && (stack.empty() || stack.back().second < hx)) stack.push_back({start, hx});
-        }
-      }
-      if (best <= 0) break;
-      // the table of tile bases: the rectangle and one ring of tiles around it
-      const int TW = bw + 2, TH = bh + 2;
-      std::vector<int32_t> t((size_t)TW * TH, -1);
-      bool good = true;
-      auto inside = [&](int i, int j) { return i >= 1 && i <= bw && j >= 1 && j <= bh; };
-      for (int j = 1; j <= bh && good; ++j)
-        for (int i = 1; i <= bw && good; ++i) {
-          const int32_t c = grid[(size_t)((bv + j - 1) * GW + (bu + i - 1))];
-          const QCand& q = cands[(size_t)c];
-          t[(size_t)j * TW + i] = q.tile;
-          for (int d = 0; d < 8 && good; ++d) {
-            const int i2 = i + ddx[d], j2 = j + ddy[d];
-            int32_t& slot = t[(size_t)j2 * TW + i2];
-            if (inside(i2, j2)) {  // the neighbour inside the rectangle must be the tile the grid holds there
-              const int32_t c2 = grid[(size_t)((bv + j2 - 1) * GW + (bu + i2 - 1))];
-              if (cands[(size_t)c2].tile != q.nbr[d]) good = false;
-            } else if (slot < 0) slot = q.nbr[d];
-            else if (slot != q.nbr[d]) good = false;  // two tiles of the rectangle name different tiles for one place of the ring
-          }
-        }
-      if (!good) {  // (a seam the sheet's coordinates paper over: these tiles stay with the tile kernels)
-        for (int j = 0; j < bh; ++j)
-          for (int i = 0; i < bw; ++i) grid[(size_t)((bv + j) * GW + (bu + i))] = -2;
-        continue;
-      }
-      const int32_t toff = (int32_t)tab.size();
-      for (int32_t tile : t) tab.push_back(tile < 0 ? 0 : tile * FUSED_P);  // (the four corners of the ring of a 1-wide rectangle ... are never -1: every ring place has a neighbour inside)
-      for (int j = 0; j < bh; ++j)
-        for (int i = 0; i < bw; ++i) {
-          int32_t& c = grid[(size_t)((bv + j) * GW + (bu + i))];
-          cands[(size_t)c].taken = true;
-          c = -2;
-        }
-      *n_taken += (int64_t)bw * bh;
-      const int X0 = 16, X1 = 16 + 16 * bw, Y0 = 16, Y1 = 16 + 16 * bh;
-      // output columns of a strip, and how far left of the first one its lane 0 stands: the kernels take a lane's four pixels
-      // for one aligned group of four inside one tile, so both are multiples of four (D = 7: 48 columns behind 8 of lead-in)
-      const int use = D == Q8_D ? Q8_USE : QS_PX - 2 * D, lead = D == Q8_D ? 8 : D;
-      for (int x0 = X0; x0 < X1; x0 += use) {
-        QStrip q{};
-        q.x0 = x0; q.w = std::min(use, X1 - x0); q.xs = x0 - lead;
-        q.y0 = Y0; q.y1 = Y1;
-        q.xlo = X0 - D; q.xhi = X1 - 1 + D; q.ylo = Y0 - D; q.yhi = Y1 - 1 + D;
-        q.tab = toff; q.tws = TW;
-        strips.push_back(q);
-      }
-    }
-  }
-  // The kernel cuts the tape of all strips' rows into equal pieces, and a piece pays 2 D + 1 run-in steps for every strip that
-  // begins in it: the greedy extraction leaves the low strips (a few tiles high) at the end of the list, where a piece would
-  // hold dozens of them (measured at the headline map: the last pieces took 14 % longer than the first, and the forward with
-  // them).  So the low strips are dealt out evenly between the tall ones, by rows.
-  {
-    std::vector<QStrip> tall, low;
-    int64_t rows_tall = 0, rows_low = 0;
-    for (const QStrip& q : strips) {
-      if (q.y1 - q.y0 >= 256) { tall.push_back(q); rows_tall += q.y1 - q.y0; }
-      else { low.push_back(q); rows_low += q.y1 - q.y0; }
-    }
-    if (!tall.empty() && !low.empty()) {
-      strips.clear();
-      size_t li = 0;
-      int64_t done_tall = 0, done_low = 0;
-      for (const QStrip& q : tall) {
-        strips.push_back(q);
-        done_tall += q.y1 - q.y0;
-        while (li < low.size() && done_low * rows_tall < rows_low * done_tall) {
-          strips.push_back(low[li]);
-          done_low += low[li].y1 - low[li].y0;
-          ++li;
-        }
-      }
-      for (; li < low.size(); ++li) strips.push_back(low[li]);
-    }
-  }
-}
-
-// Breadth-first rings of every tile; uploads the tables.  Returns a reference to the cached entry.
-// full: BFS tables of every tile (planes / weight-gradient modes of the BFS kernel); otherwise the tiles are first
-// classified and only the class-G ones (not a plain 2-D stencil square) get BFS tables, the rest go to d_rlist.
-static const FusedTiles& get_tiles(const dsph_plan* plan, int D, bool full = false) {
-  FusedPlan* fp = plan->fused;
-  std::lock_guard<std::mutex> lock(fp->mu);
-  DeviceGuard guard(plan->device);  // tables live on the plan's device, whatever the caller's current one is
-  const int key = 2 * D + (full ? 1 : 0);
-  auto it = fp->by_depth.find(key);
-  if (it != fp->by_depth.end()) return it->second;
-  if (fp->host_released) {  // the ELL arrays are gone: report "not tileable" without caching anything
-    static const FusedTiles none;
-    return none;
-  }
-  if (fp->wide && !(D == 1 && full)) {  // a wide graph has the tiled step's tables and nothing else
-    static const FusedTiles none;
-    return none;
-  }
-  FusedTiles& ft = fp->by_depth[key];
-  ft.D = D;
-  ft.width = fp->wide ? tstep_width(plan->width) : template_width(plan->width);
-  const int W = plan->width, WT = ft.width;
-  const int64_t out_rows = plan->levels.empty() ? plan->n_rows : plan->levels[0];
-  const int64_t nt64 = (out_rows + FUSED_P - 1) / FUSED_P;
-  if (D < 1 || D > FUSED_DMAX || nt64 > (1 << 30)) return ft;
-  const int ntiles = (int)nt64;
-  const int32_t* cols = fp->h_cols.data();
-  const float* vals = fp->h_vals.data();
-
-  std::vector<int32_t> stamp((size_t)plan->n_cols, -1), local((size_t)plan->n_cols, 0);
-  std::vector<int32_t> tile_off((size_t)ntiles + 1, 0), ring_end((size_t)ntiles * (FUSED_DMAX + 1), 0);
-  std::vector<int64_t> ell_off((size_t)ntiles, 0);
-  std::vector<int32_t> region;
-  std::vector<uint16_t> lcols;
-  std::vector<float> lvals;
-  region.reserve((size_t)ntiles * 600);
-  std::vector<int32_t> ring, next, interior, boundary, r_interior, r_boundary;
-  std::vector<unsigned char> cls((size_t)ntiles, 0);
-  if (!full && D <= ST_DMAX && plan->opt.use_struct) {
-    if (!fp->rows_tried) {
-      fp->rows_tried = true;
-      if (struct_build_rows(plan, &fp->d_gvals8, &fp->d_gdiag, &fp->d_rowflag) != DSPH_OK) {
-        if (fp->d_gvals8) (void)hipFree(fp->d_gvals8);
-        if (fp->d_gdiag) (void)hipFree(fp->d_gdiag);
-        if (fp->d_rowflag) (void)hipFree(fp->d_rowflag);
-        fp->d_gvals8 = fp->d_gdiag = nullptr;
-        fp->d_rowflag = nullptr;
-      }
-    }
-    if (fp->d_rowflag && struct_classify_tiles(plan, fp->d_rowflag, ntiles, D, out_rows, cls.data()) != DSPH_OK)
-      std::fill(cls.begin(), cls.end(), 0);
-  }
-  // K = 8 quad strips: which tiles' 7-ring regions are regular squares of the Morton plane (the same row flags, a deeper ring).
-  // Every tile still gets its breadth-first tables (other shapes and the weight gradient run on them).  On a sharded plan
-  // the candidates are the INTERIOR tiles (region inside the rank's own rows): they run with the interior part of a forward.
-  std::vector<unsigned char> cls8;
-  if (D == Q8_D && plan->opt.use_struct && plan->opt.strips != 2 && plan->opt.strip_form == 0 && !fp->wide) {
-    if (!fp->rows_tried) {
-      fp->rows_tried = true;
-      if (struct_build_rows(plan, &fp->d_gvals8, &fp->d_gdiag, &fp->d_rowflag) != DSPH_OK) {
-        if (fp->d_gvals8) (void)hipFree(fp->d_gvals8);
-        if (fp->d_gdiag) (void)hipFree(fp->d_gdiag);
-        if (fp->d_rowflag) (void)hipFree(fp->d_rowflag);
-        fp->d_gvals8 = fp->d_gdiag = nullptr;
-        fp->d_rowflag = nullptr;
-      }
-    }
-    if (fp->d_rowflag) {
-      cls8.assign((size_t)ntiles, 0);
-      if (struct_classify_tiles(plan, fp->d_rowflag, ntiles, D, out_rows, cls8.data(), Q8_D) != DSPH_OK) cls8.clear();
-    }
-  }
-  // class-T candidates: whatever the classification left over, when the structured kernel is in play at all
-  const bool try_tables = !full && D <= ST_DMAX && plan->opt.use_struct && plan->opt.use_tables && fp->d_rowflag != nullptr;
-  std::vector<int32_t> t_interior, t_boundary, trow_i, trow_b, e_row(ST_CELLS), h_key, h_slot;
-  std::vector<float> tval_i, tval_b, e_val((size_t)ST_CELLS * ST_TABV);
-  int rmax = 0, emax = 0;
-  int64_t ell_rows = 0;
-  for (int t = 0; t < ntiles; ++t) {
-    const int64_t r0 = (int64_t)t * FUSED_P, r1 = std::min<int64_t>(out_rows, r0 + FUSED_P);
-    const size_t base = region.size();
-    if (base > 0x7fffffffULL - 70000) return ft;  // offsets are int32
-    tile_off[t] = (int32_t)base;
-    if (cls[t] & 1) {  // class R: no BFS tables
-      ((cls[t] & 2) ? r_interior : r_boundary).push_back(t);
-      ell_off[t] = ell_rows;
-      continue;
-    }
-    if (try_tables) {  // class T: the structured kernel with per-tile tables
-      bool inner = false;
-      if (embed_tile(plan, cols, vals, W, t, D, out_rows, e_row.data(), e_val.data(), &inner, h_key, h_slot)) {
-        std::vector<int32_t>& lst = inner ? t_interior : t_boundary;
-        std::vector<int32_t>& rw = inner ? trow_i : trow_b;
-        std::vector<float>& vl = inner ? tval_i : tval_b;
-        lst.push_back(t);
-        rw.insert(rw.end(), e_row.begin(), e_row.end());
-        vl.insert(vl.end(), e_val.begin(), e_val.end());
-        ell_off[t] = ell_rows;
-        continue;
-      }
-    }
-    ring.clear();
-    for (int64_t r = r0; r < r1; ++r) {
-      stamp[r] = t;
-      local[r] = (int32_t)(r - r0);
-      ring.push_back((int32_t)r);
-      region.push_back((int32_t)r);
-    }
-    int32_t* re = &ring_end[(size_t)t * (FUSED_DMAX + 1)];
-    re[0] = (int32_t)ring.size();
-    for (int d = 1; d <= D; ++d) {
-      next.clear();
-      for (int32_t r : ring) {
-        if (r >= plan->n_rows) return ft;  // a row that must be computed has no ELL row
-        const int32_t* c = cols + (size_t)r * W;
-        const float* v = vals + (size_t)r * W;
-        for (int j = 0; j < W; ++j) {
-          if (v[j] == 0.f) continue;
-          const int32_t cj = c[j];
-          if (stamp[cj] != t) {
-            stamp[cj] = t;
-            next.push_back(cj);
-          }
-        }
-      }
-      std::sort(next.begin(), next.end());
-      // Emit the ring so that (local index & 3) == (row id & 3) wherever possible.  On a HEALPix map
-      // the low two NEST bits are the pixel's (x, y) parity; the recurrence reads the j-th neighbours
-      // of four rows with four different parities in one LDS access group, and those neighbours then
-      // sit in four different bank quarters -- halo rows included, not only the tile's own rows.
-      {
-        std::vector<int32_t> bucket[4];
-        for (int32_t r : next) bucket[r & 3].push_back(r);
-        size_t head[4] = {0, 0, 0, 0};
-        size_t left = next.size();
-        next.clear();
-        while (left > 0) {
-          const int want = (int)((region.size() - base + next.size()) & 3);
-          int take = want;
-          if (head[take] >= bucket[take].size()) {  // that parity is used up: take from the fullest
-            size_t best = 0;
-            for (int q = 0; q < 4; ++q) {
-              const size_t rem = bucket[q].size() - head[q];
-              if (rem > best) { best = rem; take = q; }
-            }
-          }
-          next.push_back(bucket[take][head[take]++]);
-          --left;
-        }
-      }
-      for (int32_t r : next) {
-        local[r] = (int32_t)(region.size() - base);
-        region.push_back(r);
-      }
-      re[d] = (int32_t)(region.size() - base);
-      ring.swap(next);
-    }
-    for (int d = D + 1; d <= FUSED_DMAX; ++d) re[d] = re[D];
-    const int R = re[D], E = re[D - 1];
-    {
-      bool inner = true;
-      for (size_t i = base; i < region.size() && inner; ++i) inner = region[i] < out_rows;
-      (inner ? interior : boundary).push_back(t);
-    }
-    if (R > 65535) return ft;  // uint16 local columns
-    rmax = std::max(rmax, R);
-    emax = std::max(emax, E);
-    // tile-local ELL of the rows within D-1 hops, stored [slot][row]
-    ell_off[t] = ell_rows;
-    const size_t lbase = lcols.size();
-    lcols.resize(lbase + (size_t)E * WT, 0);
-    lvals.resize(lbase + (size_t)E * WT, 0.f);
-    for (int i = 0; i < E; ++i) {
-      const int32_t r = region[base + i];
-      if (r >= plan->n_rows) return ft;
-      const int32_t* c = cols + (size_t)r * W;
-      const float* v = vals + (size_t)r * W;
-      if (fp->wide) {
-        // The tiled step (cheb_tstep.hip) reads slot j of four consecutive rows in one 16-lane LDS access: conflict-free when
-        // the four neighbours' local indices differ mod 4.  So the slots of a row are dealt by residue: slot j of local row i
-        // takes a neighbour with (local index & 3) == ((i + j) & 3) while there is one, else one from the fullest residue
-        // class (the sum's ORDER changes, not its terms).
-        std::vector<std::pair<uint16_t, float>> bucket[4];
-        for (int j = 0; j < W; ++j)
-          if (v[j] != 0.f) bucket[local[c[j]] & 3].push_back({(uint16_t)local[c[j]], v[j]});
-        size_t head[4] = {0, 0, 0, 0};
-        for (int j = 0; j < WT; ++j) {
-          int b = (i + j) & 3;
-          if (head[b] >= bucket[b].size()) {
-            size_t best = 0;
-            int bb = -1;
-            for (int q = 0; q < 4; ++q)
-              if (bucket[q].size() - head[q] > best) { best = bucket[q].size() - head[q]; bb = q; }
-            b = bb;
-          }
-          uint16_t lc = (uint16_t)i;
-          float lv = 0.f;
-          if (b >= 0) {
-            lc = bucket[b][head[b]].first;
-            lv = bucket[b][head[b]].second;
-            ++head[b];
-          } else {
-            const int want = (i & ~3) | ((i + j) & 3);  // padding: a row of this quad with the slot's residue (value 0)
-            lc = (uint16_t)(want < R ? want : i);
-          }
-          lcols[lbase + (size_t)j * E + i] = lc;
-          lvals[lbase + (size_t)j * E + i] = lv;
-        }
-        continue;
-      }
-      for (int j = 0; j < WT; ++j) {
-        uint16_t lc = (uint16_t)i;
-        float lv = 0.f;
-        if (j < W && v[j] != 0.f) {
-          lc = (uint16_t)local[c[j]];
-          lv = v[j];
-        }
-        lcols[lbase + (size_t)j * E + i] = lc;
-        lvals[lbase + (size_t)j * E + i] = lv;
-      }
-    }
-    ell_rows += E;
-  }
-  tile_off[ntiles] = (int32_t)region.size();
-  ft.ntiles = ntiles;
-  ft.rmax = std::max((rmax + 15) / 16 * 16, FUSED_P);
-  ft.emax = emax;
-
-  auto up = [](void** dst, const void* src, size_t bytes) -> bool {
-    if (bytes == 0) bytes = 16;
-    if (hipMalloc(dst, bytes) != hipSuccess) return false;
-    return hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice) == hipSuccess;
-  };
-  if (lcols.empty()) { lcols.push_back(0); lvals.push_back(0.f); }
-  // Small maps (BASELINE configs[0]: nside 64, 192 tiles -- 48 class R, 120 class T, 24 class G) are bound by launches, not by
-  // work: every structured tile fits the device at once, and two launches (class R, then class T) take twice as long as one.
-  // Where the strips take nothing anyway, the class-R tiles get tables too and join the class-T launch.
-  if (try_tables && D <= SP_DMAX && !(r_interior.empty() && r_boundary.empty()) &&
-      r_interior.size() + r_boundary.size() + t_interior.size() + t_boundary.size() <= (size_t)SMALL_MAP_TILES) {
-    int64_t taken = 0;
-    if (plan->opt.strips != 2) {
-      std::vector<StripPair> p0, ip0;
-      std::vector<int32_t> rest0, steps0;
-      build_strips(r_interior, D, fp->num_cu, plan->opt, p0, rest0, &taken, steps0, ip0);
-    }
-    if (taken == 0) {
-      std::vector<int32_t> keep_i, keep_b;
-      for (int pass = 0; pass < 2; ++pass) {
-        for (int32_t t : pass == 0 ? r_interior : r_boundary) {
-          bool inner = false;
-          if (embed_tile(plan, cols, vals, W, t, D, out_rows, e_row.data(), e_val.data(), &inner, h_key, h_slot)) {
-            (pass == 0 ? t_interior : t_boundary).push_back(t);
-            std::vector<int32_t>& rw = pass == 0 ? trow_i : trow_b;
-            std::vector<float>& vl = pass == 0 ? tval_i : tval_b;
-            rw.insert(rw.end(), e_row.begin(), e_row.end());
-            vl.insert(vl.end(), e_val.begin(), e_val.end());
-          } else {
-            (pass == 0 ? keep_i : keep_b).push_back(t);
-          }
-        }
-      }
-      r_interior.swap(keep_i);
-      r_boundary.swap(keep_b);
-    }
-  }
-  std::vector<int32_t> all_tiles;  // every tile, whatever its class: interior ones first
-  all_tiles.insert(all_tiles.end(), r_interior.begin(), r_interior.end());
-  all_tiles.insert(all_tiles.end(), t_interior.begin(), t_interior.end());
-  all_tiles.insert(all_tiles.end(), interior.begin(), interior.end());
-  ft.n_all_interior = (int)all_tiles.size();
-  all_tiles.insert(all_tiles.end(), r_boundary.begin(), r_boundary.end());
-  all_tiles.insert(all_tiles.end(), t_boundary.begin(), t_boundary.end());
-  all_tiles.insert(all_tiles.end(), boundary.begin(), boundary.end());
-  ft.n_all = (int)all_tiles.size();
-  if (all_tiles.empty()) all_tiles.push_back(0);
-  ft.n_interior = (int)interior.size();
-  interior.insert(interior.end(), boundary.begin(), boundary.end());
-  ft.n_part = (int)interior.size();
-  if (interior.empty()) interior.push_back(0);
-  std::vector<StripPair> pairs, ipairs;
-  std::vector<int32_t> rrest;
-  ft.n_strip_tiles = 0;
-  ft.strip_steps.clear();
-  ft.strip_span.clear();
-  ft.strip_forced = plan->opt.strips == 1;
-  std::vector<QStrip> qstrips;
-  if (!full && D <= SP_DMAX && plan->opt.strips != 2)
-    build_strips(r_interior, D, fp->num_cu, plan->opt, pairs, rrest, &ft.n_strip_tiles, ft.strip_steps, ipairs, nullptr);
-  else
-    rrest = r_interior;
-  // The quad strips (K = 5): rectangles on the logical tile grid, addressed through tables (build_qtstrips) -- every interior
-  // class-R tile and every interior class-T tile whose eight neighbour tiles are pure translations.
-  std::vector<int32_t> qtab, qrrest, qt_list, qt_rows;
-  std::vector<float> qt_vals;
-  std::vector<int32_t> patch_rows;
-  std::vector<float> patch_vals;
-  ft.n_qstrip_tiles = 0;
-  if (!full && D == QS_D && plan->opt.strips != 2 && plan->opt.strip_form == 0 && fp->d_gvals8 != nullptr) {
-    std::vector<QCand> cands;
-    cands.reserve(r_interior.size() + t_interior.size());
-    static const int ddx[8] = {-1, -1, 0, 1, 1, 1, 0, -1}, ddy[8] = {0, 1, 1, 1, 0, -1, -1, -1};
-    for (int32_t t : r_interior) {
-      QCand c{};
-      c.tile = t; c.tix = -1; c.taken = false;
-      const int tx = (int)st_compress((unsigned)t), ty = (int)st_compress((unsigned)t >> 1);
-      for (int d = 0; d < 8; ++d) {
-        const int nx = tx + ddx[d], ny = ty + ddy[d];
-        const int64_t nt = nx < 0 || ny < 0 ? -1 : (int64_t)st_morton((unsigned)nx, (unsigned)ny);
-        c.nbr[d] = nt >= 0 && nt < ntiles ? (int32_t)nt : -1;
-      }
-      cands.push_back(c);
-    }
-    const size_t n_rc = cands.size();
-    // The kernel does not clamp a row to the strip's halo (cheb_qstrip_kernel.h, "rows need no clamp"): past the halo it reads
-    // rows of the table's ring tiles that feed nothing -- rows that must exist.  The one tile whose rows may not is the map's
-    // last, incomplete one: no tile beside it is a candidate, so it is in no rectangle's ring.
-    const int32_t ragged = out_rows % FUSED_P != 0 ? ntiles - 1 : -1;
-    auto beside_ragged = [&](const QCand& c) {
-      if (ragged < 0) return false;
-      if (c.tile == ragged) return true;
-      for (int d = 0; d < 8; ++d)
-        if (c.nbr[d] == ragged) return true;
-      return false;
-    };
-#ifdef DSPH_ABLATE  // (diagnostic build only -- make ABLATE=1: the shipped library reads no environment variable)
-    const bool only_r = getenv("DSPH_QT_ONLY_R") != nullptr;  // (the strips of round 5's tile set on this round's kernel: tools/ab_r5_r6.sh)
-#else
-    const bool only_r = false;
-#endif
-    for (size_t i = 0; i < t_interior.size() && !only_r; ++i) {
-      QCand c{};
-      c.tile = t_interior[i]; c.tix = (int32_t)i; c.taken = false;
-      if (links_from_table(&trow_i[i * ST_CELLS], D, ntiles, c.nbr)) cands.push_back(c);
-    }
-    for (QCand& c : cands) c.barred = beside_ragged(c);
-    build_qtstrips(cands, ntiles, D, qstrips, qtab, &ft.n_qstrip_tiles);
-    std::vector<unsigned char> t_taken(t_interior.size(), 0);
-    for (size_t i = 0; i < cands.size(); ++i) {
-      if (i < n_rc) { if (!cands[i].taken) qrrest.push_back(cands[i].tile); }
-      else if (cands[i].taken) t_taken[(size_t)cands[i].tix] = 1;
-    }
-    // (r_interior is sorted; cands keeps its order)
-    ft.n_qrrest_interior = (int)qrrest.size();
-    qrrest.insert(qrrest.end(), r_boundary.begin(), r_boundary.end());
-    for (size_t i = 0; i < t_interior.size(); ++i) {
-      if (!t_taken[i]) {
-        qt_list.push_back(t_interior[i]);
-        qt_rows.insert(qt_rows.end(), trow_i.begin() + i * ST_CELLS, trow_i.begin() + (i + 1) * ST_CELLS);
-        qt_vals.insert(qt_vals.end(), tval_i.begin() + i * ST_CELLS * ST_TABV, tval_i.begin() + (i + 1) * ST_CELLS * ST_TABV);
-        continue;
-      }
-      // a class-T tile on the strips: the strips read L~ by direction from gvals8 / gdiag, which the row pass filled from
-      // the VIRTUAL Morton plane (a neighbour beyond a base-pixel border has no direction there and was dropped).  The
-      // tile's verified embedding has every evaluated row's values by direction: written over the rows' entries (no other
-      // kernel reads them for rows that are irregular in the virtual plane; for regular rows the two agree).
-      const int blo = ST_DMAX - D + 1, bhi = ST_DMAX + ST_TILE - 1 + D - 1;  // rings 0 .. D-1
-      for (int y = blo; y <= bhi; ++y)
-        for (int x = blo; x <= bhi; ++x) {
-          const size_t cell = i * ST_CELLS + st_cell_off((unsigned)x, (unsigned)y) / 64u;
-          patch_rows.push_back(trow_i[cell]);
-          patch_vals.insert(patch_vals.end(), tval_i.begin() + cell * ST_TABV, tval_i.begin() + cell * ST_TABV + 9);
-        }
-    }
-    ft.n_qt_interior = (int)qt_list.size();
-    qt_list.insert(qt_list.end(), t_boundary.begin(), t_boundary.end());
-    qt_rows.insert(qt_rows.end(), trow_b.begin(), trow_b.end());
-    qt_vals.insert(qt_vals.end(), tval_b.begin(), tval_b.end());
-  }
-  // K = 8: rectangles of the depth-7 regular tiles (virtual Morton neighbours: what the classification verified)
-  std::vector<QStrip> q8strips;
-  std::vector<int32_t> q8tab, q8rest;
-  ft.n_q8_tiles = 0;
-  if (!cls8.empty()) {
-    std::vector<QCand> cands;
-    static const int ddx[8] = {-1, -1, 0, 1, 1, 1, 0, -1}, ddy[8] = {0, 1, 1, 1, 0, -1, -1, -1};
-    for (int32_t t = 0; t < ntiles; ++t) {
-      if ((cls8[(size_t)t] & 3) != 3) continue;
-      QCand c{};
-      c.tile = t; c.tix = -1; c.taken = false;
-      const int tx = (int)st_compress((unsigned)t), ty = (int)st_compress((unsigned)t >> 1);
-      for (int d = 0; d < 8; ++d) {
-        const int nx = tx + ddx[d], ny = ty + ddy[d];
-        const int64_t nt = nx < 0 || ny < 0 ? -1 : (int64_t)st_morton((unsigned)nx, (unsigned)ny);
-        c.nbr[d] = nt >= 0 && nt < ntiles ? (int32_t)nt : -1;
-      }
-      cands.push_back(c);
-    }
-    build_qtstrips(cands, ntiles, D, q8strips, q8tab, &ft.n_q8_tiles);
-    std::vector<unsigned char> took((size_t)ntiles, 0);
-    for (const QCand& c : cands)
-      if (c.taken) took[(size_t)c.tile] = 1;
-    for (int i = 0; i < ft.n_part; ++i) {
-      if (i == ft.n_interior) ft.n_q8rest_interior = (int)q8rest.size();
-      if (!took[(size_t)interior[(size_t)i]]) q8rest.push_back(interior[(size_t)i]);
-    }
-    if (ft.n_interior >= ft.n_part) ft.n_q8rest_interior = (int)q8rest.size();
-  }
-  ft.n_q8strips = (int)q8strips.size();
-  ft.h_q8strips = q8strips;
-  ft.h_q8tab = q8tab;
-  ft.n_q8rest = (int)q8rest.size();
-  std::vector<int32_t> q8prefix(1, 0);
-  for (const QStrip& q : q8strips) q8prefix.push_back(q8prefix.back() + (q.y1 - q.y0));
-  ft.q8tape_rows = q8prefix.back();
-  if (q8strips.empty()) q8strips.push_back(QStrip());
-  if (q8rest.empty()) q8rest.push_back(0);
-  q8tab.resize(q8tab.size() + 8, 0);
-  ft.n_qrrest = (int)qrrest.size();
-  ft.n_qt = (int)qt_list.size();
-  if (qrrest.empty()) qrrest.push_back(0);
-  if (qt_list.empty()) { qt_list.push_back(0); qt_rows.push_back(0); qt_vals.push_back(0.f); }
-  ft.h_qtab = qtab;
-  qtab.resize(qtab.size() + 8, 0);  // (a lane's five tile columns are read by scalar loads from the strip's first column on: readable past the end)
-  ft.n_pairs = (int)pairs.size();
-  ft.h_pairs = pairs;
-  ft.n_qstrips = (int)qstrips.size();
-  ft.h_qstrips = qstrips;
-  std::vector<int32_t> qprefix(1, 0);
-  for (const QStrip& q : qstrips) qprefix.push_back(qprefix.back() + (q.y1 - q.y0));
-  ft.qtape_rows = qprefix.back();
-  if (qstrips.empty()) qstrips.push_back(QStrip());
-  ft.n_ipairs = (int)ipairs.size();
-  ft.ipair_h.clear();
-  ft.ipair_second.clear();
-  ft.iseg.clear();
-  for (const StripPair& ip : ipairs) {
-    ft.ipair_h.push_back(ip.y1 - ip.y0);
-    ft.ipair_second.push_back(ip.w[1] > 0 ? 1 : 0);
-  }
-  if (ipairs.empty()) ipairs.push_back(StripPair());
-  ft.n_rrest_interior = (int)rrest.size();
-  rrest.insert(rrest.end(), r_boundary.begin(), r_boundary.end());
-  ft.n_rrest = (int)rrest.size();
-  // every tile the QUAD strips leave over, whatever its class
-  std::vector<int32_t> nonq(qrrest.begin(), qrrest.begin() + ft.n_qrrest);
-  nonq.insert(nonq.end(), qt_list.begin(), qt_list.begin() + ft.n_qt);
-  if (ft.n_qstrip_tiles == 0) {  // (no quad strips: the list is not used; keep it the complement of nothing)
-    nonq.assign(r_interior.begin(), r_interior.end());
-    nonq.insert(nonq.end(), r_boundary.begin(), r_boundary.end());
-    nonq.insert(nonq.end(), t_interior.begin(), t_interior.end());
-    nonq.insert(nonq.end(), t_boundary.begin(), t_boundary.end());
-  }
-  nonq.insert(nonq.end(), interior.begin(), interior.begin() + ft.n_part);
-  ft.n_nonq = (int)nonq.size();
-  if (nonq.empty()) nonq.push_back(0);
-  if (rrest.empty()) rrest.push_back(0);
-  if (pairs.empty()) pairs.push_back(StripPair());
-  ft.n_r_interior = (int)r_interior.size();
-  r_interior.insert(r_interior.end(), r_boundary.begin(), r_boundary.end());
-  ft.n_r = (int)r_interior.size();
-  if (r_interior.empty()) r_interior.push_back(0);
-  ft.n_t_interior = (int)t_interior.size();
-  t_interior.insert(t_interior.end(), t_boundary.begin(), t_boundary.end());
-  trow_i.insert(trow_i.end(), trow_b.begin(), trow_b.end());
-  tval_i.insert(tval_i.end(), tval_b.begin(), tval_b.end());
-  ft.n_t = (int)t_interior.size();
-  if (t_interior.empty()) { t_interior.push_back(0); trow_i.push_back(0); tval_i.push_back(0.f); }
-  bool good = up((void**)&ft.d_tlist, t_interior.data(), t_interior.size() * 4) &&
-              up((void**)&ft.d_tabrow, trow_i.data(), trow_i.size() * 4) &&
-              up((void**)&ft.d_tabvals, tval_i.data(), tval_i.size() * 4) &&
-              up((void**)&ft.d_tile_off, tile_off.data(), tile_off.size() * 4) &&
-              up((void**)&ft.d_ring_end, ring_end.data(), ring_end.size() * 4) &&
-              up((void**)&ft.d_ell_off, ell_off.data(), ell_off.size() * 8) &&
-              up((void**)&ft.d_region, region.data(), region.size() * 4) &&
-              up((void**)&ft.d_lcols, lcols.data(), lcols.size() * 2) &&
-              up((void**)&ft.d_lvals, lvals.data(), lvals.size() * 4) &&
-              up((void**)&ft.d_part, interior.data(), interior.size() * 4) &&
-              up((void**)&ft.d_rlist, r_interior.data(), r_interior.size() * 4) &&
-              up((void**)&ft.d_rrest, rrest.data(), rrest.size() * 4) &&
-              up((void**)&ft.d_nonq, nonq.data(), nonq.size() * 4) &&
-              up((void**)&ft.d_all, all_tiles.data(), all_tiles.size() * 4) &&
-              up((void**)&ft.d_pairs, pairs.data(), pairs.size() * sizeof(StripPair)) &&
-              up((void**)&ft.d_qstrips, qstrips.data(), qstrips.size() * sizeof(QStrip)) &&
-              up((void**)&ft.d_qprefix, qprefix.data(), qprefix.size() * 4) &&
-              up((void**)&ft.d_qtab, qtab.data(), qtab.size() * 4) &&
-              up((void**)&ft.d_q8strips, q8strips.data(), q8strips.size() * sizeof(QStrip)) &&
-              up((void**)&ft.d_q8prefix, q8prefix.data(), q8prefix.size() * 4) &&
-              up((void**)&ft.d_q8tab, q8tab.data(), q8tab.size() * 4) &&
-              up((void**)&ft.d_q8rest, q8rest.data(), q8rest.size() * 4) &&
-              up((void**)&ft.d_qrrest, qrrest.data(), qrrest.size() * 4) &&
-              up((void**)&ft.d_qtlist, qt_list.data(), qt_list.size() * 4) &&
-              up((void**)&ft.d_qtabrow, qt_rows.data(), qt_rows.size() * 4) &&
-              up((void**)&ft.d_qtabvals, qt_vals.data(), qt_vals.size() * 4) &&
-              up((void**)&ft.d_ipairs, ipairs.data(), ipairs.size() * sizeof(StripPair));
-  if (good && !patch_rows.empty()) good = struct_patch_rows(plan, fp->d_gvals8, fp->d_gdiag, patch_rows.data(), patch_vals.data(), (int64_t)patch_rows.size()) == DSPH_OK;
-  if (!good) {
-    FusedTiles keep = ft;
-    free_tiles(ft);
-    ft.D = keep.D;
-    return ft;
-  }
-  ft.ok = true;
-  return ft;
 }
 
 // LDS planes are sized at compile time: 576 rows (a 16x16 tile with a 4-ring halo), 768 or 1024
@@ -1385,8 +131,8 @@ static bool supported_impl(const dsph_plan* plan, int32_t Fin, int32_t Fout, int
   if (Fin % 4 != 0 || Fin < 4 || Fout < 1) return false;  // Fout > 64: one launch per 64-column block
   const FusedTiles& ft = get_tiles(plan, K - 1, full);
   if (!ft.ok) return false;
-  if (ft.n_r + ft.n_t > 0 && !struct_shape_ok(Fin, std::min(Fout, 64), K)) return false;
-  if (ft.n_part == 0) return true;  // every tile is class R
+  if (ft.r.n + ft.t.tiles.n > 0 && !struct_shape_ok(Fin, std::min(Fout, 64), K)) return false;
+  if (ft.part.n == 0) return true;  // every tile is class R
   const int pr = plane_rows_for(ft.rmax, ft.emax, ft.width);
   if (pr == 0) return false;
   // (the weight fragments need not fit beside the planes: the forward then reads them from global memory, cheb_fused_kernel's
@@ -1405,7 +151,7 @@ int fused_num_cu(const dsph_plan* plan) { return plan->fused ? plan->fused->num_
 bool fused_tstep_tables(const dsph_plan* plan, TStepTables* out) {
   if (!plan->fused || !plan->fused->wide || plan->n_cols != plan->n_rows || !plan->levels.empty()) return false;
   const FusedTiles& ft = get_tiles(plan, 1, true);
-  if (!ft.ok || ft.rmax > 768 || ft.n_part != ft.ntiles) return false;  // (TS_RMAX of cheb_tstep.hip)
+  if (!ft.ok || ft.rmax > 768 || ft.part.n != ft.ntiles) return false;  // (TS_RMAX of cheb_tstep.hip)
   out->tile_off = ft.d_tile_off;
   out->ring_end = ft.d_ring_end;
   out->ell_off = ft.d_ell_off;
@@ -1427,53 +173,35 @@ bool fused_weights_resident(const dsph_plan* plan, int32_t Fin, int32_t Fout, in
   if (!fused_supported(plan, Fin, Fout, K)) return false;
   const int32_t Fp = pad4(Fin);
   const FusedTiles& ft = get_tiles(plan, K - 1, want_full(plan, Fp, false));
-  if (ft.n_part == 0) return true;
+  if (ft.part.n == 0) return true;
   const int pr = plane_rows_for(ft.rmax, ft.emax, ft.width);
   return (size_t)2 * pr * FUSED_CH * 4 + wfrag_bytes(Fp, std::min(Fout, 64), K) + FUSED_BIAS_BYTES <= (size_t)LDS_BYTES;
 }
 
-static bool fused_symmetric(const dsph_plan* plan);
 int fused_prepare(const dsph_plan* plan, int32_t K, int32_t Fin, int32_t flags) {
-  if (plan->fused && plan->fused->wide) {  // the tiled step's tables, so that the first forward does not build them
+  FusedPlan* fp = plan->fused;
+  if (fp && fp->wide) {  // the tiled step's tables, so that the first forward does not build them
     TStepTables tb;
     if (K >= 2) (void)fused_tstep_tables(plan, &tb);
-    if (flags & DSPH_PREPARE_RELEASE_HOST) {
-      FusedPlan* fpw = plan->fused;
-      std::lock_guard<std::mutex> lock(fpw->mu);
-      std::vector<int32_t>().swap(fpw->h_cols);
-      std::vector<float>().swap(fpw->h_vals);
-      fpw->host_released = true;
+  } else {
+    if (!fp || K < 2 || K - 1 > FUSED_DMAX) return DSPH_OK;  // nothing to build: the unfused path serves it
+    const FusedTiles& ftp = get_tiles(plan, K - 1, want_full(plan, pad4(std::max(Fin, 1)), false));
+    if (ftp.ok && plan->opt.fork && ftp.r.n + ftp.t.tiles.n > 0 && ftp.part.n > 0) {  // a forward of this K may fork: the side stream exists before it
+      std::lock_guard<std::mutex> lock(fp->fork_mu);
+      (void)side_stream_ready(plan, fp, nullptr, true);
     }
-    return DSPH_OK;
-  }
-  if (!plan->fused || K < 2 || K - 1 > FUSED_DMAX) return DSPH_OK;  // nothing to build: the unfused path serves it
-  const FusedTiles& ftp = get_tiles(plan, K - 1, want_full(plan, pad4(std::max(Fin, 1)), false));
-  if (ftp.ok && plan->opt.fork && ftp.n_r + ftp.n_t > 0 && ftp.n_part > 0) {  // a forward of this K may fork: the side stream exists before it
-    std::lock_guard<std::mutex> lock(plan->fused->fork_mu);
-    (void)side_stream_ready(plan, plan->fused, nullptr, true);
-  }
-  if (flags & DSPH_PREPARE_BACKWARD) {
-    (void)get_tiles(plan, K - 1, true);
-    (void)fused_symmetric(plan);  // (what the quad-strip weight gradient asks; the host arrays may be released below)
+    if (flags & DSPH_PREPARE_BACKWARD) {
+      (void)get_tiles(plan, K - 1, true);
+      (void)fused_symmetric(plan);  // (what the quad-strip weight gradient asks; the host arrays may be released below)
+    }
   }
   if (flags & DSPH_PREPARE_RELEASE_HOST) {
-    FusedPlan* fp = plan->fused;
     std::lock_guard<std::mutex> lock(fp->mu);
     std::vector<int32_t>().swap(fp->h_cols);
     std::vector<float>().swap(fp->h_vals);
     fp->host_released = true;
   }
   return DSPH_OK;
-}
-
-// tiles of the K-term forward by kernel: class R (structured-tile kernel) and class G (BFS-tile kernel)
-bool fused_tile_counts(const dsph_plan* plan, int32_t K, int64_t* n_struct, int64_t* n_bfs) {
-  if (!plan->fused || K < 2 || K - 1 > FUSED_DMAX) return false;
-  const FusedTiles& ft = get_tiles(plan, K - 1, false);
-  if (!ft.ok) return false;
-  *n_struct = ft.n_r + ft.n_t;
-  *n_bfs = ft.n_part;
-  return true;
 }
 
 // One rule for "does the strip kernel take this forward" (launch_fused_common and dsph_plan_strip_tiles): the shape is the
@@ -1486,7 +214,7 @@ bool fused_tile_counts(const dsph_plan* plan, int32_t K, int64_t* n_struct, int6
 // that needs batch- or shard-invariant bits fixes the choice per plan: dsph_plan_set_option(DSPH_OPT_STRIPS, 1 always | 2 never).
 //   Fout: the columns of THIS launch (one 64-column block of the layer); ld: the layer's row stride of y.
 static bool use_qstrips(const dsph_plan* plan, const FusedTiles& ft, int32_t Fin, int32_t Fout, int32_t K) {
-  return plan->opt.strip_form == 0 && ft.n_qstrips > 0 && qstrip_shape_ok(Fin, Fout, K);
+  return plan->opt.strip_form == 0 && ft.q5.n > 0 && qstrip_shape_ok(Fin, Fout, K);
 }
 static bool strips_apply(const dsph_plan* plan, const FusedTiles& ft, int32_t Fin, int32_t Fout, int32_t K, int32_t precision, int64_t N,
                          int32_t ld) {
@@ -1499,8 +227,8 @@ static bool strips_apply(const dsph_plan* plan, const FusedTiles& ft, int32_t Fi
   if (quad) {
     // (a quad-strip step takes 2.8 us, a tile-map 18.7; the tape of rows is cut evenly, so the span is a formula)
     if (N < 1) return false;
-    const int64_t span = qstrip_split(fp->num_cu, ft.qtape_rows, N, ft.qtape_rows / std::max(1, ft.n_qstrips), nullptr, nullptr, nullptr);
-    return span * 28 * 103 < ft.n_qstrip_tiles * N * 187 / fp->num_cu * 100;
+    const int64_t span = qstrip_split(fp->num_cu, ft.q5.tape_rows, N, ft.q5.tape_rows / std::max(1, ft.q5.n), nullptr, nullptr, nullptr);
+    return span * 28 * 103 < ft.q5.n_tiles * N * 187 / fp->num_cu * 100;
   }
   const std::vector<int32_t>& steps = ft.strip_steps;
   if (N < 1 || (int64_t)steps.size() * N > (1ll << 24)) return false;
@@ -1522,10 +250,10 @@ static bool q8_applies(const dsph_plan* plan, const FusedTiles& ft, int32_t Fin,
   // (no limit on the size of a map: this kernel forms its addresses in 64 bits -- configs[3] is 6.4 GB of x)
   // (ld == Fout: the layer IS 32 columns wide -- the last 32 columns of a wider layer would find no room for this kernel's weight
   // image in their block of the workspace, which is sized for 64-column blocks)
-  if (ft.n_q8strips == 0 || !qstrip8_shape_ok(Fin, Fout, K) || (precision != DSPH_PREC_BF16X3 && precision != DSPH_PREC_F16X3) || ld != Fout || N < 1) return false;
+  if (ft.q8.n == 0 || !qstrip8_shape_ok(Fin, Fout, K) || (precision != DSPH_PREC_BF16X3 && precision != DSPH_PREC_F16X3) || ld != Fout || N < 1) return false;
   if (plan->opt.strips == 1) return true;
-  const int64_t span = qstrip8_split(plan->fused->num_cu, ft.q8tape_rows, N, ft.q8tape_rows / std::max(1, ft.n_q8strips), nullptr, nullptr, nullptr);
-  return span * 26 * 103 < ft.n_q8_tiles * N * 275 / plan->fused->num_cu * 100;
+  const int64_t span = qstrip8_split(plan->fused->num_cu, ft.q8.tape_rows, N, ft.q8.tape_rows / std::max(1, ft.q8.n), nullptr, nullptr, nullptr);
+  return span * 26 * 103 < ft.q8.n_tiles * N * 275 / plan->fused->num_cu * 100;
 }
 
 // The input-side strip kernel takes the rectangles of every layer with at most 16 input channels (any arithmetic, K = 2 .. 5,
@@ -1568,70 +296,12 @@ int64_t fused_strip_tiles(const dsph_plan* plan, int64_t N, int32_t Fin, int32_t
   }
   if (qstrip8_shape_ok(Fin, Fout, K)) {
     const FusedTiles& ft8 = get_tiles(plan, K - 1, want_full(plan, Fin, false));
-    return ft8.ok && q8_applies(plan, ft8, Fin, Fout, K, precision, N, Fout) ? ft8.n_q8_tiles : 0;
+    return ft8.ok && q8_applies(plan, ft8, Fin, Fout, K, precision, N, Fout) ? ft8.q8.n_tiles : 0;
   }
   if (Fin != pad4(Fin) || Fout < 64) return 0;
   const FusedTiles& ft = get_tiles(plan, K - 1, want_full(plan, Fin, false));
   if (!ft.ok) return 0;
-  return strips_apply(plan, ft, Fin, 64, K, precision, N, Fout) ? (use_qstrips(plan, ft, Fin, 64, K) ? ft.n_qstrip_tiles : ft.n_strip_tiles) : 0;
-}
-
-// the strip pairs of the K-term tables, 12 int32 each: x0[2], w[2], xs[2], y0, y1, xlo, xhi, ylo, yhi (StripPair); returns how
-// many there are (also when cap is smaller), -1 when the plan has no fused tables for this K
-int64_t fused_strip_pairs(const dsph_plan* plan, int32_t K, int32_t* out, int64_t cap) {
-  if (!plan->fused || K < 2 || K - 1 > FUSED_DMAX) return -1;
-  const FusedTiles& ft = get_tiles(plan, K - 1, false);
-  if (!ft.ok) return -1;
-  static_assert(sizeof(StripPair) == 12 * sizeof(int32_t), "StripPair is twelve int32");
-  if (plan->opt.strip_form == 0 && ((K == 5 && !ft.h_qstrips.empty()) || (K == Q8_K && !ft.h_q8strips.empty()))) {  // the quad strips, in the same record: one strip, the second empty
-    const std::vector<QStrip>& hq = K == Q8_K ? ft.h_q8strips : ft.h_qstrips;
-    const int64_t n = (int64_t)hq.size();
-    for (int64_t i = 0; i < n && i < cap; ++i) {
-      const QStrip& q = hq[(size_t)i];
-      const int32_t rec[12] = {q.x0, q.x0, q.w, 0, q.xs, q.xs, q.y0, q.y1, q.xlo, q.xhi, q.ylo, q.yhi};
-      memcpy(out + 12 * i, rec, sizeof(rec));
-    }
-    return n;
-  }
-  const int64_t n = (int64_t)ft.h_pairs.size();
-  for (int64_t i = 0; i < n && i < cap; ++i) memcpy(out + 12 * i, &ft.h_pairs[(size_t)i], sizeof(StripPair));
-  return n;
-}
-
-// rows of n pixels of strip record `strip` (dsph_plan_strip_rows): through the rectangle's table for the quad strips, the
-// virtual Z-order plane for the strip pairs; -1 when there is no such record
-int64_t fused_strip_rows(const dsph_plan* plan, int32_t K, int64_t strip, int64_t n, const int32_t* xy, int64_t* rows) {
-  if (!plan->fused || K < 2 || K - 1 > FUSED_DMAX) return -1;
-  const FusedTiles& ft = get_tiles(plan, K - 1, false);
-  if (!ft.ok || strip < 0) return -1;
-  if (plan->opt.strip_form == 0 && ((K == 5 && !ft.h_qstrips.empty()) || (K == Q8_K && !ft.h_q8strips.empty()))) {
-    const std::vector<QStrip>& hq = K == Q8_K ? ft.h_q8strips : ft.h_qstrips;
-    const std::vector<int32_t>& htab = K == Q8_K ? ft.h_q8tab : ft.h_qtab;
-    if (strip >= (int64_t)hq.size()) return -1;
-    const QStrip& q = hq[(size_t)strip];
-    // (K = 5: the kernel steps a row's bits without clamping it to the halo -- a run of steps reads rows ylo - 1 .. yhi + 6 of
-    // the table's ring tiles, beyond the halo for nothing: they are answered as the kernel reads them)
-    const int ya = K == 5 ? q.ylo - 1 : q.ylo, yb = K == 5 ? q.yhi + 6 : q.yhi;
-    for (int64_t i = 0; i < n; ++i) {
-      const int x = std::min(std::max(xy[2 * i], q.xlo), q.xhi), y = std::min(std::max(xy[2 * i + 1], ya), yb);
-      rows[i] = (int64_t)htab[(size_t)(q.tab + (y >> 4) * q.tws + (x >> 4))] + (int64_t)st_morton((unsigned)x & 15u, (unsigned)y & 15u);
-    }
-    return n;
-  }
-  if (strip >= (int64_t)ft.h_pairs.size()) return -1;
-  for (int64_t i = 0; i < n; ++i) rows[i] = (int64_t)st_morton((unsigned)xy[2 * i], (unsigned)xy[2 * i + 1]);
-  return n;
-}
-
-// how a quad-strip forward of N maps on the K = 5 tables cuts its work (qstrip_split)
-bool fused_strip_split(const dsph_plan* plan, int64_t N, int32_t* grid, int32_t* pieces, int32_t* wg_per_piece, int64_t* tape_rows) {
-  if (!plan->fused || N < 1) return false;
-  const FusedTiles& ft = get_tiles(plan, QS_D, false);
-  if (!ft.ok || ft.n_qstrips == 0) return false;
-  int g = 0, p = 0, w = 0;
-  (void)qstrip_split(plan->fused->num_cu, ft.qtape_rows, N, ft.qtape_rows / std::max(1, ft.n_qstrips), &g, &p, &w);
-  *grid = g; *pieces = p; *wg_per_piece = w; *tape_rows = ft.qtape_rows;
-  return true;
+  return strips_apply(plan, ft, Fin, 64, K, precision, N, Fout) ? (use_qstrips(plan, ft, Fin, 64, K) ? ft.q5.n_tiles : ft.n_strip_tiles) : 0;
 }
 
 // two fragment layouts: the BFS-tile kernel's and, behind it, the structured-tile kernel's
@@ -1734,7 +404,7 @@ int launch_cheb_fused(const dsph_plan* plan, const float* x, const float* w, con
   bool defer_act = false;
   if (act != DSPH_ACT_NONE && act != DSPH_ACT_RELU && K - 1 <= FUSED_DMAX && K >= 2) {
     const FusedTiles& ft = get_tiles(plan, K - 1, want_full(plan, pad4(Fin), false));
-    defer_act = ft.ok && ft.n_r + ft.n_t > 0;
+    defer_act = ft.ok && ft.r.n + ft.t.tiles.n > 0;
   }
   // (two-part launches: each part writes the pre-activation of its tiles and then finishes exactly those tiles' rows)
   // Fin not a multiple of four: a zero-padded copy of x behind the weight fragments in the workspace (with a two-part
@@ -1749,11 +419,8 @@ int launch_cheb_fused(const dsph_plan* plan, const float* x, const float* w, con
       return DSPH_E_WORKSPACE;
     }
     float* xp = reinterpret_cast<float*>(static_cast<unsigned char*>(workspace) + frag);
-    const int64_t rows = N * plan->n_cols;
-    const int64_t work = rows * (Fp / 4);
-    hipLaunchKernelGGL(fused_pad_kernel, dim3((unsigned)std::min<int64_t>((work + 255) / 256, 65536)), dim3(256), 0, stream, x,
-                       reinterpret_cast<float4*>(xp), rows, (int)Fin, (int)(Fp / 4));
-    DSPH_HIP(hipGetLastError());
+    const int rc = launch_fused_pad(x, xp, N * plan->n_cols, Fin, Fp, stream);
+    if (rc != DSPH_OK) return rc;
     x = xp;
     Fin = Fp;
   }
@@ -1763,17 +430,17 @@ int launch_cheb_fused(const dsph_plan* plan, const float* x, const float* w, con
   bool fork = false;
   if (fp && plan->opt.fork && K >= 2 && K - 1 <= FUSED_DMAX) {
     const FusedTiles& ft = get_tiles(plan, K - 1, want_full(plan, Fin, false));
-    const int ng = !ft.ok ? 0 : (part == 0 ? ft.n_part : (part == 1 ? ft.n_interior : ft.n_part - ft.n_interior));
+    const int ng = !ft.ok ? 0 : ft.part.count(part);
     // (worth its two event operations only when the structured launches run for a while: two tile-maps per CU and more --
     // BASELINE configs[0], 168 tile-maps, is 13 us faster without it, configs[1] 29 us faster with it.  Under a stream
     // capture the fork and the join are edges of the graph and cost nothing at replay: every forward with both kinds of tiles
     // forks there, provided the side stream exists already -- dsph_plan_prepare made it)
-    bool big = N * (int64_t)(ft.n_r + ft.n_t) >= 2 * (int64_t)fp->num_cu;
+    bool big = N * (int64_t)(ft.r.n + ft.t.tiles.n) >= 2 * (int64_t)fp->num_cu;
     if (!big && fp->side && stream != nullptr) {
       hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
       big = hipStreamIsCapturing(stream, &cs) == hipSuccess && cs == hipStreamCaptureStatusActive;
     }
-    fork = ft.ok && ft.n_r + ft.n_t > 0 && ng > 0 && big;
+    fork = ft.ok && ft.r.n + ft.t.tiles.n > 0 && ng > 0 && big;
   }
   const size_t blk_frag = all_frag_bytes(Fin, std::min(Fout, 64), K);
   if (!workspace || workspace_bytes < frag_area_bytes(Fin, Fout, K)) {
@@ -1827,9 +494,7 @@ int launch_cheb_fused(const dsph_plan* plan, const float* x, const float* w, con
     if (part == 0) return launch_struct_act(y, N * orows, Fout, Fout, act, stream);
     // a part finishes the rows of its own tiles only: INTERIOR and BOUNDARY can be issued in any order, repeated, or alone
     const FusedTiles& ft = get_tiles(plan, K - 1, want_full(plan, Fin, false));
-    const int32_t* tl = part == 1 ? ft.d_all : ft.d_all + ft.n_all_interior;
-    const int nt = part == 1 ? ft.n_all_interior : ft.n_all - ft.n_all_interior;
-    return launch_struct_act_tiles(y, tl, nt, N, orows, Fout, Fout, act, stream);
+    return launch_struct_act_tiles(y, ft.all.ptr(part), ft.all.count(part), N, orows, Fout, Fout, act, stream);
   }
   return DSPH_OK;
 }
@@ -1934,35 +599,6 @@ int launch_cheb_fused_wgrad(const dsph_plan* plan, const float* x, const float* 
 }
 
 // ---- quad-strip weight gradient (cheb_qwgrad.hip) -----------------------------------------------------------------------
-// L~ equal to its transpose, entry for entry (to fp32 rounding): the product rule the quad-strip weight gradient stands on
-// moves T_j from x to dy.
-static bool fused_symmetric(const dsph_plan* plan) {
-  FusedPlan* fp = plan->fused;
-  std::lock_guard<std::mutex> lock(fp->mu);
-  if (fp->symmetric >= 0) return fp->symmetric == 1;
-  if (fp->host_released || plan->n_rows != plan->n_cols) return false;  // (not cached: unknown, or not a square operator)
-  const int W = plan->width;
-  const int64_t n = plan->n_rows;
-  const int32_t* cols = fp->h_cols.data();
-  const float* vals = fp->h_vals.data();
-  bool sym = true;
-  for (int64_t r = 0; r < n && sym; ++r)
-    for (int j = 0; j < W; ++j) {
-      const int64_t c = cols[r * W + j];
-      const float v = vals[r * W + j];
-      if (v == 0.f || c == r) continue;  // (padding entries carry zeros)
-      if (c < 0 || c >= n) { sym = false; break; }
-      // the entry (c, r) must hold the same value (every off-diagonal entry is checked from its own side)
-      float back = 0.f;
-      for (int i = 0; i < W; ++i)
-        if (cols[c * W + i] == r) back += vals[c * W + i];
-      // (to the last bits of fp32: a normalised Laplacian D^-1/2 A D^-1/2 evaluated in float64 and rounded may differ by one
-      // unit in the last place between (r, c) and (c, r); that moves dW by 1e-7 of itself, far below the arithmetic's 4e-6)
-      if (fabsf(back - v) > 2.4e-7f * fmaxf(fabsf(back), fabsf(v))) { sym = false; break; }
-    }
-  fp->symmetric = sym ? 1 : 0;
-  return sym;
-}
 
 // The quad-strip weight gradient takes the strips' pixels of a K = 5, 64 -> 64 j layer in the three-term bf16 arithmetic when
 // the forward of that shape would run on the quad strips (same tables, same cost rule) and L~ is symmetric; the BFS-tile
@@ -1983,25 +619,43 @@ int launch_cheb_fused_qwgrad(const dsph_plan* plan, const float* x, const float*
                              int32_t K, float alpha_rest, float beta_rest, void* workspace, size_t bfs_slab_bytes, hipStream_t stream) {
   const FusedTiles& ft = get_tiles(plan, K - 1, false);
   for (int32_t cb = 0; cb < Fout; cb += 64) {
-    if (ft.n_nonq > 0) {
+    if (ft.nonq.n > 0) {
       const int rc = launch_fused_common(plan, x, nullptr, nullptr, static_cast<float*>(workspace), nullptr, N, Fin, 64, K, DSPH_ACT_NONE,
                                          DSPH_PREC_BF16X3, alpha_rest, beta_rest, nullptr, 0, stream, dy + cb, dw + cb, Fout, 0, Fin, 0, false,
-                                         nullptr, ft.d_nonq, ft.n_nonq);
+                                         nullptr, ft.nonq.d, ft.nonq.n);
       if (rc != DSPH_OK) return rc;
     }
     QWgradLaunch q;
     q.x = x; q.dy = dy + cb; q.dw = dw + cb;
     q.slabs = reinterpret_cast<float*>(static_cast<char*>(workspace) + bfs_slab_bytes);
-    q.strips = ft.d_qstrips; q.prefix = ft.d_qprefix; q.tape_rows = ft.qtape_rows; q.tab = ft.d_qtab;
+    q.strips = ft.q5.d_strips; q.prefix = ft.q5.d_prefix; q.tape_rows = ft.q5.tape_rows; q.tab = ft.q5.d_tab;
     q.gvals8 = plan->fused->d_gvals8; q.gdiag = plan->fused->d_gdiag;
     q.x_rows = plan->n_cols; q.dy_rows = plan->n_rows; q.N = N;
-    q.nstrips = ft.n_qstrips; q.lddy = Fout; q.lddw = Fout; q.num_cu = plan->fused->num_cu;
+    q.nstrips = ft.q5.n; q.lddy = Fout; q.lddw = Fout; q.num_cu = plan->fused->num_cu;
     q.cheb = beta_rest != 0.f;
-    q.accumulate = ft.n_nonq > 0;
+    q.accumulate = ft.nonq.n > 0;
     const int rc = launch_cheb_qwgrad(q, stream);
     if (rc != DSPH_OK) return rc;
   }
   return DSPH_OK;
+}
+
+// the instantiation of the BFS-tile kernel for plane rows pr and ELL width wt (cheb_fused_inst.hip)
+static int launch_fused_variant(int pr, int wt, const FusedArgs& a, int nb, int prec, int grid, size_t lds, hipStream_t stream) {
+#define DSPH_FUSED_CASE(PR, WT) \
+  if (pr == PR && wt == WT) return launch_fused_##PR##_##WT(a, nb, prec, grid, lds, stream);
+  DSPH_FUSED_CASE(576, 9)
+  DSPH_FUSED_CASE(768, 9)
+  DSPH_FUSED_CASE(928, 9)
+  DSPH_FUSED_CASE(1024, 9)
+  DSPH_FUSED_CASE(1168, 9)
+  DSPH_FUSED_CASE(576, 12)
+  DSPH_FUSED_CASE(768, 12)
+  DSPH_FUSED_CASE(928, 12)
+  DSPH_FUSED_CASE(1024, 12)
+#undef DSPH_FUSED_CASE
+  set_error("cheb_fused: no kernel for plane rows %d, width %d", pr, wt);
+  return DSPH_E_UNSUPPORTED;
 }
 
 static int launch_fused_common(const dsph_plan* plan, const float* x, const float* w, const float* bias,
@@ -2036,7 +690,7 @@ static int launch_fused_common(const dsph_plan* plan, const float* x, const floa
   }
   const int C = (Fin + FUSED_CH - 1) / FUSED_CH, NB = (Fout + 31) / 32;
   // ---- class-R and class-T tiles: the structured-tile kernel (forward only), without and with per-tile tables ----------
-  if (!planes_mode && ft.n_r + ft.n_t > 0 && only != 2) {
+  if (!planes_mode && ft.r.n + ft.t.tiles.n > 0 && only != 2) {
     StructLaunch sl;
     sl.x = x; sl.w = w; sl.bias = bias; sl.y = y;
     sl.wfrag = static_cast<unsigned char*>(workspace) + wb;
@@ -2062,14 +716,14 @@ static int launch_fused_common(const dsph_plan* plan, const float* x, const floa
       qs.x = x; qs.w = w; qs.bias = bias; qs.y = y;
       qs.wimg = static_cast<unsigned char*>(workspace) + wb + struct_wfrag_bytes(Fin, Fout, K) + strip_wimg_bytes(Fin, Fout, K) +
                 2 * istrip_wimg_bytes(K, DSPH_PREC_BF16X6);
-      qs.strips = ft.d_qstrips;
-      qs.tab = ft.d_qtab;
-      qs.prefix = ft.d_qprefix;
-      qs.tape_rows = ft.qtape_rows;
+      qs.strips = ft.q5.d_strips;
+      qs.tab = ft.q5.d_tab;
+      qs.prefix = ft.q5.d_prefix;
+      qs.tape_rows = ft.q5.tape_rows;
       qs.gvals8 = plan->fused->d_gvals8;
       qs.gdiag = plan->fused->d_gdiag;
       qs.x_rows = sl.x_rows; qs.y_rows = sl.y_rows; qs.N = N;
-      qs.nstrips = ft.n_qstrips; qs.Fin = Fin; qs.Fout = Fout; qs.act = act; qs.ld = ld;
+      qs.nstrips = ft.q5.n; qs.Fin = Fin; qs.Fout = Fout; qs.act = act; qs.ld = ld;
       qs.num_cu = plan->fused->num_cu;
       qs.cheb = sl.cheb;
       qs.f16 = f16;
@@ -2118,34 +772,29 @@ static int launch_fused_common(const dsph_plan* plan, const float* x, const floa
     }
     const bool stripped = strips || istrips;
     const bool qrest = strips && use_qstrips(plan, ft, Fin, Fout, K);  // the quad strips took class-T tiles too: their own rest lists
-    const int32_t* rl = qrest ? ft.d_qrrest : (stripped ? ft.d_rrest : ft.d_rlist);
-    const int rl_n = qrest ? ft.n_qrrest : (stripped ? ft.n_rrest : ft.n_r), rl_ni = qrest ? ft.n_qrrest_interior : (stripped ? ft.n_rrest_interior : ft.n_r_interior);
-    const int nr = part == 0 ? rl_n : (part == 1 ? rl_ni : rl_n - rl_ni);
-    if (nr > 0 && !dbg_only('b')) {
-      sl.tiles = part == 2 ? rl + rl_ni : rl;
+    const TileList& rl = qrest ? ft.qrrest : (stripped ? ft.rrest : ft.r);
+    if (rl.count(part) > 0 && !dbg_only('b')) {
+      sl.tiles = rl.ptr(part);
       sl.tabrow = nullptr;
       sl.tabvals = nullptr;
-      sl.ntiles = nr;
+      sl.ntiles = rl.count(part);
       sl.prep_weights = struct_prep && fused_images_claim(plan, workspace, IMG_STRUCT);
       struct_prep = false;
       const int rc = launch_cheb_struct(sl, stream);
       if (rc != DSPH_OK) return rc;
     }
-    const int n_t = qrest ? ft.n_qt : ft.n_t, n_t_interior = qrest ? ft.n_qt_interior : ft.n_t_interior;
-    const int nt = part == 0 ? n_t : (part == 1 ? n_t_interior : n_t - n_t_interior);
-    if (nt > 0 && !dbg_only('b')) {
-      const size_t first = part == 2 ? (size_t)n_t_interior : 0;
-      sl.tiles = (qrest ? ft.d_qtlist : ft.d_tlist) + first;
-      sl.tabrow = (qrest ? ft.d_qtabrow : ft.d_tabrow) + first * ST_CELLS;
-      sl.tabvals = (qrest ? ft.d_qtabvals : ft.d_tabvals) + first * ST_CELLS * ST_TABV;
-      sl.ntiles = nt;
+    const TileTables& tt = qrest ? ft.qt : ft.t;
+    if (tt.tiles.count(part) > 0 && !dbg_only('b')) {
+      sl.tiles = tt.tiles.ptr(part);
+      sl.tabrow = tt.rows(part);
+      sl.tabvals = tt.vals(part);
+      sl.ntiles = tt.tiles.count(part);
       sl.prep_weights = struct_prep && fused_images_claim(plan, workspace, IMG_STRUCT);
       struct_prep = false;
       const int rc = launch_cheb_struct(sl, stream);
       if (rc != DSPH_OK) return rc;
     }
-    const int ng = part == 0 ? ft.n_part : (part == 1 ? ft.n_interior : ft.n_part - ft.n_interior);
-    if (ng == 0 || dbg_only('s')) return DSPH_OK;
+    if (ft.part.count(part) == 0 || dbg_only('s')) return DSPH_OK;
   }
   if (only == 1) return DSPH_OK;
   // the BFS-tile kernel has two contraction arithmetics; the six-term split of the structured kernel is fp32-equivalent
@@ -2168,16 +817,16 @@ static int launch_fused_common(const dsph_plan* plan, const float* x, const floa
     QStrip8Launch q;
     q.x = x; q.w = w; q.bias = bias; q.y = y;
     q.wimg = static_cast<unsigned char*>(workspace) + all_frag_bytes(Fin, Fout, K) - qstrip8_wimg_bytes();
-    q.strips = ft.d_q8strips; q.tab = ft.d_q8tab; q.prefix = ft.d_q8prefix; q.tape_rows = ft.q8tape_rows;
+    q.strips = ft.q8.d_strips; q.tab = ft.q8.d_tab; q.prefix = ft.q8.d_prefix; q.tape_rows = ft.q8.tape_rows;
     q.gvals8 = plan->fused->d_gvals8; q.gdiag = plan->fused->d_gdiag;
     q.x_rows = plan->n_cols; q.y_rows = plan->levels.empty() ? plan->n_rows : plan->levels[0]; q.N = N;
-    q.nstrips = ft.n_q8strips; q.act = act; q.ld = ld; q.ld_w = ld; q.num_cu = plan->fused->num_cu;
+    q.nstrips = ft.q8.n; q.act = act; q.ld = ld; q.ld_w = ld; q.num_cu = plan->fused->num_cu;
     q.f16 = f16;
     q.f16_xexp = plan->opt.f16_xexp;
     q.prep_weights = fused_images_claim(plan, workspace, IMG_Q8);
     const int rc = launch_cheb_qstrip8(q, stream);
     if (rc != DSPH_OK) return rc;
-    if ((part == 0 ? ft.n_q8rest : ft.n_q8rest_interior) == 0) return DSPH_OK;
+    if (ft.q8rest.count(part) == 0) return DSPH_OK;
   }
 
   FusedArgs args;
@@ -2212,12 +861,12 @@ static int launch_fused_common(const dsph_plan* plan, const float* x, const floa
   args.ld = ld;
   args.K = K;
   // part: 0 all tiles, 1 interior tiles (no row of another rank in their region), 2 boundary tiles
-  // the BFS-tile kernel handles the tiles of d_part (every tile of a full table, the class-G ones otherwise)
-  args.tile_list = part == 0 ? (ft.n_part == ft.ntiles ? nullptr : ft.d_part) : (part == 1 ? ft.d_part : ft.d_part + ft.n_interior);
-  args.ntiles = part == 0 ? ft.n_part : (part == 1 ? ft.n_interior : ft.n_part - ft.n_interior);
+  // the BFS-tile kernel handles the tiles of ft.part (every tile of a full table, the class-G ones otherwise)
+  args.tile_list = part == 0 && ft.part.n == ft.ntiles ? nullptr : ft.part.ptr(part);
+  args.ntiles = ft.part.count(part);
   if (q8) {  // (part 0: every tile the strips leave; part 1: the interior ones of them -- the boundary tiles are never the strips')
-    args.tile_list = ft.d_q8rest;
-    args.ntiles = part == 0 ? ft.n_q8rest : ft.n_q8rest_interior;
+    args.tile_list = ft.q8rest.ptr(part);
+    args.ntiles = ft.q8rest.count(part);
   }
   if (wgrad_mode && wg_ntiles >= 0) {  // (the strips' pixels go to cheb_qwgrad.hip: launch_cheb_fused_qwgrad)
     args.tile_list = wg_tiles;
@@ -2241,28 +890,12 @@ static int launch_fused_common(const dsph_plan* plan, const float* x, const floa
   if (wgrad_mode) {
     // as many slices per launch as fit the wave's WG_TILES accumulator tiles; every launch runs the
     // recurrence for its own slices only, so the split costs nothing but a second read of dy
-    auto launch_one = [&](const FusedArgs& la) -> int {
-#define DSPH_FUSED_CASE(PR, WT) \
-  if (pr == PR && ft.width == WT) return launch_fused_##PR##_##WT(la, NB, precision, grid, lds, stream);
-      DSPH_FUSED_CASE(576, 9)
-      DSPH_FUSED_CASE(768, 9)
-      DSPH_FUSED_CASE(928, 9)
-      DSPH_FUSED_CASE(1024, 9)
-      DSPH_FUSED_CASE(1168, 9)
-      DSPH_FUSED_CASE(576, 12)
-      DSPH_FUSED_CASE(768, 12)
-      DSPH_FUSED_CASE(928, 12)
-      DSPH_FUSED_CASE(1024, 12)
-#undef DSPH_FUSED_CASE
-      set_error("cheb_fused: no kernel for plane rows %d, width %d", pr, ft.width);
-      return DSPH_E_UNSUPPORTED;
-    };
     const int per = wgrad_slices_per_launch(plan, K);
     for (int c0 = 0; c0 < C; c0 += per) {
       FusedArgs la = args;
       la.c_begin = c0;
       la.c_count = std::min(per, C - c0);
-      const int rc = launch_one(la);
+      const int rc = launch_fused_variant(pr, ft.width, la, NB, precision, grid, lds, stream);
       if (rc != DSPH_OK) return rc;
     }
     // (Fin_w < Fin: x is a zero-padded copy, only the rows of the real channels exist in dw)
@@ -2293,24 +926,10 @@ static int launch_fused_common(const dsph_plan* plan, const float* x, const floa
       }
     return rc;
   };
-#define DSPH_FUSED_CASE(PR, WT) \
-  if (pr == PR && ft.width == WT) return dump_stamps(launch_fused_##PR##_##WT(args, NBb, precision, grid, lds, stream));
+  return dump_stamps(launch_fused_variant(pr, ft.width, args, NBb, precision, grid, lds, stream));
 #else
-#define DSPH_FUSED_CASE(PR, WT) \
-  if (pr == PR && ft.width == WT) return launch_fused_##PR##_##WT(args, NBb, precision, grid, lds, stream);
+  return launch_fused_variant(pr, ft.width, args, NBb, precision, grid, lds, stream);
 #endif
-  DSPH_FUSED_CASE(576, 9)
-  DSPH_FUSED_CASE(768, 9)
-  DSPH_FUSED_CASE(928, 9)
-  DSPH_FUSED_CASE(1024, 9)
-  DSPH_FUSED_CASE(1168, 9)
-  DSPH_FUSED_CASE(576, 12)
-  DSPH_FUSED_CASE(768, 12)
-  DSPH_FUSED_CASE(928, 12)
-  DSPH_FUSED_CASE(1024, 12)
-#undef DSPH_FUSED_CASE
-  set_error("cheb_fused: no kernel for plane rows %d, width %d", pr, ft.width);
-  return DSPH_E_UNSUPPORTED;
 }
 
 }  // namespace dsph

@@ -1,5 +1,5 @@
 // Device side of the fused Chebyshev forward (see cheb_fused.hip for the design notes).
-// Included by cheb_fused.hip (host: tile tables, dispatch) and by cheb_fused_inst.hip, which is
+// Included by cheb_fused.hip (host: dispatch), cheb_tiles.h (host: tile tables) and by cheb_fused_inst.hip, which is
 // compiled once per (plane rows, ELL width) pair so that the instantiations build in parallel.
 #pragma once
 

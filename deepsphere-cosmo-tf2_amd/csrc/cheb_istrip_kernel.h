@@ -23,7 +23,7 @@
 // Shapes: K = 2 .. 5, at most 16 input channels (a multiple of four; other counts arrive zero-padded), 32 output columns
 // per launch (wider layers: one launch per block; the layer's width a multiple of four: 16-byte stores), all three
 // contraction arithmetics, both bases.
-// Which pixels: the strip rectangles of cheb_fused.hip (class-R tiles), cut into single strips and short segments.
+// Which pixels: the strip rectangles of cheb_tiles.hip (class-R tiles), cut into single strips and short segments.
 #pragma once
 
 #include <type_traits>

@@ -333,7 +333,7 @@ __global__ __launch_bounds__(QS_THREADS, 2) void cheb_qstrip5_kernel(QStripArgs 
   const unsigned x_loff = (unsigned)xt * QS_FRAG + (unsigned)(lane & 1) * 8u +
                           (X_BY_H ? (unsigned)(xpix + 16 * (lane >> 5)) * 16u : (unsigned)(xpix + 16 * (2 * (lane >> 5) + ((lane >> 4) & 1))) * 16u);
   // Where a pixel of the strip's plane lives: row = tab[(y >> 4) tws + (x >> 4)] + morton(x & 15, y & 15) -- the rectangle's table
-  // of tile bases (cheb_fused.hip, build_qtstrips: a rectangle may cross base-pixel borders that continue the pixel grid by a
+  // of tile bases (cheb_tiles.hip, build_qtstrips: a rectangle may cross base-pixel borders that continue the pixel grid by a
   // translation; inside a base pixel the table is the Morton plane itself).  A strip's 64 columns lie in at most five tile
   // columns, the row y is wave-uniform: the five bases of a tile row come by SCALAR loads (they share no counter with the
   // vector memory: a vector load here would wait for the previous step's y stores to drain -- measured, 12 % of the forward),

@@ -701,7 +701,7 @@ __global__ __launch_bounds__(SP_THREADS, 2) void cheb_strip5_kernel(StripArgs a)
   const int G = gridDim.x, xcd = blockIdx.x & 7, slot0 = blockIdx.x >> 3;
   const int nslots = (G + 7 - xcd) / 8;
   // work items are (strip pair, map): a contiguous range of them per XCD (neighbouring pairs and the maps of a pair share an
-  // L2), dealt to the XCD's workgroups in turn -- with the pairs sorted by height (cheb_fused.hip) every workgroup gets its
+  // L2), dealt to the XCD's workgroups in turn -- with the pairs sorted by height (cheb_tiles.hip) every workgroup gets its
   // share of tall and short ones
   const int64_t n_items = (int64_t)a.npairs * a.N;
   const int p_begin = (int)(n_items * xcd / 8), p_end = (int)(n_items * (xcd + 1) / 8);

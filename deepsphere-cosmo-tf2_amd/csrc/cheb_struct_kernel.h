@@ -23,7 +23,7 @@
 //     stored, under the FIRST step of the next item, so nothing but the recurrence is on the critical path;
 //   * class-T tiles (TAB = true): the same kernel for tiles whose region is a stencil square but whose halo rows are not a
 //     Morton continuation of the tile's (the next base pixel of the sphere, the halo rows of a sharded plan): the row of
-//     every plane cell and the nine values of L~ of every cell come from per-tile tables (embed_tile, cheb_fused.hip);
+//     every plane cell and the nine values of L~ of every cell come from per-tile tables (embed_tile, cheb_tiles.hip);
 //   * three contraction arithmetics (st_contract): exact-fp32 MFMA, the three-term split-bf16 form, and the six-term
 //     fp32-equivalent split whose 3 KiB weight blocks are replaced in place in LDS (DSPH_PREC_BF16X6);
 //   * at K = 5 no barrier in front of the item: every LDS-DMA piece is issued at least an interval before the barrier that

@@ -5,14 +5,14 @@
 // cheb_step.hip pulls every neighbour row through the L2 again: 23 x |x| of L2 -> CU traffic per step (0.95 ms per step at nside
 // 256, 16 channels, batch 8, where the three planes it touches are 1.2 GB).  Here a workgroup owns a tile of 256 consecutive rows
 // (a 16 x 16 pixel square in NEST order), stages the rows within ONE hop of it -- the breadth-first region tables the fused path
-// builds (cheb_fused.hip, depth 1) -- into LDS, 16 channels at a time, and gathers from there:
+// builds (cheb_tiles.hip, depth 1) -- into LDS, 16 channels at a time, and gathers from there:
 //     out[n, m, :] = alpha * sum_j vals[m, j] * in[n, cols[m, j], :] - beta * prev[n, m, :]          (reference utils.py:49-78,
 //                                                                                                  gnn_layers.py:138,141)
 // with every row of `in` read 1.7 x instead of 23 x (a 21 x 21 region per 16 x 16 tile at 20 neighbours).  A lane owns one (row,
 // 4-channel chunk) of the tile for the whole tile: the row's tile-local columns, as swizzled LDS byte addresses, and its values
 // stay in registers across all maps and channel slices (WT of each: the template parameter).  The next (map, slice)'s region is
 // fetched into registers while the current one is summed; two planes alternate.  The slots of a row are dealt by the residue of
-// the neighbour's local index (cheb_fused.hip, get_tiles: slot j of local row i holds a neighbour with index & 3 == (i + j) & 3
+// the neighbour's local index (cheb_tiles.hip, ell_row_wide: slot j of local row i holds a neighbour with index & 3 == (i + j) & 3
 // where it can), so that the four rows a 16-lane LDS access covers hit four different bank quarters; the sum therefore runs in
 // another ORDER than the gather kernel's -- same terms, results equal to rounding (deterministic from run to run).
 // Generic in the graph: rings come from the plan's own pattern; whole graphs only (no halo columns, all rows).

@@ -33,7 +33,7 @@ struct DeviceGuard {
   }
 };
 
-struct FusedPlan;  // tile decomposition for the single-launch kernel (cheb_fused.hip)
+struct FusedPlan;  // tile decomposition for the single-launch kernel (cheb_tiles.h)
 
 // Per-plan choices of dsph_plan_set_option (include/dsphere.h: DSPH_OPT_*).  They belong to the plan, not to the process:
 // the library reads no environment variable on the product path.
@@ -91,7 +91,7 @@ int launch_cheb_wgrad(const float* const* planes, int64_t plane_rows, const floa
 int launch_rows_pack(const float* src, int64_t src_rows, const int32_t* idx, int64_t n_idx,
                      float* buf, int64_t N, int32_t F, bool unpack, hipStream_t stream);
 
-// fused path (cheb_fused.hip)
+// fused path (cheb_fused.hip; the plan, its tile tables and the queries of them: cheb_tiles.hip)
 FusedPlan* fused_plan_build(const dsph_plan* plan, const int32_t* h_cols, const float* h_vals);
 void fused_plan_destroy(FusedPlan* fp);
 void fused_plan_invalidate(FusedPlan* fp);

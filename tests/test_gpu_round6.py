@@ -249,7 +249,7 @@ def test_finely_padded_mask_runs_on_the_strips():
 def test_quad_strips_on_a_map_with_an_incomplete_last_tile(drop):
     """The K = 5 quad-strip kernel reads a row as it comes (no clamp to the strip's halo: a run of steps touches a few rows of the
     table's ring tiles past the halo, for nothing) -- so those rows must exist, and the plan keeps every tile beside the map's last,
-    incomplete tile off the strips (cheb_fused.hip, `barred`).  A sphere cut off `drop` pixels before its end: whole maps against
+    incomplete tile off the strips (cheb_tiles.hip, `barred`).  A sphere cut off `drop` pixels before its end: whole maps against
     the float64 oracle, every row."""
     nside, K, Fin, Fout, N = 128, 5, 64, 64, 2
     cols, vals = _grid_ell(nside)

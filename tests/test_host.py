@@ -312,7 +312,7 @@ def test_bench_gpus_n_starts_its_own_ranks():
 
 def test_plan_builders_under_sanitizers():
     """SURVEY 5 / VERDICT r5 weak 10: the host halves of the library -- tile classification, class-T embedding, breadth-first ring
-    tables, rectangle merge, strip lists and the tape split, shard levels: 2,000 lines of index code in csrc/cheb_fused.hip and
+    tables, rectangle merge, strip lists and the tape split, shard levels: 2,000 lines of index code in csrc/cheb_tiles.hip and
     csrc/dsphere_api.hip -- compiled with -fsanitize=address,undefined against a stub HIP runtime (`make asan`, no GPU code) and
     driven through the C ABI on full-sphere, partial-sky, k-NN, sharded and ragged graphs (tools/asan/run_plan_builders.py)."""
     import subprocess
