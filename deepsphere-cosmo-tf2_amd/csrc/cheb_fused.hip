@@ -12,19 +12,10 @@
 // take the same path; a graph whose halo does not fit in LDS simply reports "not tileable" and
 // the caller falls back to the unfused kernels.
 //
-// Data layout (device):
-//   region_rows[tile_off[t] ..]   row ids of tile t's region, ring 0 (the tile's own rows, in
-//                                 order) first, then ring 1, ... ring D, each ring ordered so that
-//                                 (local index & 3) == (row id & 3) where the ring's mix allows
-//   ring_end[t][r]                number of region entries within r hops (r = 0..D)
-//   lcols/lvals                   tile-local ELL of the rows within D-1 hops, column = index into
-//                                 the region list (uint16), stored [slot][row] per tile so that
-//                                 lane i reads row i coalesced
-// LDS: two planes [Rmax][16] fp32 (16-byte slots XOR-swizzled so that 16 lanes reading the same
-// slot of 16 different rows hit 16 different bank groups) + the weight fragments of all
-// (order, slice) pairs in MFMA operand order.
-// Registers: each lane owns one (or two) region rows for the whole tile: their ELL values and
-// pre-swizzled LDS addresses stay in VGPRs across all slices and all maps of the batch.
+// This file is the host side of a call: which kernel takes which tiles (Route, make_route), where the packed weight images
+// of a block lie in the workspace (WeightImages), and the three launches built on the two -- the forward of one 64-column
+// block, the planes mode and the weight-gradient mode of the BFS-tile kernel.  The tile tables and their lists are described
+// in cheb_tiles.h (cheb_tiles.hip builds them), the kernels' LDS and register layouts in the *_kernel.h files.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -107,42 +98,65 @@ static int plane_rows_for(int rmax, int emax, int wt) {
 // Layers the BFS-tile kernel runs with four maps per item (FusedArgs::pack): at most four input channels (padded to four),
 // at most 16 output columns.  Its weight image then has two column blocks whatever the layer's width.
 static int bfs_packs(int32_t Fin, int32_t Fout) { return Fin == 4 && Fout <= 16 ? 4 : (Fin == 8 && Fout <= 32 ? 2 : 0); }
-static size_t wfrag_bytes(int32_t Fin, int32_t Fout, int32_t K) {
-  const int C = (Fin + FUSED_CH - 1) / FUSED_CH, NB = bfs_packs(Fin, Fout) ? 2 : (Fout + 31) / 32;
-  return (size_t)K * C * NB * 2048;
-}
 
-// weight images of the three fused kernels, back to back in the workspace: BFS-tile | structured-tile | strip
-static size_t all_frag_bytes(int32_t Fin, int32_t Fout, int32_t K) {
-  return wfrag_bytes(Fin, Fout, K) + struct_wfrag_bytes(Fin, Fout, K) + strip_wimg_bytes(Fin, Fout, K) +
-         2 * istrip_wimg_bytes(K, DSPH_PREC_BF16X6) +  // (the largest of the three arithmetics, two 32-column blocks)
-         (qstrip_shape_ok(Fin, Fout, K) ? qstrip_wimg_bytes() : 0) + (qstrip8_shape_ok(Fin, Fout, K) ? qstrip8_wimg_bytes() : 0);
+// The packed weight images of one 64-column block of a layer, back to back in the workspace:
+//   BFS-tile | structured-tile | strip pairs | input-side strips | K = 5 quad strips | K = 8 quad strips
+// as byte offsets into the block (a `wimg` / `wfrag` pointer is the block's base + one of them) and the block's size.  Callers
+// hold workspaces of dsph_workspace_bytes and, with DSPH_FWD_KEEP_WEIGHTS, packed images at these very offsets.
+struct WeightImages {
+  size_t bfs = 0, structured, strip, istrip, qstrip, qstrip8, total;
+  size_t bfs_bytes;  // the BFS-tile kernel's image: what it also keeps in the LDS next to the planes
+  WeightImages(int32_t Fin, int32_t Fout, int32_t K) {
+    const int C = (Fin + FUSED_CH - 1) / FUSED_CH, NB = bfs_packs(Fin, Fout) ? 2 : (Fout + 31) / 32;
+    bfs_bytes = (size_t)K * C * NB * 2048;
+    structured = bfs + bfs_bytes;
+    strip = structured + struct_wfrag_bytes(Fin, Fout, K);
+    istrip = strip + strip_wimg_bytes(Fin, Fout, K);
+    qstrip = istrip + 2 * istrip_wimg_bytes(K, DSPH_PREC_BF16X6);  // (the largest of the three arithmetics, two 32-column blocks)
+    qstrip8 = qstrip + (qstrip_shape_ok(Fin, Fout, K) ? qstrip_wimg_bytes() : 0);
+    total = qstrip8 + (qstrip8_shape_ok(Fin, Fout, K) ? qstrip8_wimg_bytes() : 0);
+  }
+};
+
+// A layer's workspace: one block of images per 64 output columns (so that the packed images of ALL blocks survive the call:
+// DSPH_FWD_KEEP_WEIGHTS), each block sized for the layer's widest one, and behind them the zero-padded copy of x when the
+// layer's channel count is not a multiple of four.
+struct LayerWorkspace {
+  size_t block, padded_x, total;  // a block's stride; offset of the padded copy = end of the blocks; everything
+  LayerWorkspace(const dsph_plan* plan, int64_t N, int32_t Fin, int32_t Fout, int32_t K) {
+    const int32_t Fp = pad4(Fin);
+    block = WeightImages(Fp, std::min(Fout, 64), K).total;
+    padded_x = (size_t)((Fout + 63) / 64) * block;
+    total = padded_x + (Fp != Fin ? (size_t)N * (size_t)plan->n_cols * (size_t)Fp * 4 : 0);
+  }
+};
+size_t fused_workspace_bytes(const dsph_plan* plan, int64_t N, int32_t Fin, int32_t Fout, int32_t K, int32_t) {
+  return LayerWorkspace(plan, N, Fin, Fout, K).total;
 }
 
 // The structured-tile kernel addresses x by 32-bit byte offsets inside a map: larger maps take BFS tables throughout.
 static bool want_full(const dsph_plan* plan, int32_t Fin, bool full) {
   return full || (uint64_t)plan->n_cols * (uint64_t)Fin * 4ull >= (1ull << 32);
 }
+// tiles of the structured kernel, class R or T (what a fork and a deferred activation ask about; none in a full table)
+static bool has_struct_tiles(const FusedTiles& ft) { return ft.r.n + ft.t.tiles.n > 0; }
 
-static bool supported_impl(const dsph_plan* plan, int32_t Fin, int32_t Fout, int32_t K, bool full) {
-  full = want_full(plan, Fin, full);
-  if (!plan->fused || plan->fused->wide) return false;
-  if (K < 2 || K - 1 > FUSED_DMAX) return false;
-  if (Fin % 4 != 0 || Fin < 4 || Fout < 1) return false;  // Fout > 64: one launch per 64-column block
-  const FusedTiles& ft = get_tiles(plan, K - 1, full);
-  if (!ft.ok) return false;
-  if (ft.r.n + ft.t.tiles.n > 0 && !struct_shape_ok(Fin, std::min(Fout, 64), K)) return false;
-  if (ft.part.n == 0) return true;  // every tile is class R
+// The tables a launch of this shape runs on (full: those of the planes and weight-gradient modes); nullptr: the fused kernels
+// do not take the shape on this plan.  One look-up: whoever needs the tables after asking "supported" asks here.
+static const FusedTiles* tiles_for(const dsph_plan* plan, int32_t Fin, int32_t Fout, int32_t K, bool full) {
+  if (!plan->fused || plan->fused->wide) return nullptr;
+  if (K < 2 || K - 1 > FUSED_DMAX) return nullptr;
+  if (Fin % 4 != 0 || Fin < 4 || Fout < 1) return nullptr;  // Fout > 64: one launch per 64-column block
+  const FusedTiles& ft = get_tiles(plan, K - 1, want_full(plan, Fin, full));
+  if (!ft.ok) return nullptr;
+  if (has_struct_tiles(ft) && !struct_shape_ok(Fin, std::min(Fout, 64), K)) return nullptr;
+  if (ft.part.n == 0) return &ft;  // every tile is class R
   const int pr = plane_rows_for(ft.rmax, ft.emax, ft.width);
-  if (pr == 0) return false;
+  if (pr == 0) return nullptr;
   // (the weight fragments need not fit beside the planes: the forward then reads them from global memory, cheb_fused_kernel's
   // WG variant; the planes and weight-gradient modes hold no weights)
-  return (size_t)2 * pr * FUSED_CH * 4 + FUSED_BIAS_BYTES <= (size_t)LDS_BYTES;
+  return (size_t)2 * pr * FUSED_CH * 4 + FUSED_BIAS_BYTES <= (size_t)LDS_BYTES ? &ft : nullptr;
 }
-
-// The forward takes any Fin >= 1: channel counts that are not a multiple of four are zero-padded into the workspace first
-// (fused_pad_kernel; the kernels load x in 16-byte pieces).  The first layer of every reference model has Fin = 1.
-static inline int32_t pad4(int32_t Fin) { return (Fin + 3) & ~3; }
 
 int fused_dmax() { return FUSED_DMAX; }
 int fused_num_cu(const dsph_plan* plan) { return plan->fused ? plan->fused->num_cu : 256; }
@@ -163,19 +177,19 @@ bool fused_tstep_tables(const dsph_plan* plan, TStepTables* out) {
   return true;
 }
 
+// (the forward takes any Fin >= 1: pad4)
 bool fused_supported(const dsph_plan* plan, int32_t Fin, int32_t Fout, int32_t K) {
-  return Fin >= 1 && supported_impl(plan, pad4(Fin), Fout, K, false);
+  return Fin >= 1 && tiles_for(plan, pad4(Fin), Fout, K, false) != nullptr;
 }
 
 // ... and with the BFS-tile kernel's weight fragments resident in the LDS (its fast variant: what "supported" meant before the
 // WG variant existed; the K > 5 routing of dsphere_api.hip prefers the chain of passes to the WG variant)
 bool fused_weights_resident(const dsph_plan* plan, int32_t Fin, int32_t Fout, int32_t K) {
-  if (!fused_supported(plan, Fin, Fout, K)) return false;
-  const int32_t Fp = pad4(Fin);
-  const FusedTiles& ft = get_tiles(plan, K - 1, want_full(plan, Fp, false));
-  if (ft.part.n == 0) return true;
-  const int pr = plane_rows_for(ft.rmax, ft.emax, ft.width);
-  return (size_t)2 * pr * FUSED_CH * 4 + wfrag_bytes(Fp, std::min(Fout, 64), K) + FUSED_BIAS_BYTES <= (size_t)LDS_BYTES;
+  const FusedTiles* ft = Fin >= 1 ? tiles_for(plan, pad4(Fin), Fout, K, false) : nullptr;
+  if (!ft) return false;
+  if (ft->part.n == 0) return true;
+  const int pr = plane_rows_for(ft->rmax, ft->emax, ft->width);
+  return (size_t)2 * pr * FUSED_CH * 4 + WeightImages(pad4(Fin), std::min(Fout, 64), K).bfs_bytes + FUSED_BIAS_BYTES <= (size_t)LDS_BYTES;
 }
 
 int fused_prepare(const dsph_plan* plan, int32_t K, int32_t Fin, int32_t flags) {
@@ -186,7 +200,7 @@ int fused_prepare(const dsph_plan* plan, int32_t K, int32_t Fin, int32_t flags) 
   } else {
     if (!fp || K < 2 || K - 1 > FUSED_DMAX) return DSPH_OK;  // nothing to build: the unfused path serves it
     const FusedTiles& ftp = get_tiles(plan, K - 1, want_full(plan, pad4(std::max(Fin, 1)), false));
-    if (ftp.ok && plan->opt.fork && ftp.r.n + ftp.t.tiles.n > 0 && ftp.part.n > 0) {  // a forward of this K may fork: the side stream exists before it
+    if (ftp.ok && plan->opt.fork && has_struct_tiles(ftp) && ftp.part.n > 0) {  // a forward of this K may fork: the side stream exists before it
       std::lock_guard<std::mutex> lock(fp->fork_mu);
       (void)side_stream_ready(plan, fp, nullptr, true);
     }
@@ -204,26 +218,65 @@ int fused_prepare(const dsph_plan* plan, int32_t K, int32_t Fin, int32_t flags) 
   return DSPH_OK;
 }
 
-// One rule for "does the strip kernel take this forward" (launch_fused_common and dsph_plan_strip_tiles): the shape is the
-// kernel's, and the strips are worth it for this batch.  A strip step (48 output pixels of one row, one map) takes a workgroup
+// ------------------------------------------------------------------------------------------
+// routing: which kernel takes which tiles of a call
+// ------------------------------------------------------------------------------------------
+
+enum class Mode { forward, planes, wgrad };
+enum class Strips { none, pairs, quad, input };  // strip pairs (cheb_strip), K = 5 quad strips (cheb_qstrip), input-side strips (cheb_istrip)
+
+// What one fused launch is -- the forward of one 64-column block of a layer, or the planes / weight-gradient mode of the
+// BFS-tile kernel -- and with that everything its routing depends on besides the plan's tables.  A launch fills all of it; a
+// query of the plan fills in what it was asked, and the defaults are what it assumes for the rest: a whole-map forward in the
+// Chebyshev basis with no activation and no pooling, y on a 16-byte boundary.
+struct FusedRequest {
+  Mode mode = Mode::forward;
+  int64_t N = 1;
+  int32_t Fin = 0;     // channels of x as the kernels see it (a multiple of four)
+  int32_t Fin_w = 0;   // channels of w: fewer than Fin when x is a zero-padded copy
+  int32_t Fout = 0;    // the columns of THIS launch (one 64-column block of the layer)
+  int32_t ld = 0;      // the layer's row stride of y, w, dy and dw
+  int32_t K = 0, precision = DSPH_PREC_BF16X3, act = DSPH_ACT_NONE, part = 0;
+  float alpha_rest = 2.f, beta_rest = 1.f;
+  const FusedPool* pool = nullptr;       // conv + pool: the kernels store the pooled map (launch_cheb_fused)
+  const TileList* only_tiles = nullptr;  // weight-gradient mode next to the quad-strip gradient: the BFS-tile kernel on these tiles only
+  const dsph_plan* plan = nullptr;
+  const float* x = nullptr; const float* w = nullptr; const float* bias = nullptr; float* y = nullptr;
+  unsigned char* ws = nullptr;  // this block's weight images (WeightImages)
+  hipStream_t stream = nullptr;
+};
+
+struct Route {
+  const FusedTiles& ft;      // the tables it was computed on: nothing below a route looks them up again
+  bool has_struct, has_bfs;  // work for the structured half (forward only) / tiles of this part in the BFS-tile kernel's own list
+  Strips strips;             // the strip kernel that takes the rectangles of this shape and batch ...
+  bool run_strips;           // ... and whether this part launches it (rectangles are interior tiles: PART_BOUNDARY has none)
+  const TileList* r;         // structured kernel without tables: class R, or what the strips leave of it
+  const TileTables* t;       // structured kernel with tables: class T, or what the quad strips leave of it
+  bool q8;                   // the K = 8 quad strips take their rectangles
+  const int32_t* bfs_tiles;  // BFS-tile kernel: its tiles of this part (nullptr: every tile of the plan, no list) ...
+  int bfs_n;                 // ... what the K = 8 strips leave of them, or the caller's only_tiles
+  int pack;                  // maps per item of the BFS-tile kernel (FusedArgs::pack; 0: one)
+  int pr;                    // its plane-row variant (plane_rows_for; 0: none)
+};
+
+// The strips are worth it for this batch: a strip step (48 output pixels of one row, one map) takes a workgroup
 // ~3.0 us, a 256-pixel tile of one map takes the tile kernels ~18.7 us of a CU (both measured at the headline shape): in units
 // of 0.1 us,   strips: (steps of the busiest workgroup, strip_makespan) x 30      tile kernels: tiles x N x 187 / CUs,
 // with 3 % in favour of the tile kernels.  Small maps (fewer items than CUs) and ragged masks at small batches lose that
 // comparison and keep their tiles on the tile kernels.  The rule depends on the batch and on the device's CU count, so the
 // same map can be summed in two different orders at two batch sizes (both within the tolerance of the precision); a caller
 // that needs batch- or shard-invariant bits fixes the choice per plan: dsph_plan_set_option(DSPH_OPT_STRIPS, 1 always | 2 never).
-//   Fout: the columns of THIS launch (one 64-column block of the layer); ld: the layer's row stride of y.
-static bool use_qstrips(const dsph_plan* plan, const FusedTiles& ft, int32_t Fin, int32_t Fout, int32_t K) {
-  return plan->opt.strip_form == 0 && ft.q5.n > 0 && qstrip_shape_ok(Fin, Fout, K);
+static bool use_qstrips(const dsph_plan* plan, const FusedTiles& ft, const FusedRequest& q) {
+  return plan->opt.strip_form == 0 && ft.q5.n > 0 && qstrip_shape_ok(q.Fin, q.Fout, q.K);
 }
-static bool strips_apply(const dsph_plan* plan, const FusedTiles& ft, int32_t Fin, int32_t Fout, int32_t K, int32_t precision, int64_t N,
-                         int32_t ld) {
-  const bool quad = use_qstrips(plan, ft, Fin, Fout, K);
-  if (!((quad || ft.n_pairs > 0) && (precision == DSPH_PREC_BF16X3 || (precision == DSPH_PREC_F16X3 && quad)) &&
-        strip_shape_ok(Fin, Fout, K) && ld % 4 == 0 && plan->n_cols * (int64_t)std::max(Fin, ld) * 4 < (1ll << 32)))
+static bool strips_apply(const dsph_plan* plan, const FusedTiles& ft, const FusedRequest& q, bool quad) {
+  if (!((quad || ft.n_pairs > 0) && (q.precision == DSPH_PREC_BF16X3 || (q.precision == DSPH_PREC_F16X3 && quad)) &&
+        strip_shape_ok(q.Fin, q.Fout, q.K) && q.ld % 4 == 0 && plan->n_cols * (int64_t)std::max(q.Fin, q.ld) * 4 < (1ll << 32)))
     return false;
   if (ft.strip_forced) return true;
   FusedPlan* fp = plan->fused;
+  const int64_t N = q.N;
   if (quad) {
     // (a quad-strip step takes 2.8 us, a tile-map 18.7; the tape of rows is cut evenly, so the span is a formula)
     if (N < 1) return false;
@@ -245,22 +298,23 @@ static bool strips_apply(const dsph_plan* plan, const FusedTiles& ft, int32_t Fi
 // The K = 8 quad strips take their rectangles for a whole-map forward of their shape (32 -> 32, three-term bf16, Chebyshev basis,
 // bias / ReLU epilogue) when the strips pay for the batch by the same kind of rule (a step 2.6 us, a tile on the breadth-first
 // kernel 27.5 us of a CU); DSPH_OPT_STRIPS 1 / 2: always / never.
-static bool q8_applies(const dsph_plan* plan, const FusedTiles& ft, int32_t Fin, int32_t Fout, int32_t K, int32_t precision, int64_t N,
-                       int32_t ld) {
+static bool q8_applies(const dsph_plan* plan, const FusedTiles& ft, const FusedRequest& q) {
   // (no limit on the size of a map: this kernel forms its addresses in 64 bits -- configs[3] is 6.4 GB of x)
   // (ld == Fout: the layer IS 32 columns wide -- the last 32 columns of a wider layer would find no room for this kernel's weight
   // image in their block of the workspace, which is sized for 64-column blocks)
-  if (ft.q8.n == 0 || !qstrip8_shape_ok(Fin, Fout, K) || (precision != DSPH_PREC_BF16X3 && precision != DSPH_PREC_F16X3) || ld != Fout || N < 1) return false;
+  if (ft.q8.n == 0 || !qstrip8_shape_ok(q.Fin, q.Fout, q.K) || (q.precision != DSPH_PREC_BF16X3 && q.precision != DSPH_PREC_F16X3) ||
+      q.ld != q.Fout || q.N < 1)
+    return false;
   if (plan->opt.strips == 1) return true;
-  const int64_t span = qstrip8_split(plan->fused->num_cu, ft.q8.tape_rows, N, ft.q8.tape_rows / std::max(1, ft.q8.n), nullptr, nullptr, nullptr);
-  return span * 26 * 103 < ft.q8.n_tiles * N * 275 / plan->fused->num_cu * 100;
+  const int64_t span = qstrip8_split(plan->fused->num_cu, ft.q8.tape_rows, q.N, ft.q8.tape_rows / std::max(1, ft.q8.n), nullptr, nullptr, nullptr);
+  return span * 26 * 103 < ft.q8.n_tiles * q.N * 275 / plan->fused->num_cu * 100;
 }
 
 // The input-side strip kernel takes the rectangles of every layer with at most 16 input channels (any arithmetic, K = 2 .. 5,
 // any output width), unless DSPH_OPT_STRIPS says never.  No cost rule: its workers are single waves and the kernel cuts the
 // strips into as many row segments as the batch needs, so small maps fill the device too (istrip_segments).
-static bool istrips_apply(const dsph_plan* plan, const FusedTiles& ft, int32_t Fin, int32_t K, int32_t Fout, int32_t ld) {
-  return ft.n_ipairs > 0 && plan->opt.strips != 2 && istrip_shape_ok(Fin, K) && Fout % 4 == 0 && ld % 4 == 0;
+static bool istrips_apply(const dsph_plan* plan, const FusedTiles& ft, const FusedRequest& q) {
+  return ft.n_ipairs > 0 && plan->opt.strips != 2 && istrip_shape_ok(q.Fin, q.K) && q.Fout % 4 == 0 && q.ld % 4 == 0;
 }
 static int istrip_nseg(const dsph_plan* plan, const FusedTiles& ft, int64_t N, int D, bool narrow) {
   FusedPlan* fp = plan->fused;
@@ -271,6 +325,45 @@ static int istrip_nseg(const dsph_plan* plan, const FusedTiles& ft, int64_t N, i
   return it->second;
 }
 
+// THE rule: which kernel takes which tiles of this launch.  The launches below, dsph_plan_strip_tiles, fused_pool_ok and
+// fused_qwgrad_applies all read its answer; none restates a condition of it.
+// forked: this launch is one half of a forked forward.
+static Route make_route(const dsph_plan* plan, const FusedTiles& ft, const FusedRequest& q, bool forked) {
+  const bool fwd = q.mode == Mode::forward, y_aligned = (reinterpret_cast<uintptr_t>(q.y) & 15) == 0;
+  const bool plain_epilogue = q.act == DSPH_ACT_NONE || q.act == DSPH_ACT_RELU;
+  Route rt{ft};
+  rt.has_struct = fwd && has_struct_tiles(ft);
+  rt.has_bfs = ft.part.count(q.part) > 0;
+  // rectangles of interior class-R tiles: a strip kernel, when it has this shape (the strip pairs and the quad strips read w
+  // and x with the same channel count; all of them store y in 16-byte pieces); the class-R list shrinks to the rest
+  const bool quad = use_qstrips(plan, ft, q);
+  rt.strips = Strips::none;
+  if (fwd && strips_apply(plan, ft, q, quad) && q.Fin_w == q.Fin && y_aligned) rt.strips = quad ? Strips::quad : Strips::pairs;
+  else if (fwd && istrips_apply(plan, ft, q) && y_aligned) rt.strips = Strips::input;
+  rt.run_strips = rt.strips != Strips::none && q.part != 2;
+  // (the quad strips took class-T tiles too: their own rest lists)
+  rt.r = rt.strips == Strips::quad ? &ft.qrrest : (rt.strips != Strips::none ? &ft.rrest : &ft.r);
+  rt.t = rt.strips == Strips::quad ? &ft.qt : &ft.t;
+  // K = 8, 32 -> 32: the rectangles of depth-7 regular tiles on the quad strips, the rest of the tiles on the BFS-tile kernel
+  rt.q8 = fwd && q.part != 2 && !q.pool && !forked && q.Fin_w == q.Fin && q.beta_rest != 0.f && plain_epilogue && y_aligned && q8_applies(plan, ft, q);
+  // part: 0 all tiles, 1 interior tiles (no row of another rank in their region), 2 boundary tiles
+  // the BFS-tile kernel handles the tiles of ft.part (every tile of a full table, the class-G ones otherwise)
+  rt.bfs_tiles = q.part == 0 && ft.part.n == ft.ntiles ? nullptr : ft.part.ptr(q.part);
+  rt.bfs_n = ft.part.count(q.part);
+  if (rt.q8) {  // (part 0: every tile the strips leave; part 1: the interior ones of them -- the boundary tiles are never the strips')
+    rt.bfs_tiles = ft.q8rest.ptr(q.part);
+    rt.bfs_n = ft.q8rest.count(q.part);
+  }
+  if (q.only_tiles) {  // (the strips' pixels go to cheb_qwgrad.hip: launch_cheb_fused_qwgrad)
+    rt.bfs_tiles = q.only_tiles->d;
+    rt.bfs_n = q.only_tiles->n;
+  }
+  // four maps per item where the layer has at most four input channels and 16 output columns (a single map gains nothing from two column blocks)
+  rt.pack = (plan->opt.pack && fwd && q.N >= 2) ? bfs_packs(q.Fin, q.Fout) : 0;
+  rt.pr = plane_rows_for(ft.rmax, ft.emax, ft.width);
+  return rt;
+}
+
 // conv + HealpyPool(p = 1) in one forward (launch_cheb_fused with a FusedPool): the input-side strip kernels, the structured
 // kernel and the BFS-tile kernel store the pooled map themselves.  Every layer whose tiles those kernels take -- not the
 // 64 -> 64 shape on maps large enough for the Clenshaw strips --, whole unsharded maps of whole tiles,
@@ -278,43 +371,33 @@ static int istrip_nseg(const dsph_plan* plan, const FusedTiles& ft, int64_t N, i
 bool fused_pool_ok(const dsph_plan* plan, int64_t N, int32_t Fin, int32_t Fout, int32_t K, int32_t act) {
   if (!plan->fused || N < 1 || !(act == DSPH_ACT_NONE || act == DSPH_ACT_RELU)) return false;
   if (!plan->levels.empty() || plan->n_cols != plan->n_rows || plan->n_rows % FUSED_P != 0 || K < 2 || K - 1 > FUSED_DMAX) return false;
-  if (!fused_supported(plan, Fin, Fout, K)) return false;
-  const FusedTiles& ft = get_tiles(plan, K - 1, want_full(plan, pad4(Fin), false));
-  if (!ft.ok || Fout % 4 != 0) return false;  // (pooled stores are 16 bytes wide)
-  // the Clenshaw strip kernel has no pooled epilogue: not where it would take tiles (either precision could be asked for)
-  return !strips_apply(plan, ft, pad4(Fin), std::min(Fout, 64), K, DSPH_PREC_BF16X3, N, Fout);
+  const FusedTiles* ft = Fin >= 1 ? tiles_for(plan, pad4(Fin), Fout, K, false) : nullptr;
+  if (!ft || Fout % 4 != 0) return false;  // (pooled stores are 16 bytes wide)
+  // the Clenshaw strip kernel has no pooled epilogue: not where it would take tiles.  Asked for the three-term bf16 arithmetic
+  // (either precision could be asked for), the layer's first block, an aligned y and an x that needs no padding.
+  FusedRequest q;
+  q.N = N; q.Fin = q.Fin_w = pad4(Fin); q.Fout = std::min(Fout, 64); q.ld = Fout; q.K = K; q.precision = DSPH_PREC_BF16X3;
+  const Strips s = make_route(plan, *ft, q, false).strips;
+  return s != Strips::pairs && s != Strips::quad;
 }
 
-
-// tiles a forward of this shape hands to the strip kernel: the same predicate the launch uses, for the layer's first 64-column
-// block (a layer with Fout = 96 runs its first block through the strips and reports them; one with Fout < 64 has none)
+// tiles a forward of this shape hands to a strip kernel: the route of the layer's first 64-column block (a layer with
+// Fout = 96 runs its first block through the strips and reports them; one with Fout < 64 has none on the Clenshaw strips).
+// Assumed, because the question does not say: a whole-map forward in the Chebyshev basis with no activation, an aligned y.
 int64_t fused_strip_tiles(const dsph_plan* plan, int64_t N, int32_t Fin, int32_t Fout, int32_t K, int32_t precision) {
   if (!plan->fused || K < 2 || K - 1 > FUSED_DMAX) return 0;
-  if (istrip_shape_ok(pad4(Fin), K)) {
-    const FusedTiles& fti = get_tiles(plan, K - 1, want_full(plan, pad4(Fin), false));
-    return fti.ok && istrips_apply(plan, fti, pad4(Fin), K, std::min(Fout, 64), Fout) ? fti.n_strip_tiles : 0;
-  }
-  if (qstrip8_shape_ok(Fin, Fout, K)) {
-    const FusedTiles& ft8 = get_tiles(plan, K - 1, want_full(plan, Fin, false));
-    return ft8.ok && q8_applies(plan, ft8, Fin, Fout, K, precision, N, Fout) ? ft8.q8.n_tiles : 0;
-  }
-  if (Fin != pad4(Fin) || Fout < 64) return 0;
-  const FusedTiles& ft = get_tiles(plan, K - 1, want_full(plan, Fin, false));
+  const FusedTiles& ft = get_tiles(plan, K - 1, want_full(plan, pad4(Fin), false));
   if (!ft.ok) return 0;
-  return strips_apply(plan, ft, Fin, 64, K, precision, N, Fout) ? (use_qstrips(plan, ft, Fin, 64, K) ? ft.q5.n_tiles : ft.n_strip_tiles) : 0;
+  FusedRequest q;
+  q.N = N; q.Fin = pad4(Fin); q.Fin_w = Fin; q.Fout = std::min(Fout, 64); q.ld = Fout; q.K = K; q.precision = precision;
+  const Route rt = make_route(plan, ft, q, false);
+  if (rt.q8) return ft.q8.n_tiles;
+  return rt.strips == Strips::quad ? ft.q5.n_tiles : (rt.strips != Strips::none ? ft.n_strip_tiles : 0);
 }
 
-// two fragment layouts: the BFS-tile kernel's and, behind it, the structured-tile kernel's
-// (one fragment area per 64-column block of the layer, so that the packed images of ALL blocks survive the call:
-// DSPH_FWD_KEEP_WEIGHTS)
-static size_t frag_area_bytes(int32_t Fp, int32_t Fout, int32_t K) {
-  return (size_t)((Fout + 63) / 64) * all_frag_bytes(Fp, std::min(Fout, 64), K);
-}
-size_t fused_workspace_bytes(const dsph_plan* plan, int64_t N, int32_t Fin, int32_t Fout, int32_t K, int32_t) {
-  const int32_t Fp = pad4(Fin);
-  const size_t frag = frag_area_bytes(Fp, Fout, K);
-  return frag + (Fp != Fin ? (size_t)N * (size_t)plan->n_cols * (size_t)Fp * 4 : 0);  // + the zero-padded copy of x
-}
+// ------------------------------------------------------------------------------------------
+// the small kernels of this file: zero-padded copy of x, weight preparation, reduction of the weight gradient's slabs
+// ------------------------------------------------------------------------------------------
 
 __global__ __launch_bounds__(256) void fused_pad_kernel(const float* __restrict__ x, float4* __restrict__ out, int64_t rows,
                                                         int Fin, int Q) {  // out[r][q] <- x[r][4q .. 4q+3], zeros past Fin
@@ -330,10 +413,6 @@ __global__ __launch_bounds__(256) void fused_pad_kernel(const float* __restrict_
     out[i] = v;
   }
 }
-
-// ------------------------------------------------------------------------------------------
-// weight preparation + launch
-// ------------------------------------------------------------------------------------------
 
 // Weight fragments in MFMA operand order, one 2 KiB block per (order k, slice c, column block nb):
 //   bf16x3: lane l, element j  <- w[(c*16 + 8*(l>>5) + j)*K + k][32*nb + (l&31)], hi at +0, lo at +1024
@@ -364,175 +443,6 @@ __global__ __launch_bounds__(256) void fused_wprep_kernel(const float* __restric
       reinterpret_cast<float*>(base)[j * 64 + l] = v;
     }
   }
-}
-
-// Diagnostic build only (make ABLATE=1): DSPH_DBG_ONLY=s / b launches only the structured-tile / only the BFS-tile kernel
-// (wrong results by construction: the other tiles of y stay unwritten).  The shipped library always launches both.
-static inline bool dbg_only(char which) {
-#ifdef DSPH_ABLATE
-  const char* e = getenv("DSPH_DBG_ONLY");
-  return e && e[0] == which;
-#else
-  (void)which;
-  return false;
-#endif
-}
-
-static int launch_fused_common(const dsph_plan* plan, const float* x, const float* w, const float* bias,
-                               float* y, float* planes_out, int64_t N, int32_t Fin, int32_t Fout, int32_t K,
-                               int32_t act, int32_t precision, float alpha_rest, float beta_rest,
-                               void* workspace, size_t workspace_bytes, hipStream_t stream,
-                               const float* dy = nullptr, float* dw = nullptr, int32_t ld = 0, int32_t part = 0,
-                               int32_t Fin_w = 0, int32_t only = 0,  // only: 0 every launch, 1 the structured ones, 2 the BFS-tile one
-                               bool keep_weights = false,            // the weight images in the workspace are those of an earlier call
-                               const FusedPool* pool = nullptr,      // conv + pool: the strips store the pooled map (launch_cheb_fused)
-                               const int32_t* wg_tiles = nullptr, int wg_ntiles = -1);  // weight-gradient mode on these tiles only
-
-int launch_cheb_fused(const dsph_plan* plan, const float* x, const float* w, const float* bias,
-                      float* y, int64_t N, int32_t Fin, int32_t Fout, int32_t K, int32_t act,
-                      int32_t precision, float alpha_rest, float beta_rest, void* workspace,
-                      size_t workspace_bytes, hipStream_t stream, int32_t part, bool keep_weights, const FusedPool* pool) {
-  if (pool != nullptr && !(part == 0 && fused_pool_ok(plan, N, Fin, Fout, K, act) && pool->y != nullptr && (pool->type == 1 || pool->type == 2) &&
-                           ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(pool->y)) & 15) == 0)) {
-    set_error("cheb_fused: this plan / shape has no fused pooling (whole unsharded maps, no or ReLU activation, not the Clenshaw strips' shape)");
-    return DSPH_E_UNSUPPORTED;
-  }
-  // more than 64 output columns: one launch per 64-column block (the recurrence is repeated; still one pass
-  // over x per block instead of the unfused path's K planes through HBM)
-  // The structured-tile kernel fuses bias and ReLU; with any other activation both fused kernels write the pre-activation
-  // and one elementwise pass finishes y (only when class-R tiles exist: the BFS-tile kernel knows every activation).
-  bool defer_act = false;
-  if (act != DSPH_ACT_NONE && act != DSPH_ACT_RELU && K - 1 <= FUSED_DMAX && K >= 2) {
-    const FusedTiles& ft = get_tiles(plan, K - 1, want_full(plan, pad4(Fin), false));
-    defer_act = ft.ok && ft.r.n + ft.t.tiles.n > 0;
-  }
-  // (two-part launches: each part writes the pre-activation of its tiles and then finishes exactly those tiles' rows)
-  // Fin not a multiple of four: a zero-padded copy of x behind the weight fragments in the workspace (with a two-part
-  // launch both parts copy: the halo rows arrive between them)
-  const int32_t Fin_w = Fin;
-  if (Fin != pad4(Fin)) {
-    const int32_t Fp = pad4(Fin);
-    const size_t frag = frag_area_bytes(Fp, Fout, K);
-    const size_t need = frag + (size_t)N * (size_t)plan->n_cols * (size_t)Fp * 4;
-    if (!workspace || workspace_bytes < need) {
-      set_error("cheb_fused: workspace %zu < %zu", workspace_bytes, need);
-      return DSPH_E_WORKSPACE;
-    }
-    float* xp = reinterpret_cast<float*>(static_cast<unsigned char*>(workspace) + frag);
-    const int rc = launch_fused_pad(x, xp, N * plan->n_cols, Fin, Fp, stream);
-    if (rc != DSPH_OK) return rc;
-    x = xp;
-    Fin = Fp;
-  }
-  // structured launches and the BFS-tile launch write disjoint tiles: when a forward has both, the latter goes to the plan's
-  // side stream (FusedPlan::side), forked behind whatever the caller's stream holds so far and joined before this call returns
-  FusedPlan* fp = plan->fused;
-  bool fork = false;
-  if (fp && plan->opt.fork && K >= 2 && K - 1 <= FUSED_DMAX) {
-    const FusedTiles& ft = get_tiles(plan, K - 1, want_full(plan, Fin, false));
-    const int ng = !ft.ok ? 0 : ft.part.count(part);
-    // (worth its two event operations only when the structured launches run for a while: two tile-maps per CU and more --
-    // BASELINE configs[0], 168 tile-maps, is 13 us faster without it, configs[1] 29 us faster with it.  Under a stream
-    // capture the fork and the join are edges of the graph and cost nothing at replay: every forward with both kinds of tiles
-    // forks there, provided the side stream exists already -- dsph_plan_prepare made it)
-    bool big = N * (int64_t)(ft.r.n + ft.t.tiles.n) >= 2 * (int64_t)fp->num_cu;
-    if (!big && fp->side && stream != nullptr) {
-      hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-      big = hipStreamIsCapturing(stream, &cs) == hipSuccess && cs == hipStreamCaptureStatusActive;
-    }
-    fork = ft.ok && ft.r.n + ft.t.tiles.n > 0 && ng > 0 && big;
-  }
-  const size_t blk_frag = all_frag_bytes(Fin, std::min(Fout, 64), K);
-  if (!workspace || workspace_bytes < frag_area_bytes(Fin, Fout, K)) {
-    set_error("cheb_fused: workspace %zu < %zu", workspace_bytes, frag_area_bytes(Fin, Fout, K));
-    return DSPH_E_WORKSPACE;
-  }
-  for (int32_t cb = 0; cb < Fout; cb += 64) {
-    unsigned char* blk_ws = static_cast<unsigned char*>(workspace) + (size_t)(cb / 64) * blk_frag;  // this block's weight images
-    fused_images_begin(plan, blk_ws, fused_images_key(Fin, Fin_w, std::min<int32_t>(64, Fout - cb), K, Fout, precision, beta_rest != 0.f,
-                                                      N >= 2, plan->opt.pack), keep_weights);
-    const FusedPool pool_blk{pool ? pool->y + cb : nullptr, pool ? pool->type : 0};  // (this block's columns of the pooled map)
-    const FusedPool* pool_b = pool ? &pool_blk : nullptr;
-    auto run = [&](hipStream_t st, int32_t only) {
-      return launch_fused_common(plan, x, w + cb, bias ? bias + cb : nullptr, y + cb, nullptr, N, Fin,
-                                 std::min<int32_t>(64, Fout - cb), K, defer_act ? DSPH_ACT_NONE : act, precision, alpha_rest,
-                                 beta_rest, blk_ws, blk_frag, st, nullptr, nullptr, Fout, part, Fin_w, only, keep_weights, pool_b);
-    };
-    if (fork) {
-      std::unique_lock<std::mutex> lock(fp->fork_mu);
-      if (side_stream_ready(plan, fp, stream, true)) {
-        DSPH_HIP(hipEventRecord(fp->ev_fork, stream));             // (nothing is on the side stream yet: a failure here or in the
-        DSPH_HIP(hipStreamWaitEvent(fp->side, fp->ev_fork, 0));    //  next line leaves nothing to join)
-        const int rc_b = run(fp->side, 2);
-        const hipError_t e_rec = hipEventRecord(fp->ev_join, fp->side);
-        const int rc_s = run(stream, 1);
-        // the join happens whatever went wrong in between: the side stream never outlives the call.  (Without the join
-        // event the only way to join is to wait for the side stream on the host -- not while the caller is capturing, where
-        // a synchronisation would invalidate the capture: the error goes back instead, the capture is lost either way.)
-        hipError_t e_join = hipSuccess;
-        if (e_rec == hipSuccess) e_join = hipStreamWaitEvent(stream, fp->ev_join, 0);
-        else {
-          hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-          if (hipStreamIsCapturing(stream, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone) e_join = hipStreamSynchronize(fp->side);
-        }
-        if (rc_b != DSPH_OK || rc_s != DSPH_OK) fused_images_forget(plan, blk_ws);
-        if (rc_b != DSPH_OK) return rc_b;
-        if (rc_s != DSPH_OK) return rc_s;
-        if (e_rec != hipSuccess) return hip_fail(e_rec, "hipEventRecord(join)");
-        if (e_join != hipSuccess) return hip_fail(e_join, "join of the side stream");
-        continue;
-      }
-    }
-    const int rc = run(stream, 0);
-    if (rc != DSPH_OK) { fused_images_forget(plan, blk_ws); return rc; }
-  }
-  if (pool != nullptr) {
-    return DSPH_OK;  // (every kernel has stored its tiles pooled; y, the scratch of the C ABI, stays untouched)
-  }
-  if (defer_act) {
-    const int64_t orows = plan->levels.empty() ? plan->n_rows : plan->levels[0];
-    if (part == 0) return launch_struct_act(y, N * orows, Fout, Fout, act, stream);
-    // a part finishes the rows of its own tiles only: INTERIOR and BOUNDARY can be issued in any order, repeated, or alone
-    const FusedTiles& ft = get_tiles(plan, K - 1, want_full(plan, Fin, false));
-    return launch_struct_act_tiles(y, ft.all.ptr(part), ft.all.count(part), N, orows, Fout, Fout, act, stream);
-  }
-  return DSPH_OK;
-}
-
-// Planes mode of the same kernel: T_1 .. T_{K-1} of x, each (N, n_cols, Fin), valid on the plan's output rows.
-bool fused_planes_supported(const dsph_plan* plan, int32_t Fin, int32_t K) { return supported_impl(plan, Fin, 1, K, true); }
-
-int launch_cheb_fused_planes(const dsph_plan* plan, const float* x, float* planes_out, int64_t N, int32_t Fin,
-                             int32_t K, float alpha_rest, float beta_rest, hipStream_t stream) {
-  return launch_fused_common(plan, x, nullptr, nullptr, nullptr, planes_out, N, Fin, 1, K, DSPH_ACT_NONE,
-                             DSPH_PREC_FP32, alpha_rest, beta_rest, nullptr, 0, stream);
-}
-
-// ---- weight-gradient mode ------------------------------------------------------------------------------
-static int fused_grid(const dsph_plan* plan, const FusedTiles& ft, int ntiles = -1) {
-  if (ntiles < 0) ntiles = ft.ntiles;
-  return std::max(8, std::min(plan->fused->num_cu, (ntiles + 7) / 8 * 8));
-}
-
-// slices per launch: as many accumulator tiles (one per slice and order, 8 KiB each) as fit the LDS next to the planes
-static int wgrad_slices_per_launch(const dsph_plan* plan, int32_t K) {
-  const FusedTiles& ft = get_tiles(plan, K - 1, true);
-  const int pr = plane_rows_for(ft.rmax, ft.emax, ft.width);
-  if (pr == 0) return 0;
-  const long freeb = (long)LDS_BYTES - 2L * pr * FUSED_CH * 4;
-  return (int)(freeb / ((long)K * WG_TILE_BYTES));
-}
-
-bool fused_wgrad_supported(const dsph_plan* plan, int32_t Fin, int32_t Fout, int32_t K) {
-  return supported_impl(plan, Fin, Fout, K, true) && wgrad_slices_per_launch(plan, K) >= 1;
-}
-
-size_t fused_wgrad_workspace_bytes(const dsph_plan* plan, int32_t Fin, int32_t Fout, int32_t K) {
-  if (!fused_wgrad_supported(plan, Fin, Fout, K)) return 0;
-  const FusedTiles& ft = get_tiles(plan, K - 1, true);
-  const int C = (Fin + FUSED_CH - 1) / FUSED_CH;
-  // (a slab per workgroup and pixel half; a small map's batch is split over up to num_cu workgroups in all: fused_wgrad_gy)
-  return (size_t)2 * std::max(fused_grid(plan, ft), plan->fused->num_cu) * C * K * 16 * 64 * sizeof(float);
 }
 
 // dw[(f*K + k)*Fout + o] = sum over slabs, in a fixed order (deterministic): sixteen lanes per element, lane p sums the slabs
@@ -577,67 +487,222 @@ int launch_fused_pad(const float* x, float* xp, int64_t rows, int32_t Fin, int32
   return DSPH_OK;
 }
 
-int launch_cheb_fused_wgrad(const dsph_plan* plan, const float* x, const float* dy, float* dw, int64_t N,
-                            int32_t Fin, int32_t Fout, int32_t K, int32_t precision, float alpha_rest, float beta_rest,
-                            void* workspace, size_t workspace_bytes, hipStream_t stream, int32_t Fin_w) {
-  if (!fused_wgrad_supported(plan, Fin, Fout, K)) {
-    set_error("cheb_fused_wgrad: plan/shape not supported");
+// ------------------------------------------------------------------------------------------
+// launches
+// ------------------------------------------------------------------------------------------
+
+// Arithmetic of the structured-tile, strip-pair and input-side strip kernels for a request: DSPH_PREC_F16X3 is the quad strips'
+// own; every other kernel of the forward runs the six-term split then (same accuracy)
+static int32_t struct_arithmetic(int32_t precision) { return precision == DSPH_PREC_F16X3 ? DSPH_PREC_BF16X6 : precision; }
+// ... and of the BFS-tile kernel, which has two contraction arithmetics: the six-term split of the structured kernel is fp32-equivalent
+static int32_t bfs_arithmetic(int32_t precision) {
+  return struct_arithmetic(precision) == DSPH_PREC_BF16X6 ? DSPH_PREC_FP32 : precision;
+}
+
+// Diagnostic build only (make ABLATE=1): DSPH_DBG_ONLY=s / b launches only the structured-tile / only the BFS-tile kernel
+// (wrong results by construction: the other tiles of y stay unwritten), DSPH_FUSED_DEBUG sets FusedArgs::dbg (timing-only
+// ablations).  The shipped library always launches both and never skips work.
+static inline bool dbg_only(char which) {
+#ifdef DSPH_ABLATE
+  const char* e = getenv("DSPH_DBG_ONLY");
+  return e && e[0] == which;
+#else
+  (void)which;
+  return false;
+#endif
+}
+static inline int dbg_bits() {
+#ifdef DSPH_ABLATE
+  const char* dbg = getenv("DSPH_FUSED_DEBUG");
+  return dbg ? atoi(dbg) : 0;
+#else
+  return 0;
+#endif
+}
+
+// Diagnostic build only (make STAMPS=1): the BFS-tile kernel of a forward writes its clock stamps into a buffer that
+// DSPH_STAMPS_DUMP=1 prints after the launch.  Nothing in the shipped library.
+#ifdef DSPH_STAMPS
+static constexpr size_t STAMP_WORDS = 8 * 8 * 32;
+static unsigned long long* d_stamps = nullptr;
+static int stamps_begin(FusedArgs& args, hipStream_t stream) {
+  if (!d_stamps) DSPH_HIP(hipMalloc(&d_stamps, STAMP_WORDS * 8));
+  DSPH_HIP(hipMemsetAsync(d_stamps, 0, STAMP_WORDS * 8, stream));
+  args.stamps = d_stamps;
+  return DSPH_OK;
+}
+static int stamps_end(int rc, hipStream_t stream) {
+  if (rc != DSPH_OK || !getenv("DSPH_STAMPS_DUMP")) return rc;
+  std::vector<unsigned long long> h(STAMP_WORDS);
+  if (hipStreamSynchronize(stream) != hipSuccess) return rc;
+  if (hipMemcpy(h.data(), d_stamps, STAMP_WORDS * 8, hipMemcpyDeviceToHost) != hipSuccess) return rc;
+  for (int w = 0; w < 8; ++w)
+    for (int it = 0; it < 8; ++it) {
+      fprintf(stderr, "STAMP wave %d item %d:", w, it + 4);
+      const unsigned long long* r = &h[((size_t)w * 8 + it) * 32];
+      for (int i = 1; i < 32; ++i) fprintf(stderr, " %lld", r[i] && r[i - 1] ? (long long)(r[i] - r[i - 1]) : -1LL);
+      fprintf(stderr, " | t0 %llu\n", r[0]);
+    }
+  return rc;
+}
+#else
+static inline int stamps_begin(FusedArgs&, hipStream_t) { return DSPH_OK; }
+static inline int stamps_end(int rc, hipStream_t) { return rc; }
+#endif
+
+// What every launch checks first: the shape runs on these tables (ft: tiles_for), the block's images fit, the pointers the
+// kernels load and store in 16-byte pieces are aligned (out: the planes, or the slabs of the weight gradient).
+static int check_request(const FusedRequest& rq, const FusedTiles* ft, size_t ws_bytes, size_t ws_need, const void* out) {
+  if (!ft) {
+    set_error("cheb_fused: plan/shape not supported");
     return DSPH_E_UNSUPPORTED;
   }
-  const size_t need = fused_wgrad_workspace_bytes(plan, Fin, Fout, K);
-  if (!workspace || workspace_bytes < need) {
-    set_error("cheb_fused_wgrad: workspace %zu < %zu", workspace_bytes, need);
+  if (ws_need > 0 && (!rq.ws || ws_bytes < ws_need)) {
+    set_error("cheb_fused: workspace %zu < %zu", ws_bytes, ws_need);
     return DSPH_E_WORKSPACE;
   }
-  for (int32_t cb = 0; cb < Fout; cb += 64) {
-    const int rc = launch_fused_common(plan, x, nullptr, nullptr, static_cast<float*>(workspace), nullptr, N, Fin,
-                                       std::min<int32_t>(64, Fout - cb), K, DSPH_ACT_NONE, precision, alpha_rest,
-                                       beta_rest, nullptr, 0, stream, dy + cb, dw + cb, Fout, 0, Fin_w);
+  if ((reinterpret_cast<uintptr_t>(rq.x) & 15) || (reinterpret_cast<uintptr_t>(rq.ws) & 15) || (reinterpret_cast<uintptr_t>(out) & 15)) {
+    set_error("cheb_fused: x, workspace and planes must be 16-byte aligned");
+    return DSPH_E_BADARG;
+  }
+  return DSPH_OK;
+}
+
+// the part of a strip or tile launch that is the same for every kernel of the call
+static LaunchBase launch_base(const FusedRequest& rq) {
+  LaunchBase b;
+  b.x = rq.x; b.w = rq.w; b.bias = rq.bias; b.y = rq.y;
+  b.gvals8 = rq.plan->fused->d_gvals8;
+  b.gdiag = rq.plan->fused->d_gdiag;
+  b.x_rows = rq.plan->n_cols; b.y_rows = out_rows(rq.plan); b.N = rq.N;
+  b.act = rq.act; b.ld = rq.ld; b.num_cu = rq.plan->fused->num_cu;
+  b.cheb = rq.beta_rest != 0.f;
+  if (rq.pool != nullptr) {
+    b.pool = rq.pool->type;
+    b.ypool = rq.pool->y;
+    b.ypool_rows = rq.plan->n_rows / 4;
+  }
+  return b;
+}
+
+// the strip kernel of the route on the rectangles
+static int launch_strips(const FusedRequest& rq, const Route& rt, const WeightImages& img, const LaunchBase& base) {
+  const dsph_plan* plan = rq.plan;
+  const FusedTiles& ft = rt.ft;
+  if (rt.strips == Strips::quad) {
+    QStripLaunch qs;
+    static_cast<LaunchBase&>(qs) = base;
+    qs.wimg = rq.ws + img.qstrip;
+    qs.strips = ft.q5.d_strips;
+    qs.tab = ft.q5.d_tab;
+    qs.prefix = ft.q5.d_prefix;
+    qs.tape_rows = ft.q5.tape_rows;
+    qs.nstrips = ft.q5.n; qs.Fin = rq.Fin; qs.Fout = rq.Fout;
+    qs.f16 = rq.precision == DSPH_PREC_F16X3;
+    qs.f16_xexp = plan->opt.f16_xexp;
+    qs.prep_weights = fused_images_claim(plan, rq.ws, IMG_QSTRIP);
+    return launch_cheb_qstrip(qs, rq.stream);
+  }
+  if (rt.strips == Strips::pairs) {
+    StripLaunch st;
+    static_cast<LaunchBase&>(st) = base;
+    st.wimg = rq.ws + img.strip;
+    st.pairs = ft.d_pairs;
+    st.npairs = ft.n_pairs; st.Fin = rq.Fin; st.Fout = rq.Fout; st.K = rq.K; st.precision = struct_arithmetic(rq.precision);
+    st.generic = plan->opt.strip_generic;
+    st.prep_weights = fused_images_claim(plan, rq.ws, IMG_STRIP);
+    return launch_cheb_strip(st, rq.stream);
+  }
+  IStripLaunch is;
+  static_cast<LaunchBase&>(is) = base;
+  is.wimg = rq.ws + img.istrip;
+  is.pairs = ft.d_ipairs;
+  is.npairs = ft.n_ipairs; is.Fin = rq.Fin; is.Fin_w = rq.Fin_w; is.Fout = rq.Fout; is.K = rq.K; is.precision = struct_arithmetic(rq.precision);
+  // (row segments for the items the kernel will deal: maps, or pairs of maps in the one-channel kernel's pair mode)
+  is.nseg = istrip_nseg(plan, ft, istrip_pairs(rq.Fin_w, rq.Fout) ? (rq.N + 1) / 2 : rq.N, rq.K - 1, istrip_narrow(rq.Fin_w));
+  is.prep_weights = fused_images_claim(plan, rq.ws, IMG_ISTRIP);
+  return launch_cheb_istrip(is, rq.stream);
+}
+
+// The structured half of a forward: the strip kernel on the rectangles, then the structured-tile kernel on the class-R tiles
+// (without tables) and the class-T tiles (with per-tile tables) of the route.
+static int forward_structured(const FusedRequest& rq, const Route& rt, const WeightImages& img) {
+  if (dbg_only('b')) return DSPH_OK;
+  const dsph_plan* plan = rq.plan;
+  const LaunchBase base = launch_base(rq);
+  if (rt.run_strips) {
+    const int rc = launch_strips(rq, rt, img, base);
+    if (rc != DSPH_OK) return rc;
+  }
+  StructLaunch sl;
+  static_cast<LaunchBase&>(sl) = base;
+  sl.wfrag = rq.ws + img.structured;
+  sl.Fin = rq.Fin; sl.Fin_w = rq.Fin_w; sl.Fout = rq.Fout; sl.K = rq.K; sl.precision = struct_arithmetic(rq.precision);
+  sl.allow_pack = plan->opt.pack;
+  bool struct_prep = true;  // the first structured launch of this call packs the fragments, if the block lacks them
+  if (rt.r->count(rq.part) > 0) {
+    sl.tiles = rt.r->ptr(rq.part);
+    sl.ntiles = rt.r->count(rq.part);
+    sl.prep_weights = fused_images_claim(plan, rq.ws, IMG_STRUCT);
+    struct_prep = false;
+    const int rc = launch_cheb_struct(sl, rq.stream);
+    if (rc != DSPH_OK) return rc;
+  }
+  if (rt.t->tiles.count(rq.part) > 0) {
+    sl.tiles = rt.t->tiles.ptr(rq.part);
+    sl.tabrow = rt.t->rows(rq.part);
+    sl.tabvals = rt.t->vals(rq.part);
+    sl.ntiles = rt.t->tiles.count(rq.part);
+    sl.prep_weights = struct_prep && fused_images_claim(plan, rq.ws, IMG_STRUCT);
+    const int rc = launch_cheb_struct(sl, rq.stream);
     if (rc != DSPH_OK) return rc;
   }
   return DSPH_OK;
 }
 
-// ---- quad-strip weight gradient (cheb_qwgrad.hip) -----------------------------------------------------------------------
+static int fused_grid(const dsph_plan* plan, int ntiles) { return std::max(8, std::min(plan->fused->num_cu, (ntiles + 7) / 8 * 8)); }
 
-// The quad-strip weight gradient takes the strips' pixels of a K = 5, 64 -> 64 j layer in the three-term bf16 arithmetic when
-// the forward of that shape would run on the quad strips (same tables, same cost rule) and L~ is symmetric; the BFS-tile
-// kernel's weight-gradient mode takes the tiles the strips leave over.
-bool fused_qwgrad_applies(const dsph_plan* plan, int64_t N, int32_t Fin, int32_t Fout, int32_t K, int32_t precision) {
-  if (precision != DSPH_PREC_BF16X3 || !qwgrad_shape_ok(Fin, 64, K) || Fout % 64 != 0) return false;
-  if (!plan->fused || plan->fused->wide || plan->n_rows != plan->n_cols || !plan->levels.empty()) return false;
-  if (!fused_wgrad_supported(plan, Fin, Fout, K)) return false;
-  const FusedTiles& ft = get_tiles(plan, K - 1, false);
-  if (!ft.ok || !use_qstrips(plan, ft, Fin, 64, K) || !strips_apply(plan, ft, Fin, 64, K, DSPH_PREC_BF16X3, N, Fout)) return false;
-  return fused_symmetric(plan);
-}
-
-size_t fused_qwgrad_workspace_bytes(const dsph_plan* plan) { return qwgrad_slab_bytes(plan->fused ? plan->fused->num_cu : 256); }
-
-// workspace: [the BFS-tile kernel's slabs (fused_wgrad_workspace_bytes, 256-aligned) | the quad strips' slabs]
-int launch_cheb_fused_qwgrad(const dsph_plan* plan, const float* x, const float* dy, float* dw, int64_t N, int32_t Fin, int32_t Fout,
-                             int32_t K, float alpha_rest, float beta_rest, void* workspace, size_t bfs_slab_bytes, hipStream_t stream) {
-  const FusedTiles& ft = get_tiles(plan, K - 1, false);
-  for (int32_t cb = 0; cb < Fout; cb += 64) {
-    if (ft.nonq.n > 0) {
-      const int rc = launch_fused_common(plan, x, nullptr, nullptr, static_cast<float*>(workspace), nullptr, N, Fin, 64, K, DSPH_ACT_NONE,
-                                         DSPH_PREC_BF16X3, alpha_rest, beta_rest, nullptr, 0, stream, dy + cb, dw + cb, Fout, 0, Fin, 0, false,
-                                         nullptr, ft.nonq.d, ft.nonq.n);
-      if (rc != DSPH_OK) return rc;
-    }
-    QWgradLaunch q;
-    q.x = x; q.dy = dy + cb; q.dw = dw + cb;
-    q.slabs = reinterpret_cast<float*>(static_cast<char*>(workspace) + bfs_slab_bytes);
-    q.strips = ft.q5.d_strips; q.prefix = ft.q5.d_prefix; q.tape_rows = ft.q5.tape_rows; q.tab = ft.q5.d_tab;
-    q.gvals8 = plan->fused->d_gvals8; q.gdiag = plan->fused->d_gdiag;
-    q.x_rows = plan->n_cols; q.dy_rows = plan->n_rows; q.N = N;
-    q.nstrips = ft.q5.n; q.lddy = Fout; q.lddw = Fout; q.num_cu = plan->fused->num_cu;
-    q.cheb = beta_rest != 0.f;
-    q.accumulate = ft.nonq.n > 0;
-    const int rc = launch_cheb_qwgrad(q, stream);
-    if (rc != DSPH_OK) return rc;
-  }
-  return DSPH_OK;
+// The BFS-tile kernel's arguments as far as every mode shares them: the request, the tables and the route's tile list.
+// The mode adds its own: y / bias / act / weights (forward), planes_out, or dy and the slabs.
+static FusedArgs fused_args(const FusedRequest& rq, const Route& rt) {
+  const dsph_plan* plan = rq.plan;
+  const FusedTiles& ft = rt.ft;
+  const int C = (rq.Fin + FUSED_CH - 1) / FUSED_CH;
+  FusedArgs args{};  // (planes_out, dy, slabs, wfrag_bytes: none until the mode sets its own)
+  args.c_count = C;
+  args.prow_stride = plan->n_cols;
+  args.plane_stride = rq.N * plan->n_cols * (int64_t)rq.Fin;
+  args.x = rq.x;
+  args.bias = rq.bias;
+  args.y = rq.y;
+  args.wfrag = rq.ws;
+  args.tile_off = ft.d_tile_off;
+  args.ring_end = ft.d_ring_end;
+  args.ell_off = ft.d_ell_off;
+  args.region = ft.d_region;
+  args.lcols = ft.d_lcols;
+  args.lvals = ft.d_lvals;
+  args.x_rows = plan->n_cols;
+  args.y_rows = out_rows(plan);
+  args.N = rt.pack ? (int)((rq.N + rt.pack - 1) / rt.pack) : (int)rq.N;  // (packed: groups of P maps)
+  args.n_maps = (int)rq.N;
+  args.pack = rt.pack;
+  args.num_cu = plan->fused->num_cu;
+  args.pool = rq.pool ? rq.pool->type : 0;
+  args.ypool = rq.pool ? rq.pool->y : nullptr;
+  args.ypool_rows = plan->n_rows / 4;
+  args.Fin = rq.Fin;
+  args.Fout = rq.Fout;
+  args.ld = rq.ld;
+  args.K = rq.K;
+  args.tile_list = rt.bfs_tiles;
+  args.ntiles = rt.bfs_n;
+  args.nchunks = C;
+  args.act = rq.act;
+  args.alpha_rest = rq.alpha_rest;
+  args.beta_rest = rq.beta_rest;
+  args.dbg = dbg_bits();
+  return args;
 }
 
 // the instantiation of the BFS-tile kernel for plane rows pr and ELL width wt (cheb_fused_inst.hip)
@@ -658,278 +723,335 @@ static int launch_fused_variant(int pr, int wt, const FusedArgs& a, int nb, int 
   return DSPH_E_UNSUPPORTED;
 }
 
-static int launch_fused_common(const dsph_plan* plan, const float* x, const float* w, const float* bias,
-                               float* y, float* planes_out, int64_t N, int32_t Fin, int32_t Fout, int32_t K,
-                               int32_t act, int32_t precision, float alpha_rest, float beta_rest,
-                               void* workspace, size_t workspace_bytes, hipStream_t stream, const float* dy,
-                               float* dw, int32_t ld, int32_t part, int32_t Fin_w, int32_t only, bool keep_weights,
-                               const FusedPool* pool, const int32_t* wg_tiles, int wg_ntiles) {
-  // DSPH_PREC_F16X3 is the quad strips' arithmetic; every other kernel of the forward runs the six-term split (same accuracy)
-  const bool f16 = precision == DSPH_PREC_F16X3;
-  const int32_t strip_precision = precision;
-  if (f16) precision = DSPH_PREC_BF16X6;
-  if (ld <= 0) ld = Fout;
-  if (Fin_w <= 0) Fin_w = Fin;  // channels of w; smaller than Fin when x is a zero-padded copy  // row stride of w, bias-less y / dy / dw: the layer's Fout when this is one column block
-  const bool wgrad_mode = dy != nullptr;  // y then carries the slab workspace
-  const bool planes_mode = planes_out != nullptr || wgrad_mode;
-  if (!supported_impl(plan, Fin, Fout, K, planes_mode)) {
-    set_error("cheb_fused: plan/shape not supported");
+// the BFS-tile kernel on the route's tile list, in the forward (wfrag_bytes of weights in the LDS) or the planes mode
+static int launch_bfs_tiles(const FusedRequest& rq, const Route& rt, FusedArgs& args, int nb, size_t wfrag_bytes) {
+  if (args.ntiles == 0) return DSPH_OK;
+  args.wfrag_bytes = (int)wfrag_bytes;
+  const size_t lds = (size_t)2 * rt.pr * FUSED_CH * 4 + wfrag_bytes;
+  const int rc = stamps_begin(args, rq.stream);
+  if (rc != DSPH_OK) return rc;
+  return stamps_end(launch_fused_variant(rt.pr, rt.ft.width, args, nb, bfs_arithmetic(rq.precision), fused_grid(rq.plan, args.ntiles), lds,
+                                         rq.stream), rq.stream);
+}
+
+// The BFS half of a forward: the class-G tiles on the BFS-tile kernel; at K = 8, 32 -> 32 the rectangles first, on the quad strips.
+static int forward_bfs(const FusedRequest& rq, const Route& rt, const WeightImages& img) {
+  const dsph_plan* plan = rq.plan;
+  const int C = (rq.Fin + FUSED_CH - 1) / FUSED_CH;
+  const int NB = rt.pack ? 2 : (rq.Fout + 31) / 32;  // (packed: two column blocks whatever the layer's width)
+  if (fused_images_claim(plan, rq.ws, IMG_BFS)) {
+    hipLaunchKernelGGL(fused_wprep_kernel, dim3(rq.K * C * NB), dim3(256), 0, rq.stream, rq.w, rq.ws + img.bfs, (int)rq.Fin_w, (int)rq.Fout,
+                       (int)rq.K, C, NB, (int)bfs_arithmetic(rq.precision), (int)rq.ld, rt.pack);
+    DSPH_HIP(hipGetLastError());
+  }
+  if (rt.q8) {
+    QStrip8Launch q;
+    static_cast<LaunchBase&>(q) = launch_base(rq);
+    q.wimg = rq.ws + img.qstrip8;
+    q.strips = rt.ft.q8.d_strips; q.tab = rt.ft.q8.d_tab; q.prefix = rt.ft.q8.d_prefix; q.tape_rows = rt.ft.q8.tape_rows;
+    q.nstrips = rt.ft.q8.n; q.ld_w = rq.ld;
+    q.f16 = rq.precision == DSPH_PREC_F16X3;
+    q.f16_xexp = plan->opt.f16_xexp;
+    q.prep_weights = fused_images_claim(plan, rq.ws, IMG_Q8);
+    const int rc = launch_cheb_qstrip8(q, rq.stream);
+    if (rc != DSPH_OK) return rc;
+  }
+  FusedArgs args = fused_args(rq, rt);
+  return launch_bfs_tiles(rq, rt, args, NB, img.bfs_bytes);
+}
+
+// Forward of one 64-column block on the caller's stream: the structured half, then the BFS half.
+static int forward_block(const FusedRequest& rq, const FusedTiles* ft, size_t ws_bytes) {
+  const WeightImages img(rq.Fin, rq.Fout, rq.K);
+  const int rc = check_request(rq, ft, ws_bytes, img.total, nullptr);
+  if (rc != DSPH_OK) return rc;
+  const Route rt = make_route(rq.plan, *ft, rq, false);
+  if (rt.has_struct) {
+    const int rc_s = forward_structured(rq, rt, img);
+    if (rc_s != DSPH_OK) return rc_s;
+    if (!rt.has_bfs || dbg_only('s')) return DSPH_OK;
+  }
+  return forward_bfs(rq, rt, img);
+}
+
+// Whether the BFS half of a forward goes to the plan's side stream: worth its two event operations only when the structured
+// launches run for a while, two tile-maps per CU and more -- BASELINE configs[0], 168 tile-maps, is 13 us faster without it,
+// configs[1] 29 us faster with it.  Under a stream capture the fork and the join are edges of the graph and cost nothing at
+// replay: every forward with both kinds of tiles forks there, provided the side stream exists already -- dsph_plan_prepare made it.
+static bool fork_pays(const dsph_plan* plan, const FusedTiles& ft, int64_t N, int32_t part, hipStream_t stream) {
+  FusedPlan* fp = plan->fused;
+  if (!plan->opt.fork || !has_struct_tiles(ft) || ft.part.count(part) == 0) return false;
+  if (N * (int64_t)(ft.r.n + ft.t.tiles.n) >= 2 * (int64_t)fp->num_cu) return true;
+  if (!fp->side || stream == nullptr) return false;
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  return hipStreamIsCapturing(stream, &cs) == hipSuccess && cs == hipStreamCaptureStatusActive;
+}
+
+// One block of a forked forward (the halves write disjoint tiles): the BFS half on the side stream, forked behind whatever the
+// caller's stream holds so far and joined before this returns; the structured half on the caller's stream.  One route serves
+// both.  *ran = false: no side stream, nothing was launched.
+static int forward_block_forked(const FusedRequest& rq, const FusedTiles* ft, size_t ws_bytes, bool* ran) {
+  FusedPlan* fp = rq.plan->fused;
+  hipStream_t stream = rq.stream;
+  std::unique_lock<std::mutex> lock(fp->fork_mu);
+  *ran = side_stream_ready(rq.plan, fp, stream, true);
+  if (!*ran) return DSPH_OK;
+  DSPH_HIP(hipEventRecord(fp->ev_fork, stream));             // (nothing is on the side stream yet: a failure here or in the
+  DSPH_HIP(hipStreamWaitEvent(fp->side, fp->ev_fork, 0));    //  next line leaves nothing to join)
+  const WeightImages img(rq.Fin, rq.Fout, rq.K);
+  int rc_b = check_request(rq, ft, ws_bytes, img.total, nullptr), rc_s = rc_b;
+  hipError_t e_rec;
+  if (rc_b == DSPH_OK) {
+    const Route rt = make_route(rq.plan, *ft, rq, true);
+    FusedRequest side = rq;
+    side.stream = fp->side;
+    rc_b = forward_bfs(side, rt, img);
+    e_rec = hipEventRecord(fp->ev_join, fp->side);
+    rc_s = forward_structured(rq, rt, img);
+  } else {
+    e_rec = hipEventRecord(fp->ev_join, fp->side);
+  }
+  // the join happens whatever went wrong in between: the side stream never outlives the call.  (Without the join
+  // event the only way to join is to wait for the side stream on the host -- not while the caller is capturing, where
+  // a synchronisation would invalidate the capture: the error goes back instead, the capture is lost either way.)
+  hipError_t e_join = hipSuccess;
+  if (e_rec == hipSuccess) e_join = hipStreamWaitEvent(stream, fp->ev_join, 0);
+  else {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone) e_join = hipStreamSynchronize(fp->side);
+  }
+  if (rc_b != DSPH_OK || rc_s != DSPH_OK) fused_images_forget(rq.plan, rq.ws);
+  if (rc_b != DSPH_OK) return rc_b;
+  if (rc_s != DSPH_OK) return rc_s;
+  if (e_rec != hipSuccess) return hip_fail(e_rec, "hipEventRecord(join)");
+  if (e_join != hipSuccess) return hip_fail(e_join, "join of the side stream");
+  return DSPH_OK;
+}
+
+int launch_cheb_fused(const dsph_plan* plan, const float* x, const float* w, const float* bias,
+                      float* y, int64_t N, int32_t Fin, int32_t Fout, int32_t K, int32_t act,
+                      int32_t precision, float alpha_rest, float beta_rest, void* workspace,
+                      size_t workspace_bytes, hipStream_t stream, int32_t part, bool keep_weights, const FusedPool* pool) {
+  if (pool != nullptr && !(part == 0 && fused_pool_ok(plan, N, Fin, Fout, K, act) && pool->y != nullptr && (pool->type == 1 || pool->type == 2) &&
+                           ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(pool->y)) & 15) == 0)) {
+    set_error("cheb_fused: this plan / shape has no fused pooling (whole unsharded maps, no or ReLU activation, not the Clenshaw strips' shape)");
     return DSPH_E_UNSUPPORTED;
   }
-  const FusedTiles& ft = get_tiles(plan, K - 1, want_full(plan, Fin, planes_mode));
-  const size_t wb = planes_mode ? 0 : wfrag_bytes(Fin, Fout, K);
-  const size_t wb_all = planes_mode ? 0 : all_frag_bytes(Fin, Fout, K);
-  if (!planes_mode && (!workspace || workspace_bytes < wb_all)) {
-    set_error("cheb_fused: workspace %zu < %zu", workspace_bytes, wb_all);
+  const LayerWorkspace lw(plan, N, Fin, Fout, K);
+  if (!workspace || workspace_bytes < lw.total) {
+    set_error("cheb_fused: workspace %zu < %zu", workspace_bytes, lw.total);
     return DSPH_E_WORKSPACE;
   }
-  if ((reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(workspace) & 15) ||
-      (reinterpret_cast<uintptr_t>(planes_out) & 15) || (wgrad_mode && (reinterpret_cast<uintptr_t>(y) & 15))) {
-    set_error("cheb_fused: x, workspace and planes must be 16-byte aligned");
-    return DSPH_E_BADARG;
-  }
-  const int C = (Fin + FUSED_CH - 1) / FUSED_CH, NB = (Fout + 31) / 32;
-  // ---- class-R and class-T tiles: the structured-tile kernel (forward only), without and with per-tile tables ----------
-  if (!planes_mode && ft.r.n + ft.t.tiles.n > 0 && only != 2) {
-    StructLaunch sl;
-    sl.x = x; sl.w = w; sl.bias = bias; sl.y = y;
-    sl.wfrag = static_cast<unsigned char*>(workspace) + wb;
-    sl.gvals8 = plan->fused->d_gvals8;
-    sl.gdiag = plan->fused->d_gdiag;
-    sl.x_rows = plan->n_cols;
-    sl.y_rows = plan->levels.empty() ? plan->n_rows : plan->levels[0];
-    sl.N = N;
-    sl.Fin = Fin; sl.Fin_w = Fin_w; sl.Fout = Fout; sl.K = K; sl.act = act; sl.precision = precision; sl.ld = ld;
-    sl.num_cu = plan->fused->num_cu;
-    sl.cheb = beta_rest != 0.f;
-    bool struct_prep = true;  // the first structured launch of this call packs the fragments, if the block lacks them
-    sl.allow_pack = plan->opt.pack;
-    if (pool != nullptr) {
-      sl.pool = pool->type;
-      sl.ypool = pool->y;
-      sl.ypool_rows = plan->n_rows / 4;
-    }
-    // rectangles of interior class-R tiles: the strip kernel, when it has this shape; the class-R list shrinks to the rest
-    const bool strips = strips_apply(plan, ft, Fin, Fout, K, strip_precision, N, ld) && Fin_w == Fin && (reinterpret_cast<uintptr_t>(y) & 15) == 0;
-    if (strips && part != 2 && !dbg_only('b') && use_qstrips(plan, ft, Fin, Fout, K)) {
-      QStripLaunch qs;
-      qs.x = x; qs.w = w; qs.bias = bias; qs.y = y;
-      qs.wimg = static_cast<unsigned char*>(workspace) + wb + struct_wfrag_bytes(Fin, Fout, K) + strip_wimg_bytes(Fin, Fout, K) +
-                2 * istrip_wimg_bytes(K, DSPH_PREC_BF16X6);
-      qs.strips = ft.q5.d_strips;
-      qs.tab = ft.q5.d_tab;
-      qs.prefix = ft.q5.d_prefix;
-      qs.tape_rows = ft.q5.tape_rows;
-      qs.gvals8 = plan->fused->d_gvals8;
-      qs.gdiag = plan->fused->d_gdiag;
-      qs.x_rows = sl.x_rows; qs.y_rows = sl.y_rows; qs.N = N;
-      qs.nstrips = ft.q5.n; qs.Fin = Fin; qs.Fout = Fout; qs.act = act; qs.ld = ld;
-      qs.num_cu = plan->fused->num_cu;
-      qs.cheb = sl.cheb;
-      qs.f16 = f16;
-      qs.f16_xexp = plan->opt.f16_xexp;
-      qs.prep_weights = fused_images_claim(plan, workspace, IMG_QSTRIP);
-      const int rc = launch_cheb_qstrip(qs, stream);
-      if (rc != DSPH_OK) return rc;
-    } else if (strips && part != 2 && !dbg_only('b')) {
-      StripLaunch st;
-      st.x = x; st.w = w; st.bias = bias; st.y = y;
-      st.wimg = static_cast<unsigned char*>(workspace) + wb + struct_wfrag_bytes(Fin, Fout, K);
-      st.pairs = ft.d_pairs;
-      st.gvals8 = plan->fused->d_gvals8;
-      st.gdiag = plan->fused->d_gdiag;
-      st.x_rows = sl.x_rows; st.y_rows = sl.y_rows; st.N = N;
-      st.npairs = ft.n_pairs; st.Fin = Fin; st.Fout = Fout; st.K = K; st.act = act; st.precision = precision; st.ld = ld;
-      st.num_cu = plan->fused->num_cu;
-      st.cheb = sl.cheb;
-      st.generic = plan->opt.strip_generic;
-      st.prep_weights = fused_images_claim(plan, workspace, IMG_STRIP);
-      const int rc = launch_cheb_strip(st, stream);
-      if (rc != DSPH_OK) return rc;
-    }
-    const bool istrips = !strips && istrips_apply(plan, ft, Fin, K, Fout, ld) && (reinterpret_cast<uintptr_t>(y) & 15) == 0;
-    if (istrips && part != 2 && !dbg_only('b')) {
-      IStripLaunch is;
-      is.x = x; is.w = w; is.bias = bias; is.y = y;
-      is.wimg = static_cast<unsigned char*>(workspace) + wb + struct_wfrag_bytes(Fin, Fout, K) + strip_wimg_bytes(Fin, Fout, K);
-      is.pairs = ft.d_ipairs;
-      is.gvals8 = plan->fused->d_gvals8;
-      is.gdiag = plan->fused->d_gdiag;
-      is.x_rows = sl.x_rows; is.y_rows = sl.y_rows; is.N = N;
-      is.npairs = ft.n_ipairs; is.Fin = Fin; is.Fin_w = Fin_w; is.Fout = Fout; is.K = K; is.act = act; is.precision = precision; is.ld = ld;
-      is.num_cu = plan->fused->num_cu;
-      // (row segments for the items the kernel will deal: maps, or pairs of maps in the one-channel kernel's pair mode)
-      is.nseg = istrip_nseg(plan, ft, istrip_pairs(Fin_w, Fout) ? (N + 1) / 2 : N, K - 1, istrip_narrow(Fin_w));
-      is.cheb = sl.cheb;
-      is.prep_weights = fused_images_claim(plan, workspace, IMG_ISTRIP);
-      if (pool != nullptr) {
-        is.pool = pool->type;
-        is.ypool = pool->y;
-        is.ypool_rows = plan->n_rows / 4;
-      }
-      const int rc = launch_cheb_istrip(is, stream);
-      if (rc != DSPH_OK) return rc;
-    }
-    const bool stripped = strips || istrips;
-    const bool qrest = strips && use_qstrips(plan, ft, Fin, Fout, K);  // the quad strips took class-T tiles too: their own rest lists
-    const TileList& rl = qrest ? ft.qrrest : (stripped ? ft.rrest : ft.r);
-    if (rl.count(part) > 0 && !dbg_only('b')) {
-      sl.tiles = rl.ptr(part);
-      sl.tabrow = nullptr;
-      sl.tabvals = nullptr;
-      sl.ntiles = rl.count(part);
-      sl.prep_weights = struct_prep && fused_images_claim(plan, workspace, IMG_STRUCT);
-      struct_prep = false;
-      const int rc = launch_cheb_struct(sl, stream);
-      if (rc != DSPH_OK) return rc;
-    }
-    const TileTables& tt = qrest ? ft.qt : ft.t;
-    if (tt.tiles.count(part) > 0 && !dbg_only('b')) {
-      sl.tiles = tt.tiles.ptr(part);
-      sl.tabrow = tt.rows(part);
-      sl.tabvals = tt.vals(part);
-      sl.ntiles = tt.tiles.count(part);
-      sl.prep_weights = struct_prep && fused_images_claim(plan, workspace, IMG_STRUCT);
-      struct_prep = false;
-      const int rc = launch_cheb_struct(sl, stream);
-      if (rc != DSPH_OK) return rc;
-    }
-    if (ft.part.count(part) == 0 || dbg_only('s')) return DSPH_OK;
-  }
-  if (only == 1) return DSPH_OK;
-  // the BFS-tile kernel has two contraction arithmetics; the six-term split of the structured kernel is fp32-equivalent
-  if (precision == DSPH_PREC_BF16X6) precision = DSPH_PREC_FP32;
-  // four maps per item where the layer has at most four input channels and 16 output columns (FusedArgs::pack)
-  const int pack = (plan->opt.pack && !planes_mode && !wgrad_mode && N >= 2) ? bfs_packs(Fin, Fout) : 0;  // (a single map gains nothing from two column blocks)
-  const int NBb = pack ? 2 : NB;
-  if (!planes_mode && fused_images_claim(plan, workspace, IMG_BFS)) {
-    hipLaunchKernelGGL(fused_wprep_kernel, dim3(K * C * NBb), dim3(256), 0, stream, w,
-                       static_cast<unsigned char*>(workspace), (int)Fin_w, (int)Fout, (int)K, C, NBb,
-                       (int)precision, (int)ld, pack);
-    DSPH_HIP(hipGetLastError());
-  }
-
-  // K = 8, 32 -> 32: the rectangles of depth-7 regular tiles on the quad strips, the rest of the tiles below
-  const bool q8 = !planes_mode && part != 2 && pool == nullptr && only == 0 && Fin_w == Fin && beta_rest != 0.f &&
-                  (act == DSPH_ACT_NONE || act == DSPH_ACT_RELU) && (reinterpret_cast<uintptr_t>(y) & 15) == 0 &&
-                  q8_applies(plan, ft, Fin, Fout, K, strip_precision, N, ld);
-  if (q8) {
-    QStrip8Launch q;
-    q.x = x; q.w = w; q.bias = bias; q.y = y;
-    q.wimg = static_cast<unsigned char*>(workspace) + all_frag_bytes(Fin, Fout, K) - qstrip8_wimg_bytes();
-    q.strips = ft.q8.d_strips; q.tab = ft.q8.d_tab; q.prefix = ft.q8.d_prefix; q.tape_rows = ft.q8.tape_rows;
-    q.gvals8 = plan->fused->d_gvals8; q.gdiag = plan->fused->d_gdiag;
-    q.x_rows = plan->n_cols; q.y_rows = plan->levels.empty() ? plan->n_rows : plan->levels[0]; q.N = N;
-    q.nstrips = ft.q8.n; q.act = act; q.ld = ld; q.ld_w = ld; q.num_cu = plan->fused->num_cu;
-    q.f16 = f16;
-    q.f16_xexp = plan->opt.f16_xexp;
-    q.prep_weights = fused_images_claim(plan, workspace, IMG_Q8);
-    const int rc = launch_cheb_qstrip8(q, stream);
+  unsigned char* ws = static_cast<unsigned char*>(workspace);
+  // Fin not a multiple of four: a zero-padded copy of x behind the weight images in the workspace (with a two-part
+  // launch both parts copy: the halo rows arrive between them)
+  const int32_t Fin_w = Fin;
+  if (Fin != pad4(Fin)) {
+    float* xp = reinterpret_cast<float*>(ws + lw.padded_x);
+    const int rc = launch_fused_pad(x, xp, N * plan->n_cols, Fin, pad4(Fin), stream);
     if (rc != DSPH_OK) return rc;
-    if (ft.q8rest.count(part) == 0) return DSPH_OK;
+    x = xp;
+    Fin = pad4(Fin);
   }
+  // the tables of the call, looked up once (nullptr: not a shape of the fused kernels -- the first block says so)
+  const FusedTiles* ft = tiles_for(plan, Fin, Fout, K, false);
+  // The structured-tile kernel fuses bias and ReLU; with any other activation both fused kernels write the pre-activation
+  // and one elementwise pass finishes y (only when class-R tiles exist: the BFS-tile kernel knows every activation).
+  // (two-part launches: each part writes the pre-activation of its tiles and then finishes exactly those tiles' rows)
+  const bool defer_act = act != DSPH_ACT_NONE && act != DSPH_ACT_RELU && ft && has_struct_tiles(*ft);
+  // structured launches and the BFS-tile launch write disjoint tiles: when a forward has both, the latter goes to the plan's
+  // side stream (FusedPlan::side)
+  const bool fork = ft && fork_pays(plan, *ft, N, part, stream);
+  // more than 64 output columns: one launch per 64-column block (the recurrence is repeated; still one pass
+  // over x per block instead of the unfused path's K planes through HBM)
+  FusedRequest rq;
+  rq.plan = plan; rq.x = x; rq.stream = stream;
+  rq.N = N; rq.Fin = Fin; rq.Fin_w = Fin_w; rq.ld = Fout; rq.K = K; rq.precision = precision; rq.part = part;
+  rq.act = defer_act ? DSPH_ACT_NONE : act;
+  rq.alpha_rest = alpha_rest; rq.beta_rest = beta_rest;
+  for (int32_t cb = 0; cb < Fout; cb += 64) {
+    const FusedPool pool_blk{pool ? pool->y + cb : nullptr, pool ? pool->type : 0};  // (this block's columns of the pooled map)
+    rq.w = w + cb; rq.bias = bias ? bias + cb : nullptr; rq.y = y + cb;
+    rq.Fout = std::min<int32_t>(64, Fout - cb);
+    rq.ws = ws + (size_t)(cb / 64) * lw.block;
+    rq.pool = pool ? &pool_blk : nullptr;
+    fused_images_begin(plan, rq.ws, fused_images_key(Fin, Fin_w, rq.Fout, K, Fout, precision, beta_rest != 0.f, N >= 2, plan->opt.pack),
+                       keep_weights);
+    bool forked = false;
+    int rc = fork ? forward_block_forked(rq, ft, lw.block, &forked) : DSPH_OK;
+    if (!forked) {
+      rc = forward_block(rq, ft, lw.block);
+      if (rc != DSPH_OK) fused_images_forget(plan, rq.ws);
+    }
+    if (rc != DSPH_OK) return rc;
+  }
+  if (pool != nullptr) {
+    return DSPH_OK;  // (every kernel has stored its tiles pooled; y, the scratch of the C ABI, stays untouched)
+  }
+  if (defer_act) {
+    if (part == 0) return launch_struct_act(y, N * out_rows(plan), Fout, Fout, act, stream);
+    // a part finishes the rows of its own tiles only: INTERIOR and BOUNDARY can be issued in any order, repeated, or alone
+    return launch_struct_act_tiles(y, ft->all.ptr(part), ft->all.count(part), N, out_rows(plan), Fout, Fout, act, stream);
+  }
+  return DSPH_OK;
+}
 
-  FusedArgs args;
+// Planes mode of the same kernel: T_1 .. T_{K-1} of x, each (N, n_cols, Fin), valid on the plan's output rows.
+bool fused_planes_supported(const dsph_plan* plan, int32_t Fin, int32_t K) { return tiles_for(plan, Fin, 1, K, true) != nullptr; }
+
+int launch_cheb_fused_planes(const dsph_plan* plan, const float* x, float* planes_out, int64_t N, int32_t Fin,
+                             int32_t K, float alpha_rest, float beta_rest, hipStream_t stream) {
+  FusedRequest rq;
+  rq.mode = Mode::planes;
+  rq.plan = plan; rq.x = x; rq.stream = stream;
+  rq.N = N; rq.Fin = rq.Fin_w = Fin; rq.Fout = rq.ld = 1; rq.K = K; rq.precision = DSPH_PREC_FP32;
+  rq.alpha_rest = alpha_rest; rq.beta_rest = beta_rest;
+  const FusedTiles* ft = tiles_for(plan, Fin, 1, K, true);
+  const int rc = check_request(rq, ft, 0, 0, planes_out);
+  if (rc != DSPH_OK) return rc;
+  const Route rt = make_route(plan, *ft, rq, false);
+  FusedArgs args = fused_args(rq, rt);
   args.planes_out = planes_out;
-  args.dy = dy;
-  args.slabs = wgrad_mode ? y : nullptr;
-  args.c_begin = 0;
-  args.c_count = C;
-  args.prow_stride = plan->n_cols;
-  args.plane_stride = N * plan->n_cols * (int64_t)Fin;
-  args.x = x;
-  args.bias = bias;
-  args.y = y;
-  args.wfrag = static_cast<const unsigned char*>(workspace);
-  args.tile_off = ft.d_tile_off;
-  args.ring_end = ft.d_ring_end;
-  args.ell_off = ft.d_ell_off;
-  args.region = ft.d_region;
-  args.lcols = ft.d_lcols;
-  args.lvals = ft.d_lvals;
-  args.x_rows = plan->n_cols;
-  args.y_rows = plan->levels.empty() ? plan->n_rows : plan->levels[0];
-  args.N = pack ? (int)((N + pack - 1) / pack) : (int)N;  // (packed: groups of P maps)
-  args.n_maps = (int)N;
-  args.pack = pack;
-  args.num_cu = plan->fused->num_cu;
-  args.pool = pool ? pool->type : 0;
-  args.ypool = pool ? pool->y : nullptr;
-  args.ypool_rows = plan->n_rows / 4;
-  args.Fin = Fin;
-  args.Fout = Fout;
-  args.ld = ld;
-  args.K = K;
-  // part: 0 all tiles, 1 interior tiles (no row of another rank in their region), 2 boundary tiles
-  // the BFS-tile kernel handles the tiles of ft.part (every tile of a full table, the class-G ones otherwise)
-  args.tile_list = part == 0 && ft.part.n == ft.ntiles ? nullptr : ft.part.ptr(part);
-  args.ntiles = ft.part.count(part);
-  if (q8) {  // (part 0: every tile the strips leave; part 1: the interior ones of them -- the boundary tiles are never the strips')
-    args.tile_list = ft.q8rest.ptr(part);
-    args.ntiles = ft.q8rest.count(part);
-  }
-  if (wgrad_mode && wg_ntiles >= 0) {  // (the strips' pixels go to cheb_qwgrad.hip: launch_cheb_fused_qwgrad)
-    args.tile_list = wg_tiles;
-    args.ntiles = wg_ntiles;
-  }
-  if (args.ntiles == 0) return DSPH_OK;
-  args.nchunks = C;
-  args.act = act;
-  args.alpha_rest = alpha_rest;
-  args.beta_rest = beta_rest;
-  args.wfrag_bytes = (int)wb;
-#ifdef DSPH_ABLATE  // diagnostic build only (make ABLATE=1): the shipped library never skips work
-  const char* dbg = getenv("DSPH_FUSED_DEBUG");
-  args.dbg = dbg ? atoi(dbg) : 0;
-#else
-  args.dbg = 0;
-#endif
+  return launch_bfs_tiles(rq, rt, args, 1, 0);
+}
+
+// ---- weight-gradient mode ------------------------------------------------------------------------------
+
+// slices per launch: as many accumulator tiles (one per slice and order, 8 KiB each) as fit the LDS next to the planes
+static int wgrad_slices_per_launch(const FusedTiles& ft, int32_t K) {
   const int pr = plane_rows_for(ft.rmax, ft.emax, ft.width);
-  const size_t lds = (size_t)2 * pr * FUSED_CH * 4 + wb;
-  const int grid = (wgrad_mode && wg_ntiles < 0) ? fused_grid(plan, ft) : fused_grid(plan, ft, args.ntiles);
-  if (wgrad_mode) {
-    // as many slices per launch as fit the wave's WG_TILES accumulator tiles; every launch runs the
-    // recurrence for its own slices only, so the split costs nothing but a second read of dy
-    const int per = wgrad_slices_per_launch(plan, K);
-    for (int c0 = 0; c0 < C; c0 += per) {
-      FusedArgs la = args;
-      la.c_begin = c0;
-      la.c_count = std::min(per, C - c0);
-      const int rc = launch_fused_variant(pr, ft.width, la, NB, precision, grid, lds, stream);
+  if (pr == 0) return 0;
+  const long freeb = (long)LDS_BYTES - 2L * pr * FUSED_CH * 4;
+  return (int)(freeb / ((long)K * WG_TILE_BYTES));
+}
+
+// the full tables a weight gradient of this shape runs on; nullptr: not on the fused kernel
+static const FusedTiles* wgrad_tiles_for(const dsph_plan* plan, int32_t Fin, int32_t Fout, int32_t K) {
+  const FusedTiles* ft = tiles_for(plan, Fin, Fout, K, true);
+  return ft && wgrad_slices_per_launch(*ft, K) >= 1 ? ft : nullptr;
+}
+bool fused_wgrad_supported(const dsph_plan* plan, int32_t Fin, int32_t Fout, int32_t K) {
+  return wgrad_tiles_for(plan, Fin, Fout, K) != nullptr;
+}
+
+static size_t wgrad_slab_bytes(const dsph_plan* plan, const FusedTiles& ft, int32_t Fin, int32_t K) {
+  const int C = (Fin + FUSED_CH - 1) / FUSED_CH;
+  // (a slab per workgroup and pixel half; a small map's batch is split over up to num_cu workgroups in all: fused_wgrad_gy)
+  return (size_t)2 * std::max(fused_grid(plan, ft.ntiles), plan->fused->num_cu) * C * K * 16 * 64 * sizeof(float);
+}
+size_t fused_wgrad_workspace_bytes(const dsph_plan* plan, int32_t Fin, int32_t Fout, int32_t K) {
+  const FusedTiles* ft = wgrad_tiles_for(plan, Fin, Fout, K);
+  return ft ? wgrad_slab_bytes(plan, *ft, Fin, K) : 0;
+}
+
+
+// Weight gradient of one 64-column block on the BFS-tile kernel: per-workgroup partial sums into the slabs, then the reduction
+// into dw.  rq.only_tiles: the kernel runs on these tiles instead of every tile of the plan (the quad-strip gradient has the others).
+static int wgrad_block(const FusedRequest& rq, const FusedTiles* ft, const float* dy, float* dw, float* slabs) {
+  const int rc0 = check_request(rq, ft, 0, 0, slabs);
+  if (rc0 != DSPH_OK) return rc0;
+  const Route rt = make_route(rq.plan, *ft, rq, false);
+  FusedArgs args = fused_args(rq, rt);
+  args.dy = dy;
+  args.slabs = slabs;
+  args.y = slabs;  // (nothing is stored through it in this mode)
+  if (args.ntiles == 0) return DSPH_OK;
+  const int C = args.nchunks, NB = (rq.Fout + 31) / 32, prec = bfs_arithmetic(rq.precision);
+  const size_t lds = (size_t)2 * rt.pr * FUSED_CH * 4;
+  const int grid = fused_grid(rq.plan, rq.only_tiles ? args.ntiles : ft->ntiles);
+  // as many slices per launch as fit the wave's WG_TILES accumulator tiles; every launch runs the
+  // recurrence for its own slices only, so the split costs nothing but a second read of dy
+  const int per = wgrad_slices_per_launch(*ft, rq.K);
+  for (int c0 = 0; c0 < C; c0 += per) {
+    FusedArgs la = args;
+    la.c_begin = c0;
+    la.c_count = std::min(per, C - c0);
+    const int rc = launch_fused_variant(rt.pr, ft->width, la, NB, prec, grid, lds, rq.stream);
+    if (rc != DSPH_OK) return rc;
+  }
+  // (Fin_w < Fin: x is a zero-padded copy, only the rows of the real channels exist in dw)
+  const int total = rq.Fin_w * rq.K * rq.Fout;
+  hipLaunchKernelGGL(fused_wgrad_reduce_kernel, dim3((total + 15) / 16), dim3(256), 0, rq.stream, slabs, dw,
+                     2 * grid * fused_wgrad_gy(args.N, grid, args.num_cu), (int)rq.Fin_w, (int)rq.Fout, (int)rq.K, C, (int)rq.ld,
+                     prec == DSPH_PREC_BF16X3 ? grid : 0);
+  DSPH_HIP(hipGetLastError());
+  return DSPH_OK;
+}
+
+int launch_cheb_fused_wgrad(const dsph_plan* plan, const float* x, const float* dy, float* dw, int64_t N,
+                            int32_t Fin, int32_t Fout, int32_t K, int32_t precision, float alpha_rest, float beta_rest,
+                            void* workspace, size_t workspace_bytes, hipStream_t stream, int32_t Fin_w) {
+  const FusedTiles* ft = wgrad_tiles_for(plan, Fin, Fout, K);
+  if (!ft) {
+    set_error("cheb_fused_wgrad: plan/shape not supported");
+    return DSPH_E_UNSUPPORTED;
+  }
+  const size_t need = wgrad_slab_bytes(plan, *ft, Fin, K);
+  if (!workspace || workspace_bytes < need) {
+    set_error("cheb_fused_wgrad: workspace %zu < %zu", workspace_bytes, need);
+    return DSPH_E_WORKSPACE;
+  }
+  FusedRequest rq;
+  rq.mode = Mode::wgrad;
+  rq.plan = plan; rq.x = x; rq.stream = stream;
+  rq.N = N; rq.Fin = Fin; rq.Fin_w = Fin_w <= 0 ? Fin : Fin_w; rq.ld = Fout; rq.K = K; rq.precision = precision;
+  rq.alpha_rest = alpha_rest; rq.beta_rest = beta_rest;
+  for (int32_t cb = 0; cb < Fout; cb += 64) {
+    rq.Fout = std::min<int32_t>(64, Fout - cb);
+    const int rc = wgrad_block(rq, ft, dy + cb, dw + cb, static_cast<float*>(workspace));
+    if (rc != DSPH_OK) return rc;
+  }
+  return DSPH_OK;
+}
+
+// ---- quad-strip weight gradient (cheb_qwgrad.hip) -----------------------------------------------------------------------
+
+// The quad-strip weight gradient takes the strips' pixels of a K = 5, 64 -> 64 j layer in the three-term bf16 arithmetic when
+// the forward of that shape would run on the quad strips (same tables, same route: that of an unpadded, aligned, whole-map
+// forward of one 64-column block) and L~ is symmetric; the BFS-tile kernel's weight-gradient mode takes the tiles the strips
+// leave over.
+bool fused_qwgrad_applies(const dsph_plan* plan, int64_t N, int32_t Fin, int32_t Fout, int32_t K, int32_t precision) {
+  if (precision != DSPH_PREC_BF16X3 || !qwgrad_shape_ok(Fin, 64, K) || Fout % 64 != 0) return false;
+  if (!plan->fused || plan->fused->wide || plan->n_rows != plan->n_cols || !plan->levels.empty()) return false;
+  if (!fused_wgrad_supported(plan, Fin, Fout, K)) return false;
+  const FusedTiles& ft = get_tiles(plan, K - 1, false);
+  FusedRequest q;
+  q.N = N; q.Fin = q.Fin_w = Fin; q.Fout = 64; q.ld = Fout; q.K = K; q.precision = DSPH_PREC_BF16X3;
+  if (!ft.ok || make_route(plan, ft, q, false).strips != Strips::quad) return false;
+  return fused_symmetric(plan);
+}
+
+size_t fused_qwgrad_workspace_bytes(const dsph_plan* plan) { return qwgrad_slab_bytes(plan->fused ? plan->fused->num_cu : 256); }
+
+// workspace: [the BFS-tile kernel's slabs (fused_wgrad_workspace_bytes, 256-aligned) | the quad strips' slabs]
+int launch_cheb_fused_qwgrad(const dsph_plan* plan, const float* x, const float* dy, float* dw, int64_t N, int32_t Fin, int32_t Fout,
+                             int32_t K, float alpha_rest, float beta_rest, void* workspace, size_t bfs_slab_bytes, hipStream_t stream) {
+  const FusedTiles& ft = get_tiles(plan, K - 1, false);
+  const FusedTiles* full = ft.nonq.n > 0 ? tiles_for(plan, Fin, 64, K, true) : nullptr;  // (the BFS-tile kernel's own tables)
+  FusedRequest rq;  // (of the BFS-tile kernel's share)
+  rq.mode = Mode::wgrad;
+  rq.plan = plan; rq.x = x; rq.stream = stream;
+  rq.N = N; rq.Fin = rq.Fin_w = Fin; rq.Fout = 64; rq.ld = Fout; rq.K = K; rq.precision = DSPH_PREC_BF16X3;
+  rq.alpha_rest = alpha_rest; rq.beta_rest = beta_rest;
+  rq.only_tiles = &ft.nonq;
+  for (int32_t cb = 0; cb < Fout; cb += 64) {
+    if (ft.nonq.n > 0) {
+      const int rc = wgrad_block(rq, full, dy + cb, dw + cb, static_cast<float*>(workspace));
       if (rc != DSPH_OK) return rc;
     }
-    // (Fin_w < Fin: x is a zero-padded copy, only the rows of the real channels exist in dw)
-    const int total = Fin_w * K * Fout;
-    hipLaunchKernelGGL(fused_wgrad_reduce_kernel, dim3((total + 15) / 16), dim3(256), 0, stream, args.slabs, dw,
-                       2 * grid * fused_wgrad_gy(args.N, grid, args.num_cu), (int)Fin_w, (int)Fout, (int)K, C, (int)ld,
-                       precision == DSPH_PREC_BF16X3 ? grid : 0);
-    DSPH_HIP(hipGetLastError());
-    return DSPH_OK;
+    QWgradLaunch q;
+    q.x = x; q.dy = dy + cb; q.dw = dw + cb;
+    q.slabs = reinterpret_cast<float*>(static_cast<char*>(workspace) + bfs_slab_bytes);
+    q.strips = ft.q5.d_strips; q.prefix = ft.q5.d_prefix; q.tape_rows = ft.q5.tape_rows; q.tab = ft.q5.d_tab;
+    q.gvals8 = plan->fused->d_gvals8; q.gdiag = plan->fused->d_gdiag;
+    q.x_rows = plan->n_cols; q.dy_rows = plan->n_rows; q.N = N;
+    q.nstrips = ft.q5.n; q.lddy = Fout; q.lddw = Fout; q.num_cu = plan->fused->num_cu;
+    q.cheb = beta_rest != 0.f;
+    q.accumulate = ft.nonq.n > 0;
+    const int rc = launch_cheb_qwgrad(q, stream);
+    if (rc != DSPH_OK) return rc;
   }
-#ifdef DSPH_STAMPS
-  static unsigned long long* d_stamps = nullptr;
-  constexpr size_t NST = 8 * 8 * 32;
-  if (!d_stamps) DSPH_HIP(hipMalloc(&d_stamps, NST * 8));
-  DSPH_HIP(hipMemsetAsync(d_stamps, 0, NST * 8, stream));
-  args.stamps = d_stamps;
-  auto dump_stamps = [&](int rc) {
-    if (rc != DSPH_OK || !getenv("DSPH_STAMPS_DUMP")) return rc;
-    std::vector<unsigned long long> h(NST);
-    if (hipStreamSynchronize(stream) != hipSuccess) return rc;
-    if (hipMemcpy(h.data(), d_stamps, NST * 8, hipMemcpyDeviceToHost) != hipSuccess) return rc;
-    for (int w = 0; w < 8; ++w)
-      for (int it = 0; it < 8; ++it) {
-        fprintf(stderr, "STAMP wave %d item %d:", w, it + 4);
-        const unsigned long long* r = &h[((size_t)w * 8 + it) * 32];
-        for (int i = 1; i < 32; ++i) fprintf(stderr, " %lld", r[i] && r[i - 1] ? (long long)(r[i] - r[i - 1]) : -1LL);
-        fprintf(stderr, " | t0 %llu\n", r[0]);
-      }
-    return rc;
-  };
-  return dump_stamps(launch_fused_variant(pr, ft.width, args, NBb, precision, grid, lds, stream));
-#else
-  return launch_fused_variant(pr, ft.width, args, NBb, precision, grid, lds, stream);
-#endif
+  return DSPH_OK;
 }
 
 }  // namespace dsph

@@ -41,7 +41,7 @@ bool split_shape(int32_t Fin, int32_t Fout, int32_t K, SplitShape* s) {
     s->Kl[l] = k;
   }
   s->L = l;
-  s->Cz = (Fin + Fout + 3) & ~3;
+  s->Cz = pad4(Fin + Fout);
   return true;
 }
 

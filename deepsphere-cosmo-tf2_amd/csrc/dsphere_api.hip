@@ -33,7 +33,11 @@ static int64_t step_rows(const dsph_plan* p, int K, int k) {
   return p->levels[lvl < last ? lvl : last];
 }
 
-static int64_t out_rows(const dsph_plan* p) { return p->levels.empty() ? p->n_rows : p->levels[0]; }
+// coefficients of step k >= 2:  T_k = alpha * L~ T_{k-1} - beta * T_{k-2}
+struct Recurrence { float alpha_rest, beta_rest; };
+static Recurrence recurrence_of(int32_t basis) {
+  return basis == DSPH_BASIS_CHEBYSHEV ? Recurrence{2.f, 1.f} : Recurrence{1.f, 0.f};
+}
 
 }  // namespace dsph
 
@@ -223,6 +227,15 @@ int dsph_plan_prepare(dsph_plan* p, int32_t K, int32_t Fin, int32_t flags) { ret
 // A plan with halo columns and no shrinking schedule cannot run more than one recurrence step by itself: step 2
 // would gather halo entries of T_1 that no step wrote (the fused kernels reject it; the unfused path must too).
 static bool needs_levels(const dsph_plan* p, int32_t K) { return p->n_cols > p->n_rows && K > 2 && p->levels.empty(); }
+// The two checks of a plan's shrinking schedule that every K-term entry point makes, under the entry point's own name
+static bool levels_ok(const dsph_plan* p, int32_t K, const char* who) {
+  if (!p->levels.empty() && (int)p->levels.size() < K - 1) {
+    set_error("%s: plan has %d levels, K = %d needs %d", who, (int)p->levels.size(), K, K - 1);
+    return false;
+  }
+  if (needs_levels(p, K)) set_error("%s: the plan has halo columns and no levels: K = %d is not computable", who, K);
+  return !needs_levels(p, K);
+}
 
 int64_t dsph_plan_rows(const dsph_plan* p) { return p ? p->n_rows : 0; }
 int64_t dsph_plan_cols(const dsph_plan* p) { return p ? p->n_cols : 0; }
@@ -300,9 +313,9 @@ int dsph_poly_forward_pool(const dsph_plan* p, const float* x, const float* w, c
   }
   DeviceGuard guard(p->device);
   const FusedPool fp{y_pooled, pool_type == DSPH_POOL_MAX ? 1 : 2};
-  return launch_cheb_fused(p, x, w, bias, y_scratch, N, Fin, Fout, K, act, precision, basis == DSPH_BASIS_CHEBYSHEV ? 2.f : 1.f,
-                           basis == DSPH_BASIS_CHEBYSHEV ? 1.f : 0.f, workspace, workspace_bytes, (hipStream_t)hip_stream,
-                           DSPH_PART_ALL, (flags & DSPH_FWD_KEEP_WEIGHTS) != 0, &fp);
+  const Recurrence rec = recurrence_of(basis);
+  return launch_cheb_fused(p, x, w, bias, y_scratch, N, Fin, Fout, K, act, precision, rec.alpha_rest, rec.beta_rest, workspace, workspace_bytes,
+                           (hipStream_t)hip_stream, DSPH_PART_ALL, (flags & DSPH_FWD_KEEP_WEIGHTS) != 0, &fp);
 }
 
 size_t dsph_workspace_bytes(const dsph_plan* p, int64_t N, int32_t Fin, int32_t Fout, int32_t K,
@@ -379,24 +392,19 @@ int dsph_poly_forward_ex(const dsph_plan* p, const float* x, const float* w, con
     set_error("poly_forward: unknown basis %d", basis);
     return DSPH_E_BADARG;
   }
-  // coefficients of step k >= 2:  T_k = alpha * L~ T_{k-1} - beta * T_{k-2}
-  const float alpha_rest = basis == DSPH_BASIS_CHEBYSHEV ? 2.f : 1.f;
-  const float beta_rest = basis == DSPH_BASIS_CHEBYSHEV ? 1.f : 0.f;
+  const auto [alpha_rest, beta_rest] = recurrence_of(basis);
   if (!p || !x || !w || !y || N < 0 || Fin <= 0 || Fout <= 0 || K <= 0) {
     set_error("cheb_forward: bad arguments (NULL pointer or non-positive size)");
     return DSPH_E_BADARG;
   }
   if (act < DSPH_ACT_NONE || act > DSPH_ACT_TANH) { set_error("cheb_forward: unknown activation %d", act); return DSPH_E_BADARG; }
   if (precision < DSPH_PREC_FP32 || precision > DSPH_PREC_F16X3) { set_error("cheb_forward: unknown precision %d", precision); return DSPH_E_BADARG; }
-  if (!p->levels.empty() && (int)p->levels.size() < K - 1) {
-    set_error("cheb_forward: plan has %d levels, K = %d needs %d", (int)p->levels.size(), K, K - 1);
-    return DSPH_E_BADARG;
-  }
-  if (needs_levels(p, K)) {
+  if (needs_levels(p, K)) {  // (said at more length than levels_ok does)
     set_error("cheb_forward: the plan has %lld halo columns and no levels (dsph_plan_set_levels): K = %d would read halo rows of T_1 that nobody writes",
               (long long)(p->n_cols - p->n_rows), K);
     return DSPH_E_BADARG;
   }
+  if (!levels_ok(p, K, "cheb_forward")) return DSPH_E_BADARG;
   if (N == 0) return DSPH_OK;
   if (use_split(p, Fin, Fout, K, algo, part)) {
     DeviceGuard guard(p->device);
@@ -452,17 +460,9 @@ int dsph_cheb_planes(const dsph_plan* p, const float* x, float* planes, int64_t 
     set_error("cheb_planes: bad arguments (NULL pointer or non-positive size)");
     return DSPH_E_BADARG;
   }
-  if (!p->levels.empty() && (int)p->levels.size() < K - 1) {
-    set_error("cheb_planes: plan has %d levels, K = %d needs %d", (int)p->levels.size(), K, K - 1);
-    return DSPH_E_BADARG;
-  }
-  if (needs_levels(p, K)) {
-    set_error("cheb_planes: the plan has halo columns and no levels: K = %d is not computable", K);
-    return DSPH_E_BADARG;
-  }
+  if (!levels_ok(p, K, "cheb_planes")) return DSPH_E_BADARG;
   if (N == 0 || K == 1) return DSPH_OK;
-  const float alpha_rest = basis == DSPH_BASIS_CHEBYSHEV ? 2.f : 1.f;
-  const float beta_rest = basis == DSPH_BASIS_CHEBYSHEV ? 1.f : 0.f;
+  const auto [alpha_rest, beta_rest] = recurrence_of(basis);
   hipStream_t stream = (hipStream_t)hip_stream;
   DeviceGuard guard(p->device);
   const bool can_fuse = fused_planes_supported(p, Fin, K);
@@ -497,7 +497,7 @@ size_t dsph_backward_weights_workspace_bytes(const dsph_plan* p, int64_t N, int3
   // (channel counts that are no multiple of four -- a first layer's single channel -- run the fused kernel on a zero-padded
   // copy of x behind the slabs: the split-over-pixels kernel of the unfused route moves two pixel rows per MFMA whatever the
   // channel count, 13.5 ms for the 5 x 16 numbers of a 1 -> 16 layer at nside 512)
-  const int32_t Fp = (Fin + 3) & ~3;
+  const int32_t Fp = pad4(Fin);
   if (algo != DSPH_ALGO_UNFUSED && fused_wgrad_supported(p, Fp, Fout, K))
     return align_up(fused_wgrad_workspace_bytes(p, Fp, Fout, K), 256) + (Fp != Fin ? (size_t)N * (size_t)p->n_cols * (size_t)Fp * 4 : 0) +
            (qwgrad_shape_ok(Fin, 64, K) && Fout % 64 == 0 ? align_up(fused_qwgrad_workspace_bytes(p), 256) : 0);  // (the quad strips' slabs)
@@ -521,19 +521,11 @@ int dsph_cheb_backward_weights(const dsph_plan* p, const float* x, const float* 
     set_error("backward_weights: bad arguments (NULL pointer or non-positive size)");
     return DSPH_E_BADARG;
   }
-  if (!p->levels.empty() && (int)p->levels.size() < K - 1) {
-    set_error("backward_weights: plan has %d levels, K = %d needs %d", (int)p->levels.size(), K, K - 1);
-    return DSPH_E_BADARG;
-  }
-  if (needs_levels(p, K)) {
-    set_error("backward_weights: the plan has halo columns and no levels: K = %d is not computable", K);
-    return DSPH_E_BADARG;
-  }
-  const float alpha_rest = basis == DSPH_BASIS_CHEBYSHEV ? 2.f : 1.f;
-  const float beta_rest = basis == DSPH_BASIS_CHEBYSHEV ? 1.f : 0.f;
+  if (!levels_ok(p, K, "backward_weights")) return DSPH_E_BADARG;
+  const auto [alpha_rest, beta_rest] = recurrence_of(basis);
   hipStream_t stream = (hipStream_t)hip_stream;
   DeviceGuard guard0(p->device);  // the tables behind fused_wgrad_supported live on the plan's device
-  const int32_t Fp = (Fin + 3) & ~3;
+  const int32_t Fp = pad4(Fin);
   const bool can_fuse = fused_wgrad_supported(p, Fp, Fout, K);
   if (algo == DSPH_ALGO_FUSED && !can_fuse) {
     set_error("backward_weights: fused kernel cannot run this plan/shape (Fin=%d Fout=%d K=%d)", Fin, Fout, K);

@@ -69,6 +69,12 @@ struct dsph_plan {
 
 namespace dsph {
 
+// rows of y: the first level of a shrinking schedule, every row of L~ without one
+inline int64_t out_rows(const dsph_plan* p) { return p->levels.empty() ? p->n_rows : p->levels[0]; }
+// The fused kernels load x in 16-byte pieces: channel counts that are not a multiple of four are zero-padded into the workspace
+// first (fused_pad_kernel), so the forward takes any Fin >= 1.  The first layer of every reference model has Fin = 1.
+inline int32_t pad4(int32_t Fin) { return (Fin + 3) & ~3; }
+
 // out[n,m,:] = alpha * sum_j vals[m,j] * in[n, cols[m,j], :] - beta * prev[n,m,:],  m < rows
 int launch_cheb_step(const dsph_plan* plan, const float* in, int64_t in_rows, const float* prev,
                      int64_t prev_rows, float* out, int64_t out_rows, int64_t N, int32_t F,
@@ -159,23 +165,31 @@ int launch_cheb_tstep(const TStepTables& tb, const float* in, const float* prev,
                       float beta, int num_cu, hipStream_t stream);
 int fused_num_cu(const dsph_plan* plan);
 
-// structured-tile kernel (cheb_struct.hip)
-struct StructLaunch {
+// What the strip and tile kernels of one forward share (cheb_fused.hip fills it once per call; every launch_cheb_* copies what its
+// kernel takes into the kernel's own argument struct)
+struct LaunchBase {
   const float* x; const float* w; const float* bias; float* y;
+  const float* gvals8; const float* gdiag;  // direction-ordered copy of L~ (FusedPlan)
+  int64_t x_rows, y_rows, N;
+  int32_t act, ld, num_cu;
+  bool cheb;
+  // conv + pool (the structured-tile and input-side strip kernels; the latter with one or two input channels only): the 2 x 2
+  // pooled output, ypool_rows (n_rows / 4) rows per map; y is not written
+  float* ypool = nullptr;
+  int64_t ypool_rows = 0;
+  int32_t pool = 0;          // 0 none, 1 max, 2 mean
+};
+
+// structured-tile kernel (cheb_struct.hip)
+struct StructLaunch : LaunchBase {
   unsigned char* wfrag;      // workspace: struct_wfrag_bytes()
   const int32_t* tiles;      // device list of class-R tiles
-  const float* gvals8; const float* gdiag;
-  int64_t x_rows, y_rows, N;
-  int32_t ntiles, Fin, Fout, K, act, precision, ld, num_cu;
+  int32_t ntiles, Fin, Fout, K, precision;
   int32_t Fin_w;             // channels of w (< Fin when x was zero-padded to a multiple of four channels)
-  bool cheb;
   const int32_t* tabrow = nullptr;  // class-T tiles: [ntiles][ST_CELLS] rows and [ntiles][ST_CELLS][ST_TABV] values
   const float* tabvals = nullptr;   // (null: class-R tiles, rows by Morton arithmetic, values from gvals8 / gdiag)
   bool prep_weights = true;         // pack the weight fragments first (false: an earlier launch of this forward did)
   bool allow_pack = true;           // DSPH_OPT_PACK of the plan
-  float* ypool = nullptr;           // pool != 0: the 2 x 2 pooled output (n_rows / 4 rows per map); y is not written
-  int64_t ypool_rows = 0;
-  int32_t pool = 0;                 // 0 none, 1 max, 2 mean
 };
 int struct_build_rows(const dsph_plan* plan, float** gvals8, float** gdiag, unsigned char** flag);
 // gdiag[rows[i]] <- vals[9 i], gvals8[rows[i]][d] <- vals[9 i + 1 + d] (host arrays; duplicates carry equal values): the rows of
@@ -193,14 +207,10 @@ int launch_residual_epilogue(float* y, const float* skip, int64_t n, float alpha
 
 // strip kernel (cheb_strip.hip): rectangles of class-R tiles, streamed in 32-column strips
 struct StripPair;
-struct StripLaunch {
-  const float* x; const float* w; const float* bias; float* y;
+struct StripLaunch : LaunchBase {
   unsigned char* wimg;       // workspace: strip_wimg_bytes()
   const StripPair* pairs;    // device list of strip pairs
-  const float* gvals8; const float* gdiag;
-  int64_t x_rows, y_rows, N;
-  int32_t npairs, Fin, Fout, K, act, precision, ld, num_cu;
-  bool cheb;
+  int32_t npairs, Fin, Fout, K, precision;
   bool prep_weights = true;
   bool generic = false;      // DSPH_OPT_STRIP_GENERIC: the compiler-scheduled template also at K = 5
 };
@@ -210,17 +220,13 @@ int launch_cheb_strip(const StripLaunch& s, hipStream_t stream);
 
 // quad-strip kernel (cheb_qstrip.hip, round 5): the same rectangles in 64-column strips, four pixels per lane
 struct QStrip;
-struct QStripLaunch {
-  const float* x; const float* w; const float* bias; float* y;
+struct QStripLaunch : LaunchBase {
   unsigned char* wimg;       // workspace: qstrip_wimg_bytes()
   const QStrip* strips;      // device list of strips (uncut along y: the kernel cuts the tape of their rows by workgroup)
   const int32_t* tab = nullptr;  // device: the rectangles' tables of tile bases (QStrip::tab, ::tws)
   const int32_t* prefix;     // device [nstrips + 1]: rows of the strips before each one
   int64_t tape_rows;         // prefix[nstrips]
-  const float* gvals8; const float* gdiag;
-  int64_t x_rows, y_rows, N;
-  int32_t nstrips, Fin, Fout, act, ld, num_cu;
-  bool cheb;
+  int32_t nstrips, Fin, Fout;
   bool f16 = false;          // DSPH_PREC_F16X3: the three-term split on f16 pairs instead of bf16 pairs
   int f16_xexp = 0;          // f16: x is split as x 2^f16_xexp, the store takes the factor out again (DSPH_OPT_F16_XEXP)
   bool prep_weights = true;
@@ -231,14 +237,11 @@ int64_t qstrip_split(int num_cu, int64_t tape_rows, int64_t N, int64_t mean_heig
 int launch_cheb_qstrip(const QStripLaunch& s, hipStream_t stream);
 
 // K = 8, 32 -> 32 quad strips (cheb_qstrip8.hip, round 6)
-struct QStrip8Launch {
-  const float* x; const float* w; const float* bias; float* y;
+struct QStrip8Launch : LaunchBase {  // (Chebyshev basis only: `cheb` is not read)
   unsigned char* wimg;       // workspace: qstrip8_wimg_bytes()
   const QStrip* strips; const int32_t* tab; const int32_t* prefix;
   int64_t tape_rows;
-  const float* gvals8; const float* gdiag;
-  int64_t x_rows, y_rows, N;
-  int32_t nstrips, act, ld, ld_w, num_cu;
+  int32_t nstrips, ld_w;
   bool f16 = false;          // DSPH_PREC_F16X3
   int f16_xexp = 0;
   bool prep_weights = true;
@@ -272,18 +275,11 @@ int launch_healpix_pool_backward(const float* x, const float* dy, float* dx, int
                                  hipStream_t stream);
 
 // input-side strip kernel (cheb_istrip.hip): layers with at most 16 input channels, one wave per strip
-struct IStripLaunch {
-  const float* x; const float* w; const float* bias; float* y;
+struct IStripLaunch : LaunchBase {
   unsigned char* wimg;       // workspace: istrip_wimg_bytes() per 32-column block
   const StripPair* pairs;    // device list; every pair is two single strips
-  const float* gvals8; const float* gdiag;
-  int64_t x_rows, y_rows, N;
-  int32_t npairs, Fin, Fin_w, Fout, K, act, precision, ld, num_cu;
+  int32_t npairs, Fin, Fin_w, Fout, K, precision;
   int32_t nseg = 1;          // row segments per strip (istrip_segments)
-  float* ypool = nullptr;    // pool != 0 (one or two input channels only): the 2 x 2 pooled output, ypool_rows rows per map; y is not written
-  int64_t ypool_rows = 0;
-  int32_t pool = 0;          // 0 none, 1 max, 2 mean
-  bool cheb;
   bool prep_weights = true;
 };
 int istrip_segments(const std::vector<int32_t>& heights, const std::vector<unsigned char>& second, int64_t N, int num_cu, int D,

@@ -6,7 +6,11 @@ HIP runtime, no GPU).  Run with the sanitizer runtime preloaded (tests/test_host
 
     LD_PRELOAD=$(hipcc -print-file-name=libclang_rt.asan-x86_64.so) ASAN_OPTIONS=detect_leaks=0 python3 tools/asan/run_plan_builders.py
 
-Prints one line per plan and "ASAN-DRIVER-OK" at the end; any sanitizer report aborts the process (non-zero exit).
+After the look-ups of a plan it calls the compute entry points (forward, pooled forward, planes, weight gradient) over every route
+of the fused launch path: the stub drops the launches, so what runs under the sanitizers is the routing, the workspace layout and
+the images bookkeeping.  DSPH_STUB_TRACE=<file> makes the stub record every launch, event record and wait in that file.
+
+Prints one line per plan and per call, and "ASAN-DRIVER-OK" at the end; any sanitizer report aborts the process (non-zero exit).
 numpy / scipy only: torch is not imported (its allocator and the preloaded sanitizer runtime do not mix)."""
 import ctypes
 import os
@@ -41,6 +45,13 @@ LIB.dsph_workspace_bytes.restype = ctypes.c_size_t
 LIB.dsph_backward_weights_workspace_bytes.argtypes = [vp, i64, i32, i32, i32, i32]
 LIB.dsph_backward_weights_workspace_bytes.restype = ctypes.c_size_t
 LIB.dsph_last_error.restype = ctypes.c_char_p
+sz = ctypes.c_size_t
+LIB.dsph_poly_forward_ex.argtypes = [vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, sz, vp]
+LIB.dsph_poly_forward_pool.argtypes = [vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, i32, i32, vp, sz, vp]
+LIB.dsph_cheb_planes.argtypes = [vp, vp, vp, i64, i32, i32, i32, i32, vp]
+LIB.dsph_cheb_backward_weights.argtypes = [vp, vp, vp, vp, i64, i32, i32, i32, i32, i32, i32, vp, sz, vp]
+LIB.dsph_stub_trace_note.argtypes = [ctypes.c_char_p]
+LIB.dsph_stub_trace_note.restype = None
 
 
 def ell_of(L, scale=0.75):
@@ -148,8 +159,135 @@ def shard_of(cols, vals, lo, hi, K):
     return np.ascontiguousarray(lc, np.int32), np.ascontiguousarray(lv, np.float32), ids.size, levels
 
 
+# ---- the launch path: the compute entry points on the stub runtime ---------------------------------------------------------------
+# Launches are dropped, so x, w, y are never read: one small aligned buffer stands for all of them.  The workspace is a real
+# allocation of exactly the size the library asks for.  Every call prints its return code and error text; with DSPH_STUB_TRACE
+# set, the stub appends what the call launched (kernel, grid, block, stream; fork and join) under the call's name.
+_DUMMY = np.zeros(1 << 12, np.uint8)
+BUF = (_DUMMY.ctypes.data + 15) & ~15
+OPT_STRIPS, OPT_STRUCT, OPT_TABLES, OPT_FORK, OPT_MINROWS, OPT_SPLIT, OPT_PACK, OPT_STRIP_FORM = 1, 2, 3, 4, 6, 8, 10, 11
+PREC = {0: "fp32", 1: "bf16x3", 2: "bf16x6", 3: "f16x3"}
+RELU, ELU, KEEP = 1, 2, 1
+
+
+class Workspace:
+    def __init__(self, nbytes):
+        self.raw = np.empty(nbytes + 16, np.uint8)
+        self.ptr = (self.raw.ctypes.data + 15) & ~15
+        self.nbytes = nbytes
+
+
+def report(name, rc):
+    print(f"{name}: rc {rc}" + (f" [{LIB.dsph_last_error().decode()}]" if rc else ""), flush=True)
+    return rc
+
+
+def forward(h, name, N, Fin, Fout, K, prec=1, act=0, basis=0, part=0, flags=0, bias=False, ws=None, short=0, x_off=0, y_off=0, pool=None):
+    """dsph_poly_forward_ex, or dsph_poly_forward_pool with pool = 0 (max) / 1 (mean); short: bytes withheld from the workspace;
+    x_off, y_off: bytes by which x / y miss their 16-byte boundary (x: an error; y: the strips fall back to the tile kernels)."""
+    need = LIB.dsph_workspace_bytes(h, N, Fin, Fout, K, prec, 0)
+    ws = ws or Workspace(need)
+    name = f"{name}: forward N {N} {Fin}->{Fout} K {K} {PREC[prec]} act {act} basis {basis} part {part} flags {flags} workspace {need}" + \
+           (f" pool {pool}" if pool is not None else "") + (f" short {short}" if short else "") + (f" x+{x_off}" if x_off else "") + \
+           (f" y+{y_off}" if y_off else "")
+    LIB.dsph_stub_trace_note(name.encode())
+    b = BUF if bias else None
+    if pool is None:
+        rc = LIB.dsph_poly_forward_ex(h, BUF + x_off, BUF, b, BUF + y_off, N, Fin, Fout, K, basis, act, prec, 0, part, flags, ws.ptr, ws.nbytes - short, None)
+    else:
+        rc = LIB.dsph_poly_forward_pool(h, BUF + x_off, BUF, b, BUF, BUF, N, Fin, Fout, K, basis, act, prec, pool, flags, ws.ptr, ws.nbytes - short, None)
+    report(name, rc)
+    return ws
+
+
+def planes(h, name, N, Fin, K):
+    name = f"{name}: planes N {N} Fin {Fin} K {K}"
+    LIB.dsph_stub_trace_note(name.encode())
+    report(name, LIB.dsph_cheb_planes(h, BUF, BUF, N, Fin, K, 0, 0, None))
+
+
+def wgrad(h, name, N, Fin, Fout, K, prec=1, short=0):
+    need = LIB.dsph_backward_weights_workspace_bytes(h, N, Fin, Fout, K, 0)
+    ws = Workspace(need)
+    name = f"{name}: weight gradient N {N} {Fin}->{Fout} K {K} {PREC[prec]} workspace {need}" + (f" short {short}" if short else "")
+    LIB.dsph_stub_trace_note(name.encode())
+    report(name, LIB.dsph_cheb_backward_weights(h, BUF, BUF, BUF, N, Fin, Fout, K, 0, prec, 0, ws.ptr, ws.nbytes - short, None))
+
+
+def grid_launches(cols, vals, nside):
+    """Every route of the launch path on the full-sphere grid: strips by cost rule / always / never in both forms, column
+    blocks, deferred activation, kept weight images, padded and packed narrow layers, pooling, the K = 8 strips, K > 5."""
+    for strips in (0, 1, 2):
+        for form in (0, 1):
+            name = f"launch grid nside {nside} strips {strips} form {form}"
+            h = plan_of(cols, vals, options={OPT_STRIPS: strips, OPT_STRIP_FORM: form})
+            for N in (1, 3, 16):
+                for prec in (1, 3):
+                    forward(h, name, N, 64, 64, 5, prec)
+                forward(h, name, N, 64, 96, 5)
+                forward(h, name, N, 64, 128, 5, bias=True, act=RELU)
+                forward(h, name, N, 64, 64, 5, act=ELU, bias=True)
+            forward(h, name, 3, 64, 64, 5, basis=1)
+            forward(h, name, 16, 64, 64, 5, y_off=4)
+            if form == 0:  # kept images: nothing packed by the second call, only the missing ones after strips <-> tiles
+                ws = forward(h, name + " keep", 16, 64, 64, 5, flags=KEEP)
+                forward(h, name + " keep", 16, 64, 64, 5, flags=KEEP, ws=ws)
+                forward(h, name + " keep", 1, 64, 64, 5, flags=KEEP, ws=ws)
+                wgrad(h, name, 16, 64, 64, 5)       # the quad-strip gradient + the rest on the BFS kernel, where the rule says so
+                wgrad(h, name, 1, 64, 64, 5, prec=0)
+            LIB.dsph_plan_destroy(h)
+    name = f"launch grid nside {nside}"
+    h = plan_of(cols, vals)
+    for Fin in (1, 2, 3, 16):
+        for Fout in (16, 32):
+            for K in (3, 5):
+                for prec in (0, 1, 2, 3):
+                    forward(h, name, 4, Fin, Fout, K, prec, act=RELU, bias=True)
+        forward(h, name, 1, Fin, 16, 5)
+        for pool in (0, 1):
+            forward(h, name, 4, Fin, 16, 5, act=RELU, pool=pool)
+    ws = forward(h, name + " keep", 4, 4, 16, 5, flags=KEEP)
+    forward(h, name + " keep", 1, 4, 16, 5, flags=KEEP, ws=ws)  # (a single map is not packed: other images)
+    forward(h, name, 4, 8, 32, 5)
+    wgrad(h, name, 4, 128, 64, 5)
+    wgrad(h, name, 4, 16, 32, 5)
+    wgrad(h, name, 4, 1, 16, 5)
+    planes(h, name, 2, 16, 5)
+    forward(h, name, 1, 64, 64, 5, short=1)
+    forward(h, name, 2, 1, 16, 5, short=1)
+    wgrad(h, name, 2, 64, 64, 5, short=1)
+    forward(h, name, 1, 64, 64, 5, x_off=4)
+    forward(h, name, 4, 4, 16, 5, y_off=4)
+    forward(h, name, 1, 64, 64, 5, act=ELU, pool=0)   # no fused pooling: the activation
+    if nside == 128:
+        for strips in (0, 2):
+            assert LIB.dsph_plan_set_option(h, OPT_STRIPS, strips) == 0
+            for N in (1, 16):
+                forward(h, name + f" strips {strips}", N, 32, 32, 8, act=RELU, bias=True)
+                forward(h, name + f" strips {strips}", N, 32, 32, 8, prec=3)
+            forward(h, name + f" strips {strips}", 2, 32, 32, 8, act=ELU)
+            forward(h, name + f" strips {strips}", 16, 32, 32, 8, y_off=4)
+    else:
+        forward(h, name, 2, 32, 32, 8)        # 7-ring BFS tables
+        forward(h, name, 2, 16, 32, 10)       # the 1168-row variant
+        forward(h, name, 2, 32, 32, 12)
+        assert LIB.dsph_plan_set_option(h, OPT_SPLIT, 1) == 0
+        forward(h, name + " split", 2, 16, 32, 10)  # the chain of passes
+        ws = forward(h, name + " split keep", 2, 16, 32, 10, flags=KEEP)
+        forward(h, name + " split keep", 2, 16, 32, 10, flags=KEEP, ws=ws)
+    LIB.dsph_plan_destroy(h)
+    if nside == 64:
+        for opt in (OPT_STRUCT, OPT_TABLES, OPT_FORK, OPT_PACK):
+            h = plan_of(cols, vals, options={opt: 0})
+            forward(h, f"launch grid nside {nside} option {opt}=0", 4, 64, 64, 5)
+            forward(h, f"launch grid nside {nside} option {opt}=0", 4, 4, 16, 5)
+            LIB.dsph_plan_destroy(h)
+        h = plan_of(cols, vals, options={OPT_STRIPS: 1})
+        forward(h, f"launch grid nside {nside} strips 1", 4, 64, 64, 5, act=RELU, pool=0)  # no fused pooling: the strips' shape
+        LIB.dsph_plan_destroy(h)
+
+
 def main():
-    OPT_STRIPS, OPT_STRUCT, OPT_TABLES, OPT_SPLIT, OPT_STRIP_FORM, OPT_MINROWS = 1, 2, 3, 8, 11, 6
     # full-sphere grid stencil: class R interiors (strips at 64 -> 64), class T face borders, class G corners
     for nside in (32, 64, 128):
         cols, vals = ell_of(healpix.healpix_laplacian(nside, mode="grid"))
@@ -173,6 +311,8 @@ def main():
         look(h, 5, 64, 64, f"grid nside {nside} release", flags=3)  # DSPH_PREPARE_RELEASE_HOST: further K fail cleanly
         assert LIB.dsph_plan_prepare_layer(h, 4, 64, 64, 0) in (0, -3)
         LIB.dsph_plan_destroy(h)
+        if nside >= 64:
+            grid_launches(cols, vals, nside)
     # partial sky: a cap padded to superpixels (ragged rectangles, compacted rows: class T rings around every superpixel)
     for nside, sup in ((64, 8), (128, 8), (64, 2)):
         idx = healpix.extend_indices(healpix.cap_indices(nside, fraction=1.0 / 3.0), nside, sup)
@@ -182,11 +322,20 @@ def main():
         if st[0]:
             assert check_strip_tables(h, 5, cols, vals, f"cap nside {nside} superpixels {sup}") == st[0]
         LIB.dsph_plan_destroy(h)
+        if nside == 64:
+            h = plan_of(cols, vals)
+            for N in (1, 16):
+                forward(h, f"launch cap superpixels {sup}", N, 64, 64, 5)
+            wgrad(h, f"launch cap superpixels {sup}", 16, 64, 64, 5)
+            LIB.dsph_plan_destroy(h)
     # the reference's graphs: k nearest neighbours (ELL width 11: BFS tiles; 23: the tiled step's depth-1 tables)
     for k in (8, 20):
         cols, vals = ell_of(healpix.healpix_laplacian(32, n_neighbors=k, mode="knn"))
         h = plan_of(cols, vals)
         look(h, 5, 16, 32, f"knn{k} nside 32 (width {cols.shape[1]})")
+        forward(h, f"launch knn{k}", 2, 16, 32, 5)  # (k = 20: no fused kernel, the tiled step)
+        if k == 8:
+            planes(h, f"launch knn{k}", 2, 16, 5)
         LIB.dsph_plan_destroy(h)
     # a shard: half the sphere with its (K-1)-ring halo as trailing columns and a shrinking schedule
     cols, vals = ell_of(healpix.healpix_laplacian(64, mode="grid"))
@@ -196,7 +345,20 @@ def main():
             lc, lv, n_cols, levels = shard_of(cols, vals, lo, hi, K)
             h = plan_of(lc, lv, n_cols=n_cols, levels=levels)
             look(h, K, 32, 32, f"shard rows [{lo}, {hi}) K {K}: {lc.shape[0]} rows, {n_cols} columns")
+            for part in (0, 1, 2):
+                for act in (RELU, ELU):
+                    forward(h, f"launch shard [{lo}, {hi})", 2, 32, 32, K, act=act, bias=True, part=part)
+            if K == 5:
+                planes(h, f"launch shard [{lo}, {hi})", 2, 32, K)
+                wgrad(h, f"launch shard [{lo}, {hi})", 2, 32, 32, K)
             LIB.dsph_plan_destroy(h)
+            if K == 5 and lo == 0:  # the schedule's errors: none at all, too short
+                for bad, what in ((None, "no levels"), (levels[:2], "two levels")):
+                    h = plan_of(lc, lv, n_cols=n_cols, levels=bad)
+                    forward(h, f"launch shard with {what}", 2, 32, 32, K)
+                    planes(h, f"launch shard with {what}", 2, 32, K)
+                    wgrad(h, f"launch shard with {what}", 2, 32, 32, K)
+                    LIB.dsph_plan_destroy(h)
     # a map whose last tile is incomplete, with strips: no rectangle may have that tile in its ring (the kernel reads rows of the
     # ring tiles past the halo)
     M = 12 * 64 * 64
