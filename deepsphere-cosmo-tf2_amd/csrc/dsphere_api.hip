@@ -3,6 +3,7 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <initializer_list>
 #include <new>
 
 #include "dsphere_common.h"
@@ -631,6 +632,62 @@ int dsph_residual_epilogue(float* y, const float* skip, int64_t n, float alpha, 
   if (act < DSPH_ACT_NONE || act > DSPH_ACT_TANH) { set_error("residual_epilogue: unknown activation %d", act); return DSPH_E_BADARG; }
   DeviceGuard guard(device);
   return launch_residual_epilogue(y, skip, n, alpha, act, act_before != 0, (hipStream_t)hip_stream);
+}
+
+// the shape limits of csrc/nbr_attention.hip, each named in its message
+static int nbr_attention_args_ok(const char* who, int64_t ld, int32_t width, int64_t N, int64_t M, int32_t heads, int32_t depth) {
+  if (N < 0 || M < 0) { set_error("%s: negative size (N %lld, M %lld)", who, (long long)N, (long long)M); return DSPH_E_BADARG; }
+  if (M > 0x7fffffffLL) { set_error("%s: M = %lld exceeds the int32 row indices of the neighbour table", who, (long long)M); return DSPH_E_BADARG; }
+  if (depth != 4 && depth != 8 && depth != 16 && depth != 32 && depth != 64) {
+    set_error("%s: depth %d per head is not one of 4, 8, 16, 32, 64", who, (int)depth);
+    return DSPH_E_BADARG;
+  }
+  if (heads < 1 || (int64_t)heads * depth > 256) {
+    set_error("%s: heads * depth = %d * %d must lie in [depth, 256] (one wave holds a row)", who, (int)heads, (int)depth);
+    return DSPH_E_BADARG;
+  }
+  if (width < 1) { set_error("%s: neighbour table width %d, must be at least 1", who, (int)width); return DSPH_E_BADARG; }
+  if (ld % 4 != 0 || ld < (int64_t)heads * depth) {
+    set_error("%s: row stride %lld must be a multiple of 4 floats and at least heads * depth = %d", who, (long long)ld, (int)(heads * depth));
+    return DSPH_E_BADARG;
+  }
+  return DSPH_OK;
+}
+
+static bool aligned16(std::initializer_list<const void*> ps) {
+  uintptr_t a = 0;
+  for (const void* p : ps) a |= reinterpret_cast<uintptr_t>(p);
+  return (a & 15) == 0;
+}
+
+int dsph_nbr_attention_forward(const float* q, const float* k, const float* v, int64_t ld, float* out, float* lse, const int32_t* nbr,
+                               int32_t width, int64_t N, int64_t M, int32_t heads, int32_t depth, int device, void* hip_stream) {
+  if (!q || !k || !v || !out || !nbr) { set_error("nbr_attention_forward: NULL pointer"); return DSPH_E_BADARG; }
+  const int rc = nbr_attention_args_ok("nbr_attention_forward", ld, width, N, M, heads, depth);
+  if (rc != DSPH_OK) return rc;
+  if (!aligned16({q, k, v, out})) { set_error("nbr_attention_forward: q, k, v and out must be 16-byte aligned"); return DSPH_E_BADARG; }
+  DeviceGuard guard(device);
+  return launch_nbr_attention_forward(q, k, v, ld, out, lse, nbr, width, N, M, heads, depth, (hipStream_t)hip_stream);
+}
+
+int dsph_nbr_attention_backward(const float* q, const float* k, const float* v, int64_t ld, const float* out, const float* lse,
+                                const float* dout, const int32_t* nbr, int32_t width, const int32_t* nbrT, int32_t widthT, float* delta,
+                                float* dq, float* dk, float* dv, int64_t ld_grad, int64_t N, int64_t M, int32_t heads, int32_t depth,
+                                int device, void* hip_stream) {
+  if (!q || !k || !v || !out || !lse || !dout || !nbr || !nbrT || !delta || !dq || !dk || !dv) {
+    set_error("nbr_attention_backward: NULL pointer");
+    return DSPH_E_BADARG;
+  }
+  int rc = nbr_attention_args_ok("nbr_attention_backward", ld, width, N, M, heads, depth);
+  if (rc == DSPH_OK) rc = nbr_attention_args_ok("nbr_attention_backward (gradients, transposed table)", ld_grad, widthT, N, M, heads, depth);
+  if (rc != DSPH_OK) return rc;
+  if (!aligned16({q, k, v, out, dout, dq, dk, dv})) {
+    set_error("nbr_attention_backward: q, k, v, out, dout, dq, dk and dv must be 16-byte aligned");
+    return DSPH_E_BADARG;
+  }
+  DeviceGuard guard(device);
+  return launch_nbr_attention_backward(q, k, v, ld, out, lse, dout, nbr, width, nbrT, widthT, delta, dq, dk, dv, ld_grad, N, M, heads,
+                                       depth, (hipStream_t)hip_stream);
 }
 
 }  // extern "C"

@@ -274,6 +274,14 @@ int launch_healpix_pool(const float* x, float* y, int64_t rows_out, int32_t F, i
 int launch_healpix_pool_backward(const float* x, const float* dy, float* dx, int64_t rows_out, int32_t F, int32_t group, bool maxp,
                                  hipStream_t stream);
 
+// attention over the neighbour table of the pixel graph (nbr_attention.hip)
+int launch_nbr_attention_forward(const float* q, const float* k, const float* v, int64_t ld, float* out, float* lse, const int32_t* nbr,
+                                 int32_t width, int64_t N, int64_t M, int32_t heads, int32_t depth, hipStream_t stream);
+int launch_nbr_attention_backward(const float* q, const float* k, const float* v, int64_t ld, const float* out, const float* lse,
+                                  const float* dout, const int32_t* nbr, int32_t width, const int32_t* nbrT, int32_t widthT,
+                                  float* delta, float* dq, float* dk, float* dv, int64_t ld_grad, int64_t N, int64_t M, int32_t heads,
+                                  int32_t depth, hipStream_t stream);
+
 // input-side strip kernel (cheb_istrip.hip): layers with at most 16 input channels, one wave per strip
 struct IStripLaunch : LaunchBase {
   unsigned char* wimg;       // workspace: istrip_wimg_bytes() per 32-column block

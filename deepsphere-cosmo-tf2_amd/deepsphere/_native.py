@@ -112,6 +112,10 @@ SIGNATURES = {
     "dsph_healpix_pool": (ctypes.c_int, [_c_vp, _c_vp, _c_i64, _c_i64, _c_i32, _c_i32, _c_i32, ctypes.c_int, _c_vp]),
     "dsph_healpix_pool_backward": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i32, _c_i32, _c_i32, ctypes.c_int, _c_vp]),
     "dsph_residual_epilogue": (ctypes.c_int, [_c_vp, _c_vp, _c_i64, ctypes.c_float, _c_i32, _c_i32, ctypes.c_int, _c_vp]),
+    "dsph_nbr_attention_forward": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, _c_i64, _c_vp, _c_vp, _c_vp, _c_i32, _c_i64, _c_i64, _c_i32, _c_i32,
+                                                   ctypes.c_int, _c_vp]),
+    "dsph_nbr_attention_backward": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, _c_i64, _c_vp, _c_vp, _c_vp, _c_vp, _c_i32, _c_vp, _c_i32, _c_vp,
+                                                    _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i32, _c_i32, ctypes.c_int, _c_vp]),
 }
 
 
@@ -527,3 +531,85 @@ def healpix_pool_backward(x, dy, group, pool_type=POOL_MAX):
                                           int(pool_type), dy.device.index, _stream_ptr(dy.device))
     check(rc, "dsph_healpix_pool_backward")
     return dx
+
+
+def rows_layout(t):
+    """Row stride ``ld`` (in elements) of a float32 HIP tensor (N, M, d) whose rows are ``ld >= d`` apart with the maps back to
+    back -- a contiguous tensor, or a channel slice of one (a view into a wider projection buffer); ``None`` for any other layout."""
+    import torch
+
+    if not (t.is_cuda and t.dtype == torch.float32 and t.dim() == 3):
+        return None
+    N, M, d = t.shape
+    s0, s1, s2 = t.stride()
+    if d > 1 and s2 != 1:
+        return None
+    if M > 1 and s1 < d:
+        return None
+    ld = s1 if M > 1 else max(s1, d)
+    if N > 1 and s0 != M * ld:
+        return None
+    return int(ld)
+
+
+def _check_tables(nbr, M, device, name):
+    import torch
+
+    if not (isinstance(nbr, torch.Tensor) and nbr.dtype == torch.int32 and nbr.dim() == 2 and nbr.is_contiguous()):
+        raise ValueError(f"{name} must be a contiguous int32 tensor [M, W]")
+    if nbr.device != device:
+        raise ValueError(f"{name} lives on {nbr.device}, the maps on {device}")
+    if nbr.shape[0] != M:
+        raise ValueError(f"{name} has {nbr.shape[0]} rows, the maps have {M}")
+
+
+def nbr_attention(q, k, v, nbr, num_heads, need_lse=True):
+    """Attention over the neighbour table ``nbr`` (int32 [M, W], -1 padded) on (N, M, d) maps (``dsph_nbr_attention_forward``):
+    -> (out (N, M, d), lse (N, M, heads) or None).  q, k, v may be channel slices of one wider buffer (``rows_layout``)."""
+    import torch
+
+    require_gpu()
+    lds = [rows_layout(t) for t in (q, k, v)]
+    if None in lds or len(set(lds)) != 1 or not (q.shape == k.shape == v.shape) or not (q.device == k.device == v.device):
+        raise ValueError("q, k, v must be float32 HIP tensors of one shape (N, M, d) on one device, rows one common stride apart")
+    N, M, d = q.shape
+    if num_heads < 1 or d % num_heads != 0:
+        raise ValueError(f"d = {d} is not a multiple of num_heads = {num_heads}")
+    _check_tables(nbr, M, q.device, "nbr")
+    out = torch.empty((N, M, d), dtype=torch.float32, device=q.device)
+    lse = torch.empty((N, M, num_heads), dtype=torch.float32, device=q.device) if need_lse else None
+    rc = lib().dsph_nbr_attention_forward(_ptr(q), _ptr(k), _ptr(v), lds[0], _ptr(out), _ptr(lse), _ptr(nbr), int(nbr.shape[1]),
+                                          int(N), int(M), int(num_heads), int(d // num_heads), q.device.index,
+                                          _stream_ptr(q.device))
+    check(rc, "dsph_nbr_attention_forward")
+    return out, lse
+
+
+def nbr_attention_backward(q, k, v, out, lse, dout, nbr, nbrT, num_heads, grads=None):
+    """dq, dk, dv of ``nbr_attention`` (``dsph_nbr_attention_backward``; deterministic).  ``nbrT``: the table of the transposed
+    graph.  ``grads``: three tensors to write into (channel slices of one buffer: the gradient of a fused q/k/v projection comes
+    out as one tensor); allocated when None."""
+    import torch
+
+    require_gpu()
+    lds = [rows_layout(t) for t in (q, k, v)]
+    if None in lds or len(set(lds)) != 1:
+        raise ValueError("q, k, v must be float32 HIP tensors (N, M, d), rows one common stride apart")
+    N, M, d = q.shape
+    _check_tables(nbr, M, q.device, "nbr")
+    _check_tables(nbrT, M, q.device, "nbrT")
+    out, dout = out.contiguous(), dout.contiguous()
+    if tuple(out.shape) != (N, M, d) or tuple(dout.shape) != (N, M, d) or tuple(lse.shape) != (N, M, num_heads):
+        raise ValueError("out / dout / lse do not have the forward's shapes")
+    if grads is None:
+        grads = tuple(torch.empty((N, M, d), dtype=torch.float32, device=q.device) for _ in range(3))
+    glds = [rows_layout(t) for t in grads]
+    if None in glds or len(set(glds)) != 1 or any(tuple(g.shape) != (N, M, d) for g in grads):
+        raise ValueError("dq, dk, dv must be float32 HIP tensors (N, M, d), rows one common stride apart")
+    delta = torch.empty((N, M, num_heads), dtype=torch.float32, device=q.device)
+    rc = lib().dsph_nbr_attention_backward(_ptr(q), _ptr(k), _ptr(v), lds[0], _ptr(out), _ptr(lse.contiguous()), _ptr(dout), _ptr(nbr),
+                                           int(nbr.shape[1]), _ptr(nbrT), int(nbrT.shape[1]), _ptr(delta), _ptr(grads[0]),
+                                           _ptr(grads[1]), _ptr(grads[2]), glds[0], int(N), int(M), int(num_heads),
+                                           int(d // num_heads), q.device.index, _stream_ptr(q.device))
+    check(rc, "dsph_nbr_attention_backward")
+    return grads

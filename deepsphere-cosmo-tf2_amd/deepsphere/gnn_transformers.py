@@ -1,0 +1,303 @@
+"""Graph transformer layers: attention restricted to the edges of the pixel graph.
+
+Mirror of the reference's ``deepsphere.gnn_transformers`` (``gnn_transformers.py``): ``Graph_Transformer`` with its
+``MultiHeadAttention`` blocks and ``AddPositionEmbs``.  The attention itself -- in the reference three embedding lookups that
+materialise q, k and v per edge, ``exp`` and two segment sums (``:54-106``) -- is one gather kernel forward and two backward
+(``csrc/nbr_attention.hip``) working on channels-last (N, M, d) maps and a padded neighbour table; the dense layers and layer
+norms around it are the host framework's, like the GEMM of ``HealpyPseudoConv``.  ``Graph_ViT`` (dense attention over
+super-pixels) is not rebuilt.
+"""
+
+import numpy as np
+import torch
+from scipy import sparse
+
+from . import _native
+from .gnn_layers import _resolve_activation
+from .utils import adjacency_to_ell
+
+
+def _as_table(t):
+    return t if isinstance(t, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(t, dtype=np.int32))
+
+
+def neighbour_tables(A):
+    """(nbr, nbrT): the neighbour tables (``utils.adjacency_to_ell``) of ``A`` and of ``A.T`` as int32 CPU tensors -- ONE tensor
+    when the two are equal, as for every HEALPix graph."""
+    A = sparse.csr_matrix(A)
+    nbr, nbrT = adjacency_to_ell(A), adjacency_to_ell(A.T)
+    nbr = torch.from_numpy(nbr)
+    if nbr.shape == nbrT.shape and np.array_equal(nbr.numpy(), nbrT):
+        return nbr, nbr
+    return nbr, torch.from_numpy(nbrT)
+
+
+def _tables_from_indices(sparse_A_indices):
+    """What ``MultiHeadAttention(sparse_A_indices=...)`` accepts: a pair of neighbour tables (nbr, nbrT), a (sparse) adjacency
+    matrix, or the reference's [E, 2] array of (row, column) positions (the graph then has max index + 1 nodes)."""
+    if isinstance(sparse_A_indices, (tuple, list)) and len(sparse_A_indices) == 2 and all(
+            getattr(t, "ndim", 0) == 2 and "int32" in str(t.dtype) for t in sparse_A_indices):
+        return _as_table(sparse_A_indices[0]), _as_table(sparse_A_indices[1])
+    if sparse.issparse(sparse_A_indices):
+        return neighbour_tables(sparse_A_indices)
+    idx = np.asarray(sparse_A_indices)
+    if idx.ndim == 2 and idx.shape[1] == 2 and np.issubdtype(idx.dtype, np.integer):
+        M = int(idx.max()) + 1 if idx.size else 0
+        return neighbour_tables(sparse.csr_matrix((np.ones(idx.shape[0]), (idx[:, 0], idx[:, 1])), shape=(M, M)))
+    if idx.ndim == 2 and idx.shape[0] == idx.shape[1]:
+        return neighbour_tables(sparse.csr_matrix(idx))
+    raise ValueError("sparse_A_indices: expected (nbr, nbrT) int32 tables, an adjacency matrix or an [E, 2] index array")
+
+
+def _kernel_layout(q, k, v):
+    """q, k, v as the kernel reads them: untouched when they are rows of one common stride (contiguous, or channel slices of one
+    projection buffer), contiguous copies otherwise."""
+    lds = [_native.rows_layout(t) for t in (q, k, v)]
+    ok = None not in lds and len(set(lds)) == 1 and lds[0] % 4 == 0 and all(t.data_ptr() % 16 == 0 for t in (q, k, v))
+    return (q, k, v) if ok else (q.contiguous(), k.contiguous(), v.contiguous())
+
+
+def _require_hip(*tensors):
+    _native.require_gpu()
+    for t in tensors:
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 3):
+            raise ValueError("the neighbour attention works on float32 HIP tensors (N, M, d); there is no CPU path")
+
+
+class _SparseAttention(torch.autograd.Function):
+    """out = softmax over the neighbours of (q k^T / sqrt(depth)) v; saves q, k, v, out and the log-sum-exp, gradients from
+    ``dsph_nbr_attention_backward``."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, nbr, nbrT, num_heads):
+        q, k, v = _kernel_layout(q, k, v)
+        out, lse = _native.nbr_attention(q, k, v, nbr, num_heads)
+        ctx.save_for_backward(q, k, v, out, lse, nbr, nbrT)
+        ctx.num_heads = num_heads
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, k, v, out, lse, nbr, nbrT = ctx.saved_tensors
+        dq, dk, dv = _native.nbr_attention_backward(q, k, v, out, lse, dout, nbr, nbrT, ctx.num_heads)
+        return dq, dk, dv, None, None, None
+
+
+class _SparseAttentionPacked(torch.autograd.Function):
+    """The same on the output of a fused projection, qkv (N, M, 3 d) = [q | k | v]: the kernels read the three channel slices in
+    place and write dq, dk, dv into the slices of ONE gradient tensor (autograd would otherwise pad and add three of them)."""
+
+    @staticmethod
+    def forward(ctx, qkv, nbr, nbrT, num_heads):
+        qkv = qkv.contiguous()
+        d = qkv.shape[2] // 3
+        q, k, v = qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:]
+        if d % 4 != 0:  # (slices that are not 16-byte aligned: copies; the kernels then name their limit)
+            q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+        out, lse = _native.nbr_attention(q, k, v, nbr, num_heads)
+        ctx.save_for_backward(qkv, out, lse, nbr, nbrT)
+        ctx.num_heads = num_heads
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        qkv, out, lse, nbr, nbrT = ctx.saved_tensors
+        d = qkv.shape[2] // 3
+        dqkv = torch.empty_like(qkv)
+        _native.nbr_attention_backward(qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:], out, lse, dout, nbr, nbrT, ctx.num_heads,
+                                       grads=(dqkv[..., :d], dqkv[..., d:2 * d], dqkv[..., 2 * d:]))
+        return dqkv, None, None, None
+
+
+def scaled_dot_product_sparse_attention(q, k, v, nbr, nbrT, num_heads):
+    """Attention of every pixel over its graph neighbours (reference ``gnn_transformers.py:54-106``), differentiable.
+
+    :param q, k, v: float32 HIP tensors (N, M, d), channels last; head h is channels [h d / num_heads, (h + 1) d / num_heads)
+        -- the reference's ``split_heads`` without its transposes.  Strided views are read in place when their rows share one
+        stride (three slices of one projection buffer).
+    :param nbr: int32 [M, W] neighbour table (``utils.adjacency_to_ell(A)``), on the tensors' device
+    :param nbrT: the table of ``A.T`` (the same tensor for a symmetric graph); read by the backward only
+    :param num_heads: number of heads
+    :return: (N, M, d)
+
+    The softmax is evaluated in its stable form (running maximum), a deliberate deviation from the reference, which
+    exponentiates the raw logits and overflows in fp32 once one exceeds about 88; mathematically the two are equal.  A row
+    without neighbours gives zeros (the reference: 0 / 0)."""
+    _require_hip(q, k, v)
+    return _SparseAttention.apply(q, k, v, nbr, nbrT, int(num_heads))
+
+
+def _glorot_uniform_(w):
+    torch.nn.init.xavier_uniform_(w)  # Keras' default glorot_uniform: limit = sqrt(6 / (fan_in + fan_out))
+
+
+class AddPositionEmbs(torch.nn.Module):
+    """Adds a learned positional embedding (1, M, d) to the input (reference ``gnn_transformers.py:113-146``); built on the
+    first call.  Default initialiser: Glorot-uniform with Keras' fans for that shape, limit = sqrt(6 / (M + d)) (the reference
+    passes ``posemb_init=None``, Keras' default for ``add_weight``)."""
+
+    def __init__(self, posemb_init=None, **kwargs):
+        super().__init__()
+        self.posemb_init = posemb_init
+        self.pos_embedding = None
+
+    def build(self, inputs_shape, device=None):
+        M, d = int(inputs_shape[1]), int(inputs_shape[2])
+        w = torch.empty((1, M, d), dtype=torch.float32, device=device)
+        if self.posemb_init is not None:
+            self.posemb_init(w)
+        else:
+            limit = float(np.sqrt(6.0 / (M + d)))
+            torch.nn.init.uniform_(w, -limit, limit)
+        self.pos_embedding = torch.nn.Parameter(w)
+
+    def forward(self, inputs):
+        if self.pos_embedding is None:
+            self.build(inputs.shape, inputs.device)
+        return inputs + self.pos_embedding.to(inputs.dtype)
+
+    call = forward
+
+
+class MultiHeadAttention(torch.nn.Module):
+    """One transformer block of the reference (``gnn_transformers.py:149-245``), in its order: layer norm, q / k / v projections,
+    attention over the graph neighbours, + the normed input, layer norm, dense, activation, + the residual again.
+
+    Parameters: ``wqkv`` -- the reference's three ``Dense(d_model)`` layers ``wq``, ``wk``, ``wv`` fused into ONE [d, 3 d]
+    projection (rows [0, d) of ``wqkv.weight`` are wq, [d, 2 d) wk, [2 d, 3 d) wv; each block Glorot-uniform with its own
+    fans, zero bias), whose output the kernel reads as three strided views -- ``dense``, ``layer_norm1``, ``layer_norm2``
+    (eps = 1e-3, Keras' default).  ``use_norm=False`` makes both norms the identity (the reference crashes there: it calls
+    norms it did not create)."""
+
+    def __init__(self, d_model, num_heads, use_norm=True, activation="relu", sparse_A_indices=None):
+        """
+        :param d_model: channels of q, k and v (all heads together)
+        :param num_heads: number of heads; must divide ``d_model``
+        :param use_norm: layer norms, or identities
+        :param activation: by Keras name or a callable
+        :param sparse_A_indices: the graph -- a pair of neighbour tables (nbr, nbrT), an adjacency matrix or the reference's
+            [E, 2] positions.  None: the tables must come with the call (``Graph_Transformer`` passes its own); dense attention
+            (the reference's ``mask`` path) is not built.
+        """
+        super().__init__()
+        if num_heads < 1 or d_model % num_heads != 0:
+            raise ValueError(f"d_model = {d_model} must be a multiple of num_heads = {num_heads}")
+        self.d_model, self.num_heads, self.use_norm = int(d_model), int(num_heads), bool(use_norm)
+        self.depth = self.d_model // self.num_heads
+        self.activation, _ = _resolve_activation(activation)
+        if sparse_A_indices is not None:
+            nbr, nbrT = _tables_from_indices(sparse_A_indices)
+            self.register_buffer("nbr", nbr, persistent=False)
+            if nbrT is not nbr:
+                self.register_buffer("nbrT_", nbrT, persistent=False)
+        else:
+            self.nbr = None
+        d = self.d_model
+        self.wqkv = torch.nn.Linear(d, 3 * d)
+        self.dense = torch.nn.Linear(d, d)
+        with torch.no_grad():
+            for i in range(3):
+                _glorot_uniform_(self.wqkv.weight[i * d:(i + 1) * d])
+            _glorot_uniform_(self.dense.weight)
+            self.wqkv.bias.zero_()
+            self.dense.bias.zero_()
+        if self.use_norm:
+            self.layer_norm1 = torch.nn.LayerNorm(d, eps=1e-3)
+            self.layer_norm2 = torch.nn.LayerNorm(d, eps=1e-3)
+        else:
+            self.layer_norm1 = torch.nn.Identity()
+            self.layer_norm2 = torch.nn.Identity()
+
+    @property
+    def nbrT(self):
+        return getattr(self, "nbrT_", self.nbr)
+
+    def forward(self, inputs, tables=None):
+        nbr, nbrT = tables if tables is not None else (self.nbr, self.nbrT)
+        if nbr is None:
+            raise NotImplementedError("MultiHeadAttention without neighbour tables is dense attention over all pixels (the "
+                                      "reference's Graph_ViT path); it needs a flash-style kernel that is not built yet")
+        _require_hip(inputs)
+        x = self.layer_norm1(inputs)
+        qkv = self.wqkv(x)  # (N, M, 3 d): q | k | v
+        att = _SparseAttentionPacked.apply(qkv, nbr, nbrT, self.num_heads)
+        att = x + att
+        out = self.dense(self.layer_norm2(att))
+        if self.activation is not None:
+            out = self.activation(out)
+        return out + att
+
+    call = forward
+
+
+class Graph_Transformer(torch.nn.Module):
+    """A graph transformer on the pixels of a map (reference ``gnn_transformers.py:359-450``): a dense embedding to
+    ``key_dim * num_heads`` channels, an optional learned position embedding and ``n_layers`` attention blocks whose softmax
+    runs over the edges of the adjacency matrix ``A`` (only its pattern is used).
+
+    Parameter names follow the reference's attributes: ``embed``, ``pos_encoder.pos_embedding``,
+    ``mha_layers.{i}.wqkv / dense / layer_norm1 / layer_norm2`` (``wqkv``: wq, wk, wv fused, see ``MultiHeadAttention``).
+    ``embed`` and the position embedding are built on the first call, like Keras builds them.  Runs on a HIP device only."""
+
+    def __init__(self, A, key_dim, num_heads, positional_encoding=True, n_layers=1, activation="relu", layer_norm=True):
+        super().__init__()
+        if not n_layers >= 1:
+            raise ValueError("Number of attention layers should be at least 1")
+        self.A = A
+        self.key_dim, self.num_heads = int(key_dim), int(num_heads)
+        self.embedding_size = self.key_dim * self.num_heads
+        self.Fout = self.embedding_size  # read by the model builder to track the channel count
+        self.positional_encoding = positional_encoding
+        self.n_layers = n_layers
+        self.activation = activation
+        self.layer_norm = layer_norm
+        nbr, nbrT = neighbour_tables(A)
+        self.register_buffer("nbr", nbr, persistent=False)
+        if nbrT is not nbr:
+            self.register_buffer("nbrT_", nbrT, persistent=False)
+        self.embed = None
+        if self.positional_encoding:
+            self.pos_encoder = AddPositionEmbs()
+        self.mha_layers = torch.nn.ModuleList(
+            MultiHeadAttention(d_model=self.embedding_size, num_heads=self.num_heads, use_norm=self.layer_norm,
+                               activation=self.activation) for _ in range(n_layers))
+
+    @property
+    def nbrT(self):
+        return getattr(self, "nbrT_", self.nbr)
+
+    def build(self, input_shape, device=None):
+        self.embed = torch.nn.Linear(int(input_shape[-1]), self.embedding_size, device=device)
+        with torch.no_grad():
+            _glorot_uniform_(self.embed.weight)
+            self.embed.bias.zero_()
+        if self.positional_encoding and self.pos_encoder.pos_embedding is None:
+            self.pos_encoder.build((1, int(input_shape[1]), self.embedding_size), device)
+
+    def forward(self, inputs):
+        x = inputs if isinstance(inputs, torch.Tensor) else torch.as_tensor(np.asarray(inputs), dtype=torch.float32)
+        _require_hip(x)
+        if x.shape[1] != self.nbr.shape[0]:
+            raise ValueError(f"the input has {x.shape[1]} pixels, the graph {self.nbr.shape[0]}")
+        if self.embed is None:
+            self.build(x.shape, x.device)
+        if self.nbr.device != x.device:  # (the tables follow the maps, like the plans of the convolution layers)
+            self.nbr = self.nbr.to(x.device)
+            if hasattr(self, "nbrT_"):
+                self.nbrT_ = self.nbrT_.to(x.device)
+        for m in self.mha_layers:  # (lazily built layers: parameters created before a .to(device) of the parent are moved by it)
+            if m.wqkv.weight.device != x.device:
+                m.to(x.device)
+        x = self.embed(x)
+        if self.positional_encoding:
+            x = self.pos_encoder(x)
+        tables = (self.nbr, self.nbrT)
+        for mha in self.mha_layers:
+            x = mha(x, tables)
+        return x
+
+    call = forward
+
+
+__all__ = ["scaled_dot_product_sparse_attention", "AddPositionEmbs", "MultiHeadAttention", "Graph_Transformer",
+           "neighbour_tables"]

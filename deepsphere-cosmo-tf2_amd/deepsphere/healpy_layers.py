@@ -11,6 +11,7 @@ import torch
 
 from . import _native
 from .gnn_layers import Chebyshev, GCNN_ResidualLayer, Monomial
+from .gnn_transformers import Graph_Transformer
 
 
 def _as_tensor(x):
@@ -224,5 +225,33 @@ class Healpy_ResidualLayer:
                                   bn_kwargs=self.bn_kwargs, alpha=self.alpha)
 
 
+class Healpy_Transformer:
+    """Deferred spec of a graph transformer on a HEALPix map (reference ``healpy_layers.py:417-459``): the model builder hands
+    ``_get_layer`` the ADJACENCY matrix of the current resolution, not the Laplacian."""
+
+    def __init__(self, key_dim, num_heads, positional_encoding=True, n_layers=1, activation="relu", layer_norm=True):
+        """
+        :param key_dim: channels of key, query and value per head; the embedding has ``key_dim * num_heads`` channels
+        :param num_heads: number of heads
+        :param positional_encoding: add a learned position embedding after the initial embedding
+        :param n_layers: number of attention blocks
+        :param activation: activation of the blocks
+        :param layer_norm: layer norms in the blocks
+        """
+        self.key_dim = key_dim
+        self.num_heads = num_heads
+        self.positional_encoding = positional_encoding
+        self.n_layers = n_layers
+        self.activation = activation
+        self.layer_norm = layer_norm
+        self.Fout = key_dim * num_heads  # read by the model builder to track the channel count
+
+    def _get_layer(self, A):
+        """Instantiate the layer for the graph with adjacency matrix ``A`` (NEST pixel order)."""
+        return Graph_Transformer(A=A, key_dim=self.key_dim, num_heads=self.num_heads,
+                                 positional_encoding=self.positional_encoding, n_layers=self.n_layers,
+                                 activation=self.activation, layer_norm=self.layer_norm)
+
+
 __all__ = ["HealpyPool", "HealpyPseudoConv", "HealpyPseudoConv_Transpose", "HealpyChebyshev", "HealpyMonomial",
-           "Healpy_ResidualLayer"]
+           "Healpy_ResidualLayer", "Healpy_Transformer"]

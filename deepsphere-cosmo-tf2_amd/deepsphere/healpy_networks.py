@@ -70,6 +70,10 @@ class HealpyGCNN(torch.nn.Sequential):
                     layers_use.append(layer._get_layer(L, splits))
                 else:
                     layers_use.append(layer._get_layer(L))
+            elif isinstance(layer, hp_nn.Healpy_Transformer):
+                # the graph transformer attends along the edges: it gets the adjacency matrix of this resolution (:118-120)
+                A = healpix.healpix_graph(current_nside, current_indices, n_neighbors, graph_mode)
+                layers_use.append(layer._get_layer(A))
             elif isinstance(layer, (hp_nn.HealpyPool, hp_nn.HealpyPseudoConv)):
                 new_nside = int(current_nside // 2 ** layer.p)
                 current_indices = self._transform_indices(current_nside, new_nside, current_indices)

@@ -9,7 +9,7 @@ from scipy.sparse.linalg import eigsh
 from .healpix import extend_indices  # noqa: F401  (same public name as utils.py:9)
 
 __all__ = ["extend_indices", "rescale_L", "prepare_L", "csr_to_ell", "split_sparse_dense_matmul", "lanczos_lmax",
-           "rescale_ell"]
+           "rescale_ell", "adjacency_to_ell"]
 
 
 def rescale_L(L, lmax=2, scale=1):
@@ -68,6 +68,31 @@ def csr_to_ell(A, width=None):
     cols[rows, slot] = A.indices.astype(np.int32)
     vals[rows, slot] = A.data.astype(np.float32)
     return cols, vals
+
+
+def adjacency_to_ell(A):
+    """Neighbour table of an adjacency matrix for the attention kernel: int32 [M, W], row i lists the columns j of the
+    positions ``A.nonzero()`` reports in ascending order, then -1; W = max(longest row, 1).
+
+    The positions are the ones the reference turns into its attention mask (``gnn_transformers.py:399``:
+    ``sparse.csc_matrix.nonzero(A)``), so an explicitly stored zero is not an edge.  Only the pattern is used, never the
+    weights.  The table of the transposed graph is ``adjacency_to_ell(A.T)``."""
+    A = sparse.csr_matrix(A)
+    if A.shape[0] != A.shape[1]:
+        raise ValueError("the adjacency matrix must be square")
+    M = A.shape[0]
+    if M >= 2**31:
+        raise ValueError("the neighbour table holds int32 row indices")
+    rows, cols = A.nonzero()
+    order = np.lexsort((cols, rows))
+    rows, cols = np.asarray(rows, dtype=np.int64)[order], np.asarray(cols, dtype=np.int64)[order]
+    lens = np.bincount(rows, minlength=M)
+    W = max(int(lens.max()) if M > 0 else 0, 1)
+    start = np.concatenate([[0], np.cumsum(lens)[:-1]]) if M > 0 else np.zeros(0, dtype=np.int64)
+    slot = np.arange(rows.shape[0], dtype=np.int64) - np.repeat(start, lens)
+    nbr = np.full((M, W), -1, dtype=np.int32)
+    nbr[rows, slot] = cols.astype(np.int32)
+    return nbr
 
 
 def split_sparse_dense_matmul(sparse_tensor, dense_tensor, n_splits=1):

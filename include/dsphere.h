@@ -406,6 +406,33 @@ int dsph_healpix_pool(const float* x, float* y, int64_t N, int64_t rows_out, int
 int dsph_healpix_pool_backward(const float* x, const float* dy, float* dx, int64_t N, int64_t rows_out, int32_t F, int32_t group,
                                int32_t type, int device, void* hip_stream);
 
+/* Attention over the edges of the pixel graph (plan-free; csrc/nbr_attention.hip).
+ * Replaces: gnn_transformers.scaled_dot_product_sparse_attention (reference gnn_transformers.py:54-106: three embedding lookups that
+ * materialise q, k, v per edge, exp, two segment sums) and the split_heads transposes around it (:189-196, :225-231).
+ *   q, k, v  device (N, M, heads * depth) fp32, channels last, rows `ld` floats apart (ld >= heads * depth: three views of one
+ *            (N, M, 3 heads depth) projection need no copy); head h is channels [h depth, (h + 1) depth)
+ *   nbr      device int32 [M][width]: the neighbours of row i first, -1 in the unused slots; summed in slot order; an entry
+ *            outside [0, M) counts as unused
+ *   out      device (N, M, heads * depth), contiguous:  out[n,i,h] = sum_j softmax_j(q_i,h . k_j,h / sqrt(depth)) v_j,h
+ *   lse      device (N, M, heads) or NULL:  log sum_j exp(q_i,h . k_j,h / sqrt(depth)), what the backward needs
+ * The softmax is the stable form (running maximum); the reference exponentiates the raw logits, which is the same number until
+ * it overflows (logits above 88).  A row without neighbours gives out = 0 and lse = 0 (the reference: 0 / 0).
+ * Shapes: depth one of 4, 8, 16, 32, 64; heads >= 1 with heads * depth <= 256; width >= 1; ld a multiple of 4; q, k, v, out
+ * 16-byte aligned.  Anything else: DSPH_E_BADARG with the limit named in the message; there is no slower path.
+ *
+ * The backward (the reference: TensorFlow's autodiff), from the forward's out and lse and the upstream gradient dout (contiguous,
+ * out's shape): dq, dk, dv with rows ld_grad floats apart.  nbrT [M][widthT] is the table of the transposed graph (row j lists
+ * the i whose row names j; pass nbr again for a symmetric graph).  `delta` is scratch of N * M * heads floats (the call writes
+ * delta[n,i,h] = dout_i,h . out_i,h there).  No atomics: every element has one writer and a fixed order of summation, so two
+ * runs agree bit for bit.  Two launches.  Both calls only enqueue on `hip_stream`. */
+int dsph_nbr_attention_forward(const float* q, const float* k, const float* v, int64_t ld, float* out, float* lse,
+                               const int32_t* nbr, int32_t width, int64_t N, int64_t M, int32_t heads, int32_t depth, int device,
+                               void* hip_stream);
+int dsph_nbr_attention_backward(const float* q, const float* k, const float* v, int64_t ld, const float* out, const float* lse,
+                                const float* dout, const int32_t* nbr, int32_t width, const int32_t* nbrT, int32_t widthT,
+                                float* delta, float* dq, float* dk, float* dv, int64_t ld_grad, int64_t N, int64_t M, int32_t heads,
+                                int32_t depth, int device, void* hip_stream);
+
 const char* dsph_last_error(void);
 int dsph_abi_version(void);
 
