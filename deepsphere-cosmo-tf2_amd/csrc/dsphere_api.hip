@@ -690,4 +690,52 @@ int dsph_nbr_attention_backward(const float* q, const float* k, const float* v, 
                                        depth, (hipStream_t)hip_stream);
 }
 
+// the shape limits of csrc/dense_attention.hip, each named in its message
+static int dense_attention_args_ok(const char* who, int64_t ld, int64_t N, int64_t M, int32_t heads, int32_t depth) {
+  if (N < 0) { set_error("%s: negative batch size N = %lld", who, (long long)N); return DSPH_E_BADARG; }
+  if (M < 1) { set_error("%s: M = %lld rows, must be at least 1", who, (long long)M); return DSPH_E_BADARG; }
+  if (depth != 4 && depth != 8 && depth != 16 && depth != 32 && depth != 64) {
+    set_error("%s: depth %d per head is not one of 4, 8, 16, 32, 64", who, (int)depth);
+    return DSPH_E_BADARG;
+  }
+  if (heads < 1 || (int64_t)heads * depth > 256) {
+    set_error("%s: heads * depth = %d * %d must lie in [depth, 256]", who, (int)heads, (int)depth);
+    return DSPH_E_BADARG;
+  }
+  if (ld % 4 != 0 || ld < (int64_t)heads * depth) {
+    set_error("%s: row stride %lld must be a multiple of 4 floats and at least heads * depth = %d", who, (long long)ld, (int)(heads * depth));
+    return DSPH_E_BADARG;
+  }
+  return DSPH_OK;
+}
+
+int dsph_dense_attention_forward(const float* q, const float* k, const float* v, int64_t ld, float* out, float* lse, int64_t N, int64_t M,
+                                 int32_t heads, int32_t depth, int device, void* hip_stream) {
+  if (!q || !k || !v || !out) { set_error("dense_attention_forward: NULL pointer"); return DSPH_E_BADARG; }
+  const int rc = dense_attention_args_ok("dense_attention_forward", ld, N, M, heads, depth);
+  if (rc != DSPH_OK) return rc;
+  if (!aligned16({q, k, v, out})) { set_error("dense_attention_forward: q, k, v and out must be 16-byte aligned"); return DSPH_E_BADARG; }
+  DeviceGuard guard(device);
+  return launch_dense_attention_forward(q, k, v, ld, out, lse, N, M, heads, depth, (hipStream_t)hip_stream);
+}
+
+int dsph_dense_attention_backward(const float* q, const float* k, const float* v, int64_t ld, const float* out, const float* lse,
+                                  const float* dout, float* delta, float* dq, float* dk, float* dv, int64_t ld_grad, int64_t N, int64_t M,
+                                  int32_t heads, int32_t depth, int device, void* hip_stream) {
+  if (!q || !k || !v || !out || !lse || !dout || !delta || !dq || !dk || !dv) {
+    set_error("dense_attention_backward: NULL pointer");
+    return DSPH_E_BADARG;
+  }
+  int rc = dense_attention_args_ok("dense_attention_backward", ld, N, M, heads, depth);
+  if (rc == DSPH_OK) rc = dense_attention_args_ok("dense_attention_backward (gradients)", ld_grad, N, M, heads, depth);
+  if (rc != DSPH_OK) return rc;
+  if (!aligned16({q, k, v, out, dout, dq, dk, dv})) {
+    set_error("dense_attention_backward: q, k, v, out, dout, dq, dk and dv must be 16-byte aligned");
+    return DSPH_E_BADARG;
+  }
+  DeviceGuard guard(device);
+  return launch_dense_attention_backward(q, k, v, ld, out, lse, dout, delta, dq, dk, dv, ld_grad, N, M, heads, depth,
+                                         (hipStream_t)hip_stream);
+}
+
 }  // extern "C"

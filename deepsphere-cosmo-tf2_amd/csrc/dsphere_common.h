@@ -282,6 +282,13 @@ int launch_nbr_attention_backward(const float* q, const float* k, const float* v
                                   float* delta, float* dq, float* dk, float* dv, int64_t ld_grad, int64_t N, int64_t M, int32_t heads,
                                   int32_t depth, hipStream_t stream);
 
+// dense attention over all rows of a map, flash style on the fp32 MFMA (dense_attention.hip)
+int launch_dense_attention_forward(const float* q, const float* k, const float* v, int64_t ld, float* out, float* lse, int64_t N, int64_t M,
+                                   int32_t heads, int32_t depth, hipStream_t stream);
+int launch_dense_attention_backward(const float* q, const float* k, const float* v, int64_t ld, const float* out, const float* lse,
+                                    const float* dout, float* delta, float* dq, float* dk, float* dv, int64_t ld_grad, int64_t N,
+                                    int64_t M, int32_t heads, int32_t depth, hipStream_t stream);
+
 // input-side strip kernel (cheb_istrip.hip): layers with at most 16 input channels, one wave per strip
 struct IStripLaunch : LaunchBase {
   unsigned char* wimg;       // workspace: istrip_wimg_bytes() per 32-column block

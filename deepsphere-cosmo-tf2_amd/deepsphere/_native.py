@@ -116,6 +116,10 @@ SIGNATURES = {
                                                    ctypes.c_int, _c_vp]),
     "dsph_nbr_attention_backward": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, _c_i64, _c_vp, _c_vp, _c_vp, _c_vp, _c_i32, _c_vp, _c_i32, _c_vp,
                                                     _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i32, _c_i32, ctypes.c_int, _c_vp]),
+    "dsph_dense_attention_forward": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, _c_i64, _c_vp, _c_vp, _c_i64, _c_i64, _c_i32, _c_i32, ctypes.c_int,
+                                                     _c_vp]),
+    "dsph_dense_attention_backward": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, _c_i64, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64,
+                                                      _c_i64, _c_i64, _c_i32, _c_i32, ctypes.c_int, _c_vp]),
 }
 
 
@@ -612,4 +616,52 @@ def nbr_attention_backward(q, k, v, out, lse, dout, nbr, nbrT, num_heads, grads=
                                            _ptr(grads[1]), _ptr(grads[2]), glds[0], int(N), int(M), int(num_heads),
                                            int(d // num_heads), q.device.index, _stream_ptr(q.device))
     check(rc, "dsph_nbr_attention_backward")
+    return grads
+
+
+def dense_attention(q, k, v, num_heads, need_lse=True):
+    """Attention of every row over ALL rows of its map on (N, M, d) maps (``dsph_dense_attention_forward``; flash style, no logit
+    reaches memory): -> (out (N, M, d), lse (N, M, heads) or None).  q, k, v may be channel slices of one wider buffer
+    (``rows_layout``)."""
+    import torch
+
+    require_gpu()
+    lds = [rows_layout(t) for t in (q, k, v)]
+    if None in lds or len(set(lds)) != 1 or not (q.shape == k.shape == v.shape) or not (q.device == k.device == v.device):
+        raise ValueError("q, k, v must be float32 HIP tensors of one shape (N, M, d) on one device, rows one common stride apart")
+    N, M, d = q.shape
+    if num_heads < 1 or d % num_heads != 0:
+        raise ValueError(f"d = {d} is not a multiple of num_heads = {num_heads}")
+    out = torch.empty((N, M, d), dtype=torch.float32, device=q.device)
+    lse = torch.empty((N, M, num_heads), dtype=torch.float32, device=q.device) if need_lse else None
+    rc = lib().dsph_dense_attention_forward(_ptr(q), _ptr(k), _ptr(v), lds[0], _ptr(out), _ptr(lse), int(N), int(M), int(num_heads),
+                                            int(d // num_heads), q.device.index, _stream_ptr(q.device))
+    check(rc, "dsph_dense_attention_forward")
+    return out, lse
+
+
+def dense_attention_backward(q, k, v, out, lse, dout, num_heads, grads=None):
+    """dq, dk, dv of ``dense_attention`` (``dsph_dense_attention_backward``; deterministic, nothing of size M^2 is allocated).
+    ``grads``: three tensors to write into (channel slices of one buffer: the gradient of a fused q/k/v projection comes out as
+    one tensor); allocated when None."""
+    import torch
+
+    require_gpu()
+    lds = [rows_layout(t) for t in (q, k, v)]
+    if None in lds or len(set(lds)) != 1 or not (q.shape == k.shape == v.shape):
+        raise ValueError("q, k, v must be float32 HIP tensors of one shape (N, M, d), rows one common stride apart")
+    N, M, d = q.shape
+    out, dout = out.contiguous(), dout.contiguous()
+    if tuple(out.shape) != (N, M, d) or tuple(dout.shape) != (N, M, d) or tuple(lse.shape) != (N, M, num_heads):
+        raise ValueError("out / dout / lse do not have the forward's shapes")
+    if grads is None:
+        grads = tuple(torch.empty((N, M, d), dtype=torch.float32, device=q.device) for _ in range(3))
+    glds = [rows_layout(t) for t in grads]
+    if None in glds or len(set(glds)) != 1 or any(tuple(g.shape) != (N, M, d) for g in grads):
+        raise ValueError("dq, dk, dv must be float32 HIP tensors (N, M, d), rows one common stride apart")
+    delta = torch.empty((N, M, num_heads), dtype=torch.float32, device=q.device)
+    rc = lib().dsph_dense_attention_backward(_ptr(q), _ptr(k), _ptr(v), lds[0], _ptr(out), _ptr(lse.contiguous()), _ptr(dout),
+                                             _ptr(delta), _ptr(grads[0]), _ptr(grads[1]), _ptr(grads[2]), glds[0], int(N), int(M),
+                                             int(num_heads), int(d // num_heads), q.device.index, _stream_ptr(q.device))
+    check(rc, "dsph_dense_attention_backward")
     return grads

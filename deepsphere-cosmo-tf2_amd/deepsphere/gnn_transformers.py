@@ -1,11 +1,13 @@
-"""Graph transformer layers: attention restricted to the edges of the pixel graph.
+"""Graph transformer layers: attention restricted to the edges of the pixel graph, and dense attention over super-pixels.
 
-Mirror of the reference's ``deepsphere.gnn_transformers`` (``gnn_transformers.py``): ``Graph_Transformer`` with its
-``MultiHeadAttention`` blocks and ``AddPositionEmbs``.  The attention itself -- in the reference three embedding lookups that
-materialise q, k and v per edge, ``exp`` and two segment sums (``:54-106``) -- is one gather kernel forward and two backward
-(``csrc/nbr_attention.hip``) working on channels-last (N, M, d) maps and a padded neighbour table; the dense layers and layer
-norms around it are the host framework's, like the GEMM of ``HealpyPseudoConv``.  ``Graph_ViT`` (dense attention over
-super-pixels) is not rebuilt.
+Mirror of the reference's ``deepsphere.gnn_transformers`` (``gnn_transformers.py``): ``Graph_Transformer`` and ``Graph_ViT`` with
+their ``MultiHeadAttention`` blocks and ``AddPositionEmbs``.  The attention over the graph's edges -- in the reference three
+embedding lookups that materialise q, k and v per edge, ``exp`` and two segment sums (``:54-106``) -- is one gather kernel forward
+and two backward (``csrc/nbr_attention.hip``) working on channels-last (N, M, d) maps and a padded neighbour table.  The dense
+attention of ``Graph_ViT`` -- in the reference two ``matmul``s around a softmax over a materialised (N, heads, M, M) tensor
+(``:14-51``) -- is a flash-style kernel on the exact-fp32 MFMA (``csrc/dense_attention.hip``: key tiles through LDS, online
+softmax, no logit in memory; two deterministic backward launches) on the same layout.  The dense layers and layer norms around
+both are the host framework's, like the GEMM of ``HealpyPseudoConv``.
 """
 
 import numpy as np
@@ -109,6 +111,67 @@ class _SparseAttentionPacked(torch.autograd.Function):
         return dqkv, None, None, None
 
 
+class _DenseAttention(torch.autograd.Function):
+    """out = softmax over ALL rows of (q k^T / sqrt(depth)) v; saves q, k, v, out and the log-sum-exp, gradients from
+    ``dsph_dense_attention_backward``."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, num_heads):
+        q, k, v = _kernel_layout(q, k, v)
+        out, lse = _native.dense_attention(q, k, v, num_heads)
+        ctx.save_for_backward(q, k, v, out, lse)
+        ctx.num_heads = num_heads
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, k, v, out, lse = ctx.saved_tensors
+        dq, dk, dv = _native.dense_attention_backward(q, k, v, out, lse, dout, ctx.num_heads)
+        return dq, dk, dv, None
+
+
+class _DenseAttentionPacked(torch.autograd.Function):
+    """The same on the output of a fused projection, qkv (N, M, 3 d) = [q | k | v], like ``_SparseAttentionPacked``: three channel
+    slices read in place, dq, dk, dv written into the slices of ONE gradient tensor."""
+
+    @staticmethod
+    def forward(ctx, qkv, num_heads):
+        qkv = qkv.contiguous()
+        d = qkv.shape[2] // 3
+        q, k, v = qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:]
+        if d % 4 != 0:  # (slices that are not 16-byte aligned: copies; the kernels then name their limit)
+            q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+        out, lse = _native.dense_attention(q, k, v, num_heads)
+        ctx.save_for_backward(qkv, out, lse)
+        ctx.num_heads = num_heads
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        qkv, out, lse = ctx.saved_tensors
+        d = qkv.shape[2] // 3
+        dqkv = torch.empty_like(qkv)
+        _native.dense_attention_backward(qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:], out, lse, dout, ctx.num_heads,
+                                         grads=(dqkv[..., :d], dqkv[..., d:2 * d], dqkv[..., 2 * d:]))
+        return dqkv, None
+
+
+def scaled_dot_product_attention(q, k, v, num_heads):
+    """Attention of every row over all rows of its map (reference ``gnn_transformers.py:14-51`` with ``mask=None``),
+    differentiable.
+
+    :param q, k, v: float32 HIP tensors (N, M, d), channels last; head h is channels [h d / num_heads, (h + 1) d / num_heads)
+        -- the reference's ``split_heads`` without its transposes.  Strided views are read in place when their rows share one
+        stride (three slices of one projection buffer).
+    :param num_heads: number of heads; d / num_heads one of 4, 8, 16, 32, 64 and d <= 256
+    :return: (N, M, d)
+
+    The reference also returns the attention weights, an (N, heads, M, M) tensor that nothing in it reads; they are never formed
+    here (that is the point of the kernel), and its ``mask`` argument, which ``Graph_ViT`` never passes, is not rebuilt."""
+    _require_hip(q, k, v)
+    return _DenseAttention.apply(q, k, v, int(num_heads))
+
+
 def scaled_dot_product_sparse_attention(q, k, v, nbr, nbrT, num_heads):
     """Attention of every pixel over its graph neighbours (reference ``gnn_transformers.py:54-106``), differentiable.
 
@@ -169,21 +232,25 @@ class MultiHeadAttention(torch.nn.Module):
     (eps = 1e-3, Keras' default).  ``use_norm=False`` makes both norms the identity (the reference crashes there: it calls
     norms it did not create)."""
 
-    def __init__(self, d_model, num_heads, use_norm=True, activation="relu", sparse_A_indices=None):
+    def __init__(self, d_model, num_heads, use_norm=True, activation="relu", sparse_A_indices=None, dense=False):
         """
         :param d_model: channels of q, k and v (all heads together)
         :param num_heads: number of heads; must divide ``d_model``
         :param use_norm: layer norms, or identities
         :param activation: by Keras name or a callable
         :param sparse_A_indices: the graph -- a pair of neighbour tables (nbr, nbrT), an adjacency matrix or the reference's
-            [E, 2] positions.  None: the tables must come with the call (``Graph_Transformer`` passes its own); dense attention
-            (the reference's ``mask`` path) is not built.
+            [E, 2] positions.  None: the tables must come with the call (``Graph_Transformer`` passes its own), or ``dense``
+            must be set.
+        :param dense: not a reference argument -- attention over ALL rows on the dense kernel (what the reference does when it has
+            no ``sparse_A_indices``; ``Graph_ViT`` builds its blocks this way).  No tables are needed or read.  The reference's
+            ``mask`` argument of that path is not rebuilt (``Graph_ViT`` never passes one).
         """
         super().__init__()
         if num_heads < 1 or d_model % num_heads != 0:
             raise ValueError(f"d_model = {d_model} must be a multiple of num_heads = {num_heads}")
         self.d_model, self.num_heads, self.use_norm = int(d_model), int(num_heads), bool(use_norm)
         self.depth = self.d_model // self.num_heads
+        self.dense_attention = bool(dense)
         self.activation, _ = _resolve_activation(activation)
         if sparse_A_indices is not None:
             nbr, nbrT = _tables_from_indices(sparse_A_indices)
@@ -213,14 +280,17 @@ class MultiHeadAttention(torch.nn.Module):
         return getattr(self, "nbrT_", self.nbr)
 
     def forward(self, inputs, tables=None):
-        nbr, nbrT = tables if tables is not None else (self.nbr, self.nbrT)
-        if nbr is None:
+        nbr, nbrT = (None, None) if self.dense_attention else tables if tables is not None else (self.nbr, self.nbrT)
+        if nbr is None and not self.dense_attention:
             raise NotImplementedError("MultiHeadAttention without neighbour tables is dense attention over all pixels (the "
-                                      "reference's Graph_ViT path); it needs a flash-style kernel that is not built yet")
+                                      "reference's Graph_ViT path): construct the block with dense=True to run it")
         _require_hip(inputs)
         x = self.layer_norm1(inputs)
         qkv = self.wqkv(x)  # (N, M, 3 d): q | k | v
-        att = _SparseAttentionPacked.apply(qkv, nbr, nbrT, self.num_heads)
+        if self.dense_attention:
+            att = _DenseAttentionPacked.apply(qkv, self.num_heads)
+        else:
+            att = _SparseAttentionPacked.apply(qkv, nbr, nbrT, self.num_heads)
         att = x + att
         out = self.dense(self.layer_norm2(att))
         if self.activation is not None:
@@ -299,5 +369,78 @@ class Graph_Transformer(torch.nn.Module):
     call = forward
 
 
-__all__ = ["scaled_dot_product_sparse_attention", "AddPositionEmbs", "MultiHeadAttention", "Graph_Transformer",
-           "neighbour_tables"]
+class Graph_ViT(torch.nn.Module):
+    """A vision transformer on the super-pixels of a map (reference ``gnn_transformers.py:248-356``): the 4^p NEST children of
+    a pixel of the p-times coarser map are one patch, embedded to ``key_dim * num_heads`` channels by a Conv1D with
+    kernel = stride = 4^p, an optional learned position embedding, then ``n_layers`` attention blocks in which every super-pixel
+    attends to every other one (``MultiHeadAttention(dense=True)``, the flash-style kernel).  The layer reduces the pixel count
+    by 4^p; it only checks that the count is a multiple of 4^p, not the ordering (NEST).
+
+    ``p >= 1`` is accepted: the reference's check ``not p > 1`` rejects p = 1 and so contradicts its own message ("has to be at
+    least 1") and its docstring; p = 1 is a valid patch of four pixels.
+
+    Parameter names follow the reference's attributes: ``embed.weight`` (d, Fin, 4^p) and ``embed.bias`` -- a lazily built
+    ``torch.nn.Conv1d``, Glorot-uniform / zero like Keras, evaluated as the single ``addmm`` that ``HealpyPseudoConv`` uses --
+    ``pos_encoder.pos_embedding`` (1, M / 4^p, d) and ``mha_layers.{i}.wqkv / dense / layer_norm1 / layer_norm2`` as in
+    ``Graph_Transformer``.  Runs on a HIP device only."""
+
+    def __init__(self, p, key_dim, num_heads, positional_encoding=True, n_layers=1, activation="relu", layer_norm=True):
+        super().__init__()
+        if not p >= 1:
+            raise IOError("The super pixel size factor p has to be at least 1!")
+        if not n_layers >= 1:
+            raise ValueError("Number of attention layers should be at least 1")
+        self.p = p
+        self.embed_filter_size = int(4 ** p)
+        self.key_dim, self.num_heads = int(key_dim), int(num_heads)
+        self.embedding_size = self.key_dim * self.num_heads
+        self.Fout = self.embedding_size  # read by the model builder to track the channel count
+        self.positional_encoding = positional_encoding
+        self.n_layers = n_layers
+        self.activation = activation
+        self.layer_norm = layer_norm
+        self.embed = None
+        if self.positional_encoding:
+            self.pos_encoder = AddPositionEmbs()
+        self.mha_layers = torch.nn.ModuleList(
+            MultiHeadAttention(d_model=self.embedding_size, num_heads=self.num_heads, use_norm=self.layer_norm,
+                               activation=self.activation, dense=True) for _ in range(n_layers))
+
+    def build(self, input_shape, device=None):
+        n_nodes, g = int(input_shape[1]), self.embed_filter_size
+        if n_nodes % g != 0:
+            raise IOError(f"Input shape {tuple(input_shape)} not compatible with the embedding filter size {g}")
+        self.embed = torch.nn.Conv1d(int(input_shape[-1]), self.embedding_size, g, stride=g, device=device)
+        with torch.no_grad():
+            _glorot_uniform_(self.embed.weight)
+            self.embed.bias.zero_()
+        if self.positional_encoding and self.pos_encoder.pos_embedding is None:
+            self.pos_encoder.build((1, n_nodes // g, self.embedding_size), device)
+
+    def forward(self, inputs):
+        x = inputs if isinstance(inputs, torch.Tensor) else torch.as_tensor(np.asarray(inputs), dtype=torch.float32)
+        g = self.embed_filter_size
+        if x.dim() == 3 and x.shape[1] % g != 0:
+            raise IOError(f"Input shape {tuple(x.shape)} not compatible with the embedding filter size {g}")
+        _require_hip(x)
+        if self.embed is None:
+            self.build(x.shape, x.device)
+        for m in self.mha_layers:  # (lazily built layers: parameters created before a .to(device) of the parent are moved by it)
+            if m.wqkv.weight.device != x.device:
+                m.to(x.device)
+        # kernel = stride = 4^p on NEST-ordered rows: the input is, without a copy, an (N M / 4^p) x (4^p Fin) matrix and the
+        # embedding one GEMM against the [4^p Fin, d] view of the Conv1D weights (HealpyPseudoConv.forward)
+        N, M, Fin = x.shape
+        w2 = self.embed.weight.permute(2, 1, 0).reshape(g * Fin, self.embedding_size)  # row (i, f) <- weight[o, f, i]
+        x = torch.addmm(self.embed.bias, x.reshape(N * (M // g), g * Fin), w2).reshape(N, M // g, self.embedding_size)
+        if self.positional_encoding:
+            x = self.pos_encoder(x)
+        for mha in self.mha_layers:
+            x = mha(x)
+        return x
+
+    call = forward
+
+
+__all__ = ["scaled_dot_product_attention", "scaled_dot_product_sparse_attention", "AddPositionEmbs", "MultiHeadAttention",
+           "Graph_Transformer", "Graph_ViT", "neighbour_tables"]

@@ -11,7 +11,7 @@ import torch
 
 from . import _native
 from .gnn_layers import Chebyshev, GCNN_ResidualLayer, Monomial
-from .gnn_transformers import Graph_Transformer
+from .gnn_transformers import Graph_Transformer, Graph_ViT
 
 
 def _as_tensor(x):
@@ -253,5 +253,23 @@ class Healpy_Transformer:
                                  activation=self.activation, layer_norm=self.layer_norm)
 
 
+class Healpy_ViT(Graph_ViT):
+    """``Graph_ViT`` under its HEALPix name (reference ``healpy_layers.py:381-414``, a subclass that adds nothing): a layer, not
+    a deferred spec -- it needs no graph.  The model builder counts it as a reduction by 2^p in nside, like ``HealpyPool``."""
+
+    def __init__(self, p, key_dim, num_heads, positional_encoding=True, n_layers=1, activation="relu", layer_norm=True):
+        """
+        :param p: the super-pixels are the 4^p NEST children of a pixel at nside / 2^p; p >= 1
+        :param key_dim: channels of key, query and value per head; the embedding has ``key_dim * num_heads`` channels
+        :param num_heads: number of heads
+        :param positional_encoding: add a learned position embedding after the initial embedding
+        :param n_layers: number of attention blocks
+        :param activation: activation of the blocks
+        :param layer_norm: layer norms in the blocks
+        """
+        super().__init__(p=p, key_dim=key_dim, num_heads=num_heads, positional_encoding=positional_encoding, n_layers=n_layers,
+                         activation=activation, layer_norm=layer_norm)
+
+
 __all__ = ["HealpyPool", "HealpyPseudoConv", "HealpyPseudoConv_Transpose", "HealpyChebyshev", "HealpyMonomial",
-           "Healpy_ResidualLayer", "Healpy_Transformer"]
+           "Healpy_ResidualLayer", "Healpy_Transformer", "Healpy_ViT"]

@@ -38,7 +38,7 @@ class HealpyGCNN(torch.nn.Sequential):
         nside_in = int(nside)
         reduction_fac = 1.0
         for layer in layers:
-            if isinstance(layer, (hp_nn.HealpyPool, hp_nn.HealpyPseudoConv)):
+            if isinstance(layer, (hp_nn.HealpyPool, hp_nn.HealpyPseudoConv, hp_nn.Healpy_ViT)):
                 reduction_fac *= 2 ** layer.p
             if isinstance(layer, hp_nn.HealpyPseudoConv_Transpose):
                 reduction_fac /= 2 ** layer.p
@@ -74,7 +74,7 @@ class HealpyGCNN(torch.nn.Sequential):
                 # the graph transformer attends along the edges: it gets the adjacency matrix of this resolution (:118-120)
                 A = healpix.healpix_graph(current_nside, current_indices, n_neighbors, graph_mode)
                 layers_use.append(layer._get_layer(A))
-            elif isinstance(layer, (hp_nn.HealpyPool, hp_nn.HealpyPseudoConv)):
+            elif isinstance(layer, (hp_nn.HealpyPool, hp_nn.HealpyPseudoConv, hp_nn.Healpy_ViT)):
                 new_nside = int(current_nside // 2 ** layer.p)
                 current_indices = self._transform_indices(current_nside, new_nside, current_indices)
                 current_nside = new_nside

@@ -433,6 +433,31 @@ int dsph_nbr_attention_backward(const float* q, const float* k, const float* v, 
                                 float* delta, float* dq, float* dk, float* dv, int64_t ld_grad, int64_t N, int64_t M, int32_t heads,
                                 int32_t depth, int device, void* hip_stream);
 
+/* Dense attention: every row attends to every row of its map (plan-free; csrc/dense_attention.hip).
+ * Replaces: gnn_transformers.scaled_dot_product_attention (reference gnn_transformers.py:14-51: matmul, softmax over a materialised
+ * (N, heads, M, M) tensor of logits, matmul) with mask = None -- what Graph_ViT (:248-356) and Healpy_ViT (healpy_layers.py:381-414)
+ * run on -- and the split_heads transposes around it (:189-196, :225-231).
+ *   q, k, v  device (N, M, heads * depth) fp32, channels last, rows `ld` floats apart (ld >= heads * depth: three views of one
+ *            (N, M, 3 heads depth) projection need no copy); head h is channels [h depth, (h + 1) depth)
+ *   out      device (N, M, heads * depth), contiguous:  out[n,i,h] = sum_j softmax_j(q_i,h . k_j,h / sqrt(depth)) v_j,h, j over [0, M)
+ *   lse      device (N, M, heads) or NULL:  log sum_j exp(q_i,h . k_j,h / sqrt(depth)), what the backward needs
+ * Flash style: key tiles stream through LDS, the softmax is the online, stable form, all products are exact-fp32 MFMA; no logit is
+ * written to global memory and nothing of size M^2 is allocated.
+ * Shapes: depth one of 4, 8, 16, 32, 64; heads >= 1 with heads * depth <= 256; M >= 1 (any value: tails are masked); ld a multiple
+ * of 4; q, k, v, out 16-byte aligned.  Anything else: DSPH_E_BADARG with the limit named in the message, before any device call;
+ * there is no slower path.
+ *
+ * The backward (the reference: TensorFlow's autodiff), from the forward's out and lse and the upstream gradient dout (contiguous,
+ * out's shape): dq, dk, dv with rows ld_grad floats apart.  `delta` is scratch of N * M * heads floats (the call writes
+ * delta[n,i,h] = dout_i,h . out_i,h there); the library allocates nothing.  No atomics: every element has one writer and a fixed
+ * order of summation, so two runs agree bit for bit.  Two launches (query blocks: delta and dq; key blocks: dk and dv; the
+ * probabilities are recomputed from lse).  Both calls only enqueue on `hip_stream`. */
+int dsph_dense_attention_forward(const float* q, const float* k, const float* v, int64_t ld, float* out, float* lse, int64_t N,
+                                 int64_t M, int32_t heads, int32_t depth, int device, void* hip_stream);
+int dsph_dense_attention_backward(const float* q, const float* k, const float* v, int64_t ld, const float* out, const float* lse,
+                                  const float* dout, float* delta, float* dq, float* dk, float* dv, int64_t ld_grad, int64_t N,
+                                  int64_t M, int32_t heads, int32_t depth, int device, void* hip_stream);
+
 const char* dsph_last_error(void);
 int dsph_abi_version(void);
 
