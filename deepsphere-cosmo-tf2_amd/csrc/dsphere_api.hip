@@ -738,4 +738,28 @@ int dsph_dense_attention_backward(const float* q, const float* k, const float* v
                                          (hipStream_t)hip_stream);
 }
 
+// one smoothing pass (csrc/ell_smooth.hip): every argument is checked here, before any launch
+int dsph_ell_smooth(const int32_t* cols, const float* vals, int64_t M, int32_t W, const float* x, float* y, int64_t N, int32_t C,
+                    const int32_t* reps, int32_t pass, const float* mask, int32_t mask_C, int device, void* hip_stream) {
+  if (!cols || !vals || !x || !y) { set_error("ell_smooth: NULL pointer (cols, vals, x and y are required)"); return DSPH_E_BADARG; }
+  if (N < 0 || M < 0) { set_error("ell_smooth: negative size (N %lld, M %lld)", (long long)N, (long long)M); return DSPH_E_BADARG; }
+  if (M > 0x7fffffffLL) { set_error("ell_smooth: M = %lld exceeds the int32 column indices of the table", (long long)M); return DSPH_E_BADARG; }
+  if (W <= 0) { set_error("ell_smooth: table width W = %d, must be at least 1", (int)W); return DSPH_E_BADARG; }
+  if (C <= 0) { set_error("ell_smooth: C = %d channels, must be at least 1", (int)C); return DSPH_E_BADARG; }
+  if (pass < 0) { set_error("ell_smooth: pass %d is negative", (int)pass); return DSPH_E_BADARG; }
+  if (mask && mask_C != 1 && mask_C != C) {
+    set_error("ell_smooth: mask_C = %d, the mask has 1 or C = %d columns", (int)mask_C, (int)C);
+    return DSPH_E_BADARG;
+  }
+  const double elems = (double)N * (double)M * (double)C;
+  if (elems >= 9.0e18 / 4) { set_error("ell_smooth: N * M * C = %.3g elements do not fit 64-bit byte offsets", elems); return DSPH_E_UNSUPPORTED; }
+  const uintptr_t bytes = (uintptr_t)(N * M * (int64_t)C) * sizeof(float), xa = reinterpret_cast<uintptr_t>(x), ya = reinterpret_cast<uintptr_t>(y);
+  if (xa < ya + bytes && ya < xa + bytes && (bytes > 0 || xa == ya)) {
+    set_error("ell_smooth: x and y overlap; a pass reads neighbours of every row and cannot run in place");
+    return DSPH_E_BADARG;
+  }
+  DeviceGuard guard(device);
+  return launch_ell_smooth(cols, vals, M, W, x, y, N, C, reps, pass, mask, mask_C, (hipStream_t)hip_stream);
+}
+
 }  // extern "C"

@@ -289,6 +289,11 @@ int launch_dense_attention_backward(const float* q, const float* k, const float*
                                     const float* dout, float* delta, float* dq, float* dk, float* dv, int64_t ld_grad, int64_t N,
                                     int64_t M, int32_t heads, int32_t depth, hipStream_t stream);
 
+// one pass of a wide-row ELL matrix over a map of few channels: Gaussian smoothing (ell_smooth.hip)
+int ell_smooth_group(int32_t W);  // lanes that share one row of a table of width W
+int launch_ell_smooth(const int32_t* cols, const float* vals, int64_t M, int32_t W, const float* x, float* y, int64_t N, int32_t C,
+                      const int32_t* reps, int32_t pass, const float* mask, int32_t mask_C, hipStream_t stream);
+
 // input-side strip kernel (cheb_istrip.hip): layers with at most 16 input channels, one wave per strip
 struct IStripLaunch : LaunchBase {
   unsigned char* wimg;       // workspace: istrip_wimg_bytes() per 32-column block

@@ -120,6 +120,8 @@ SIGNATURES = {
                                                      _c_vp]),
     "dsph_dense_attention_backward": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, _c_i64, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64,
                                                       _c_i64, _c_i64, _c_i32, _c_i32, ctypes.c_int, _c_vp]),
+    "dsph_ell_smooth": (ctypes.c_int, [_c_vp, _c_vp, _c_i64, _c_i32, _c_vp, _c_vp, _c_i64, _c_i32, _c_vp, _c_i32, _c_vp, _c_i32,
+                                        ctypes.c_int, _c_vp]),
 }
 
 
@@ -665,3 +667,35 @@ def dense_attention_backward(q, k, v, out, lse, dout, num_heads, grads=None):
                                              int(num_heads), int(d // num_heads), q.device.index, _stream_ptr(q.device))
     check(rc, "dsph_dense_attention_backward")
     return grads
+
+
+def ell_smooth(cols, vals, x, out=None, reps=None, pass_index=0, mask=None):
+    """One smoothing pass of the [M, W] table (int32 ``cols``, float32 ``vals``) over the (N, M, C) map ``x``
+    (``dsph_ell_smooth``): out[n, m, c] = sum_j vals[m, j] x[n, cols[m, j], c] for the channels with ``reps[c] > pass_index``
+    (all of them when ``reps`` is None; ``reps``: int32 [C] on the device), x[n, m, c] for the others, times ``mask`` ([M, 1] or
+    [M, C]) when one is given.  ``out`` must not share memory with ``x``; allocated when None."""
+    import torch
+
+    require_gpu()
+    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.is_contiguous()):
+        raise ValueError("ell_smooth works on a contiguous float32 (N, M, C) HIP tensor")
+    N, M, C = x.shape
+    _check_tables(cols, M, x.device, "cols")
+    if not (vals.dtype == torch.float32 and vals.is_contiguous() and vals.shape == cols.shape and vals.device == x.device):
+        raise ValueError("vals must be a contiguous float32 tensor of cols' shape on the maps' device")
+    if out is None:
+        out = torch.empty_like(x)
+    elif not (out.is_cuda and out.device == x.device and out.dtype == torch.float32 and out.is_contiguous() and out.shape == x.shape):
+        raise ValueError("out must be a contiguous float32 HIP tensor of x's shape on x's device")
+    if reps is not None and not (reps.dtype == torch.int32 and reps.is_contiguous() and reps.numel() == C and reps.device == x.device):
+        raise ValueError(f"reps must be a contiguous int32 tensor of C = {C} elements on the maps' device")
+    mask_C = 1
+    if mask is not None:
+        if not (mask.dtype == torch.float32 and mask.is_contiguous() and mask.dim() == 2 and mask.shape[0] == M
+                and mask.device == x.device):
+            raise ValueError(f"mask must be a contiguous float32 tensor [M = {M}, 1 or C] on the maps' device")
+        mask_C = int(mask.shape[1])
+    rc = lib().dsph_ell_smooth(_ptr(cols), _ptr(vals), int(M), int(cols.shape[1]), _ptr(x), _ptr(out), int(N), int(C), _ptr(reps),
+                               int(pass_index), _ptr(mask), mask_C, x.device.index, _stream_ptr(x.device))
+    check(rc, "dsph_ell_smooth")
+    return out

@@ -6,10 +6,13 @@ Chebyshev layer that a model builder turns into a real layer once it has compute
 Laplacian of the current resolution (``healpy_networks.py:110-137``).
 """
 
+import logging
+import os
+
 import numpy as np
 import torch
 
-from . import _native
+from . import _native, healpix
 from .gnn_layers import Chebyshev, GCNN_ResidualLayer, Monomial
 from .gnn_transformers import Graph_Transformer, Graph_ViT
 
@@ -271,5 +274,315 @@ class Healpy_ViT(Graph_ViT):
                          activation=activation, layer_norm=layer_norm)
 
 
+class _SmoothFunction(torch.autograd.Function):
+    """The passes of ``HealpySmoothing`` on the GPU (``dsph_ell_smooth``); the input gradient is the same passes with the
+    transposed table, on the upstream gradient times the mask."""
+
+    @staticmethod
+    def forward(ctx, x, layer):
+        ctx.layer = layer
+        cols, vals = layer._tables(x.device)
+        return layer._run_passes(x, cols, vals, layer._device_mask(x.device))
+
+    @staticmethod
+    def backward(ctx, dy):
+        layer = ctx.layer
+        mask = layer._device_mask(dy.device)
+        g = dy.contiguous() if mask is None else (dy * mask.unsqueeze(0)).contiguous()
+        colsT, valsT = layer._transposed_tables(dy.device)
+        return layer._run_passes(g, colsT, valsT, None), None
+
+
+class HealpySmoothing(torch.nn.Module):
+    """Smooths a HEALPix map with a Gaussian kernel (reference ``healpy_layers.py:510-853``).
+
+    Every pixel of the patch is replaced by the normalised, Gaussian-weighted sum of its ``max_neighbors`` nearest pixels, where
+    ``max_neighbors`` is the largest number of pixels any pixel has within ``n_sigma_support * sigma``.  The smoothing always uses
+    one base scale: per-channel scales are reached by applying the kernel ``ceil((s / s_min)^2)`` times (variances add).  The
+    kernel matrix is an ELL table of equal-length rows on the GPU (int32 ``cols``, float32 ``vals``, [n_indices, max_neighbors]);
+    one pass is one launch of ``dsph_ell_smooth`` over the (batch, pixel, channel) map in place of the reference's per-channel
+    sparse matmuls."""
+
+    def __init__(self, nside, indices, nest=True, mask=None, fwhm=None, sigma=None, n_sigma_support=3, arcmin=True,
+                 per_channel_repetitions=None, data_path=None, max_batch_size=None):
+        """
+        :param nside: nside of the input maps
+        :param indices: 1d array of the NEST pixel ids of the input maps
+        :param nest: must be True; RING ordering is not supported
+        :param mask: boolean or float array of shape (n_indices,), (n_indices, 1) or (n_indices, n_channels): the output is
+            multiplied by it.  None: the maps bleed into the zero padding
+        :param fwhm: FWHM of the kernel, a number or one per channel (then the smallest is the base scale)
+        :param sigma: the same as a standard deviation; exactly one of ``fwhm`` and ``sigma`` is given.  0 makes the layer the identity
+        :param n_sigma_support: radius of the kernel's support in sigmas
+        :param arcmin: ``fwhm`` / ``sigma`` are in arcmin (True) or radians
+        :param per_channel_repetitions: with a single scale, how often the kernel is applied to each channel
+        :param data_path: directory the kernel is loaded from if present and stored to otherwise (``ind_coo<label>.npy``,
+            ``val_coo<label>.npy``, the reference's files)
+        :param max_batch_size: the reference sizes its sparse-matmul splits by it; the number is computed (``n_matmul_splits``),
+            the kernel needs no split
+        """
+        super().__init__()
+        if not nest:
+            raise NotImplementedError("only NEST ordering is supported")
+        self.nside = nside
+        self.indices = indices
+        self.nest = nest
+        self.mask = mask
+
+        assert fwhm is not None or sigma is not None, "One of fwhm and sigma has to be specified"
+        assert fwhm is None or sigma is None, "Only one of fwhm and sigma can be specified"
+        self.fwhm = fwhm
+        self.sigma = sigma
+        self.n_sigma_support = n_sigma_support
+        self.arcmin = arcmin
+        self.per_channel_repetitions = per_channel_repetitions
+        self.data_path = data_path
+        self.max_batch_size = max_batch_size
+        self.n_channels = None
+        self._tables_T = None  # the transposed table: built by the first backward
+        self._dev = {}         # per-device copies of reps and mask
+
+        log = logging.getLogger(__name__)
+        scalar = lambda v: v is not None and np.ndim(v) == 0
+        if (scalar(self.fwhm) and self.fwhm == 0.0) or (scalar(self.sigma) and self.sigma == 0.0):
+            self.do_smoothing = False
+            log.info("The layer implements the identity, smoothing is disabled")
+            return
+        self.do_smoothing = True
+        if isinstance(self.fwhm, (list, tuple, np.ndarray)):
+            assert self.per_channel_repetitions is None, \
+                "per_channel_repetitions can't be specified when fwhm is a list, since it is then inferred"
+            self.fwhm = np.array(self.fwhm)
+            fwhm_min = np.min(self.fwhm)
+            # ceil to be conservative, squared because the variances of Gaussians add
+            self.per_channel_repetitions = np.ceil((self.fwhm / fwhm_min) ** 2).astype(int)
+            self.fwhm = fwhm_min
+        elif isinstance(self.sigma, (list, tuple, np.ndarray)):
+            assert self.per_channel_repetitions is None, \
+                "per_channel_repetitions can't be specified when sigma is a list, since it is then inferred"
+            self.sigma = np.array(self.sigma)
+            sigma_min = np.min(self.sigma)
+            self.per_channel_repetitions = np.ceil((self.sigma / sigma_min) ** 2).astype(int)
+            self.sigma = sigma_min
+        elif isinstance(self.per_channel_repetitions, (list, tuple)):
+            self.per_channel_repetitions = np.array(self.per_channel_repetitions)
+        if self.sigma is None:
+            self.sigma = self.fwhm / np.sqrt(8 * np.log(2))
+        if self.arcmin:
+            self.sigma_arcmin = self.sigma
+            self.sigma_rad = self._arcmin_to_rad(self.sigma_arcmin)
+        else:
+            self.sigma_rad = self.sigma
+            self.sigma_arcmin = self._rad_to_arcmin(self.sigma_rad)
+        self.fwhm_arcmin = self.sigma_arcmin * np.sqrt(8 * np.log(2))
+        self.n_indices = len(indices)
+        self.kernel_func = lambda r: np.exp(-0.5 / self.sigma_rad**2 * r**2)
+        self.file_label = f"-nside{self.nside}-sigma{self.sigma_arcmin:4.2f}-n_sigma{n_sigma_support}"
+        if self.per_channel_repetitions is not None:
+            log.info(f"Using the per channel smoothing repetitions {self.per_channel_repetitions}")
+
+        ind_coo = val_coo = None
+        if self.data_path is not None:
+            try:
+                ind_coo = np.load(os.path.join(self.data_path, f"ind_coo{self.file_label}.npy"))
+                val_coo = np.load(os.path.join(self.data_path, f"val_coo{self.file_label}.npy"))
+                log.info(f"Successfully loaded sparse kernel indices and values from {self.data_path}")
+            except FileNotFoundError:
+                ind_coo = val_coo = None
+        if ind_coo is None:
+            cols, vals = self._build_tree()
+            if self.data_path is not None:
+                self._store_kernel(cols, vals)
+        else:
+            cols, vals = self._table_from_coo(ind_coo, val_coo)
+            self.max_neighbors = int(cols.shape[1])
+        cols, vals = self._finish_table(cols, vals)
+        # non-persistent: the table is derived from the constructor's arguments (and cached by data_path), not learned
+        self.register_buffer("cols", torch.from_numpy(cols), persistent=False)
+        self.register_buffer("vals", torch.from_numpy(vals), persistent=False)
+
+    # ---- the kernel matrix ---------------------------------------------------------------------------------------------------
+    def _build_tree(self):
+        """-> (cols int32, vals float32) [n_indices, max_neighbors], every row ordered by distance, values not normalised.
+        The reference asks a haversine BallTree; here a k-d tree on the pixels' unit vectors, where a great-circle distance
+        theta is the chord 2 sin(theta / 2)."""
+        from scipy.spatial import cKDTree
+
+        vec = healpix.pix2vec(self.nside, np.asarray(self.indices, dtype=np.int64))
+        tree = cKDTree(vec)
+        workers = min(16, os.cpu_count() or 1)
+        radius = min(float(self.sigma_rad) * float(self.n_sigma_support), np.pi)
+        counts = tree.query_ball_point(vec, 2.0 * np.sin(0.5 * radius), return_length=True, workers=workers)
+        self.max_neighbors = int(np.max(counts))
+        W, M = self.max_neighbors, self.n_indices
+        cols = np.empty((M, W), dtype=np.int32)
+        vals = np.empty((M, W), dtype=np.float32)
+        step = max(1, (1 << 24) // W)  # rows per query: the float64 distances of a slice stay small
+        for a in range(0, M, step):
+            chord, ind = tree.query(vec[a:a + step], k=W, workers=workers)
+            chord, ind = chord.reshape(-1, W), ind.reshape(-1, W)
+            theta = 2.0 * np.arcsin(np.minimum(0.5 * chord, 1.0))
+            cols[a:a + step] = ind
+            vals[a:a + step] = self.kernel_func(theta).astype(np.float32)
+        return cols, vals
+
+    def _store_kernel(self, cols, vals):
+        """The reference's files: (nnz, 2) int64 (row, column) pairs and the float32 values before normalisation."""
+        M, W = cols.shape
+        ind_coo = np.empty((M * W, 2), dtype=np.int64)
+        ind_coo[:, 0] = np.repeat(np.arange(M, dtype=np.int64), W)
+        ind_coo[:, 1] = cols.reshape(-1)
+        os.makedirs(self.data_path, exist_ok=True)
+        np.save(os.path.join(self.data_path, f"ind_coo{self.file_label}.npy"), ind_coo)
+        np.save(os.path.join(self.data_path, f"val_coo{self.file_label}.npy"), vals.reshape(-1))
+
+    def _table_from_coo(self, ind_coo, val_coo):
+        """A stored kernel (entries in any order) as the [n_indices, W] table; every row must hold the same number of entries."""
+        M = self.n_indices
+        ind_coo, val_coo = np.asarray(ind_coo), np.asarray(val_coo, dtype=np.float32).reshape(-1)
+        if ind_coo.ndim != 2 or ind_coo.shape[1] != 2 or ind_coo.shape[0] != val_coo.shape[0]:
+            raise ValueError("the stored kernel must be (nnz, 2) indices and (nnz,) values")
+        per_row = np.bincount(ind_coo[:, 0], minlength=M)
+        W = int(per_row[0]) if M > 0 else 0
+        if per_row.shape[0] != M or W < 1 or np.any(per_row != W) or ind_coo[:, 1].min() < 0 or ind_coo[:, 1].max() >= M:
+            raise ValueError(f"the stored kernel does not fit a patch of {M} pixels with equally long rows")
+        order = np.argsort(ind_coo[:, 0], kind="stable")
+        return ind_coo[order, 1].astype(np.int32).reshape(M, W), val_coo[order].reshape(M, W)
+
+    @staticmethod
+    def _finish_table(cols, vals):
+        """Rows ordered by column (neighbouring lanes of the kernel then read neighbouring pixels) and normalised to sum 1:
+        float32 values, their sum taken in float64."""
+        M, W = cols.shape
+        out_c, out_v = np.empty_like(cols), np.empty_like(vals)
+        step = max(1, (1 << 24) // W)
+        for a in range(0, M, step):
+            c, v = cols[a:a + step], vals[a:a + step]
+            order = np.argsort(c, axis=1, kind="stable")
+            c, v = np.take_along_axis(c, order, axis=1), np.take_along_axis(v, order, axis=1)
+            out_c[a:a + step] = c
+            out_v[a:a + step] = (v / v.sum(axis=1, dtype=np.float64, keepdims=True)).astype(np.float32)
+        return out_c, out_v
+
+    def _tables(self, device):
+        if self.cols.device != device:
+            self.cols, self.vals = self.cols.to(device), self.vals.to(device)
+        return self.cols, self.vals
+
+    def _transposed_tables(self, device):
+        """The table of the transposed matrix, every row padded to the longest with (column = the row itself, value = 0)."""
+        if self._tables_T is None:
+            from scipy import sparse
+
+            cols, vals = self.cols.cpu().numpy(), self.vals.cpu().numpy()
+            M, W = cols.shape
+            K = sparse.csr_matrix((vals.reshape(-1), cols.reshape(-1), np.arange(0, M * W + 1, W)), shape=(M, M))
+            K.eliminate_zeros()  # (weights that underflowed: far pixels of the rows at a patch's edge)
+            KT = K.T.tocsr()
+            KT.sort_indices()
+            lens = np.diff(KT.indptr)
+            WT = max(int(lens.max()), 1)
+            colsT = np.repeat(np.arange(M, dtype=np.int32)[:, None], WT, axis=1)
+            valsT = np.zeros((M, WT), dtype=np.float32)
+            slot = np.arange(KT.nnz) - np.repeat(KT.indptr[:-1], lens)
+            rows = np.repeat(np.arange(M), lens)
+            colsT[rows, slot] = KT.indices
+            valsT[rows, slot] = KT.data
+            self._tables_T = (torch.from_numpy(colsT), torch.from_numpy(valsT))
+        if self._tables_T[0].device != device:
+            self._tables_T = tuple(t.to(device) for t in self._tables_T)
+        return self._tables_T
+
+    # ---- the layer -----------------------------------------------------------------------------------------------------------
+    def build(self, input_shape):
+        """Checks the input shape (n_batch, n_indices, n_channels) against the layer; brings the mask into shape."""
+        if not self.do_smoothing:
+            return
+        if self.max_batch_size is not None:
+            self.n_batch = self.max_batch_size
+        elif input_shape[0] is not None:
+            self.n_batch = int(input_shape[0])
+        else:
+            self.n_batch = None
+        assert self.n_indices == input_shape[1]
+        self.n_channels = int(input_shape[2])
+        if self.per_channel_repetitions is not None:
+            assert len(self.per_channel_repetitions) == self.n_channels, \
+                f"The list per_channel_repetitions has to have length {self.n_channels}"
+            assert self.per_channel_repetitions.dtype == int, "The list per_channel_repetitions has to contain integers only"
+        if self.mask is not None:
+            mask = torch.as_tensor(np.asarray(self.mask.detach().cpu() if isinstance(self.mask, torch.Tensor) else self.mask),
+                                   dtype=torch.float32)
+            if mask.dim() == 1:
+                mask = mask[None, :, None]
+            elif mask.dim() == 2:
+                mask = mask[None]
+            assert mask.dim() == 3 and mask.shape[0] == 1 and mask.shape[1] == self.n_indices and mask.shape[2] in (1, self.n_channels), \
+                "The mask has to have shape (1, n_indices, 1) or (1, n_indices, n_channels)"
+            self.mask = mask
+        # the reference splits its sparse matmul so that no piece passes TensorFlow's int32 limit; one launch here
+        self.n_matmul_splits = 1
+        if self.n_batch is not None:
+            nnz = self.n_indices * self.max_neighbors
+            while not (self.n_batch % self.n_matmul_splits == 0 and self.n_matmul_splits >= self.n_batch * nnz / 2**31):
+                self.n_matmul_splits += 1
+        self._dev = {}
+
+    def _device_mask(self, device):
+        """The mask as a contiguous [n_indices, 1 | n_channels] tensor on ``device`` (None without one)."""
+        if self.mask is None:
+            return None
+        key = ("mask", device)
+        if key not in self._dev:
+            self._dev[key] = self.mask[0].contiguous().to(device)
+        return self._dev[key]
+
+    def _device_reps(self, device):
+        if self.per_channel_repetitions is None:
+            return None
+        key = ("reps", device)
+        if key not in self._dev:
+            self._dev[key] = torch.as_tensor(np.asarray(self.per_channel_repetitions, dtype=np.int32), device=device)
+        return self._dev[key]
+
+    def _n_passes(self):
+        return 1 if self.per_channel_repetitions is None else int(np.max(self.per_channel_repetitions))
+
+    def _run_passes(self, x, cols, vals, mask):
+        """``_n_passes()`` launches, ping-pong between two buffers (a pass cannot run in place); the mask in the last."""
+        reps, n = self._device_reps(x.device), self._n_passes()
+        bufs = [torch.empty_like(x) for _ in range(min(n, 2))]
+        src = x
+        for p in range(n):
+            src = _native.ell_smooth(cols, vals, src, out=bufs[p % 2], reps=reps, pass_index=p, mask=mask if p == n - 1 else None)
+        return src
+
+    def forward(self, inputs):
+        """(n_batch, n_indices, n_channels) -> the smoothed maps, same shape."""
+        if not self.do_smoothing:
+            return inputs
+        x = _as_tensor(inputs)
+        if self.n_channels is None or x.shape[2] != self.n_channels:
+            self.build(tuple(x.shape))
+        assert x.dim() == 3 and x.shape[1] == self.n_indices
+        if not x.is_cuda:
+            raise RuntimeError("HealpySmoothing runs on a HIP device only; there is no CPU fallback")
+        x = x.to(torch.float32).contiguous()
+        if self._n_passes() == 0:  # every channel passes through
+            mask = self._device_mask(x.device)
+            return x if mask is None else x * mask.unsqueeze(0)
+        return _SmoothFunction.apply(x, self)
+
+    call = forward
+
+    @staticmethod
+    def _rad_to_arcmin(theta):
+        return theta / np.pi * (180 * 60)
+
+    @staticmethod
+    def _arcmin_to_rad(theta):
+        return theta * np.pi / (60 * 180)
+
+
 __all__ = ["HealpyPool", "HealpyPseudoConv", "HealpyPseudoConv_Transpose", "HealpyChebyshev", "HealpyMonomial",
-           "Healpy_ResidualLayer", "Healpy_Transformer", "Healpy_ViT"]
+           "Healpy_ResidualLayer", "Healpy_Transformer", "Healpy_ViT", "HealpySmoothing"]

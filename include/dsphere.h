@@ -458,6 +458,24 @@ int dsph_dense_attention_backward(const float* q, const float* k, const float* v
                                   const float* dout, float* delta, float* dq, float* dk, float* dv, int64_t ld_grad, int64_t N,
                                   int64_t M, int32_t heads, int32_t depth, int device, void* hip_stream);
 
+/* One pass of Gaussian smoothing: a wide-row ELL matrix over a map of few channels (plan-free; csrc/ell_smooth.hip).
+ * Replaces: one utils.split_sparse_dense_matmul per channel and repetition of healpy_layers.HealpySmoothing.call (reference
+ * healpy_layers.py:725-764) with the transposes, the unstack / stack and the mask multiply around them.
+ *   cols, vals  device int32 / fp32 [M][W], row-major: row m of the kernel matrix, every row W entries.  An entry outside [0, M)
+ *               counts as an empty slot.  The transposed table, padded with col = row, val = 0, gives the input gradient.
+ *   x, y        device (N, M, C) fp32, contiguous, the caller's layout; they must not overlap (a pass cannot run in place)
+ *   reps        device int32 [C] or NULL: channel c is smoothed if reps == NULL or reps[c] > pass, copied through otherwise
+ *   mask        device fp32 [M][mask_C] or NULL, mask_C = 1 or C: the stored value (smoothed or copied) is multiplied by
+ *               mask[m * mask_C + (mask_C == 1 ? 0 : c)]
+ *     y[n,m,c] = sum_j vals[m,j] * x[n, cols[m,j], c]
+ * A group of 16 (W <= 128) or 64 lanes owns a row and keeps its entries in registers over the batch and channel loops, so the table
+ * is read from memory once per call; sums are a fused multiply-add chain per lane and a fixed butterfly: no atomics, one writer,
+ * bitwise reproducible.  Any W >= 1 and C >= 1 (C = 1, 2 and multiples of 4 with 16-byte aligned maps take vector loads).
+ * Bad arguments (NULL, W <= 0, C <= 0, pass < 0, mask_C not 1 or C, x overlapping y): DSPH_E_BADARG before any launch.
+ * Only enqueues on `hip_stream`. */
+int dsph_ell_smooth(const int32_t* cols, const float* vals, int64_t M, int32_t W, const float* x, float* y, int64_t N, int32_t C,
+                    const int32_t* reps, int32_t pass, const float* mask, int32_t mask_C, int device, void* hip_stream);
+
 const char* dsph_last_error(void);
 int dsph_abi_version(void);
 
