@@ -122,6 +122,7 @@ SIGNATURES = {
                                                       _c_i64, _c_i64, _c_i32, _c_i32, ctypes.c_int, _c_vp]),
     "dsph_ell_smooth": (ctypes.c_int, [_c_vp, _c_vp, _c_i64, _c_i32, _c_vp, _c_vp, _c_i64, _c_i32, _c_vp, _c_i32, _c_vp, _c_i32,
                                         ctypes.c_int, _c_vp]),
+    "dsph_basis_change": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, _c_i32, _c_i32, _c_i32, _c_i32, ctypes.c_int, _c_vp]),
 }
 
 
@@ -698,4 +699,30 @@ def ell_smooth(cols, vals, x, out=None, reps=None, pass_index=0, mask=None):
     rc = lib().dsph_ell_smooth(_ptr(cols), _ptr(vals), int(M), int(cols.shape[1]), _ptr(x), _ptr(out), int(N), int(C), _ptr(reps),
                                int(pass_index), _ptr(mask), mask_C, x.device.index, _stream_ptr(x.device))
     check(rc, "dsph_ell_smooth")
+    return out
+
+
+def basis_change(w, coeff, transpose=False, out=None):
+    """The weights ``w`` [Fin * Kp, Fout] (row index f * Kp + i) in another polynomial basis (``dsph_basis_change``):
+    out[f*Kp + j, o] = sum_i coeff[i, j] w[f*Kp + i, o], or with ``transpose`` sum_i coeff[j, i] w[f*Kp + i, o] -- the map a weight
+    gradient takes back.  ``coeff``: float32 [Kp, Kp] on w's device.  ``out`` must not share memory with ``w``; allocated when
+    None.  One launch on the current stream, nothing else: it can be captured into a graph."""
+    import torch
+
+    require_gpu()
+    if not (isinstance(w, torch.Tensor) and w.is_cuda and w.dtype == torch.float32 and w.dim() == 2 and w.is_contiguous()):
+        raise ValueError("basis_change works on a contiguous float32 [Fin * Kp, Fout] HIP tensor")
+    if not (isinstance(coeff, torch.Tensor) and coeff.dtype == torch.float32 and coeff.dim() == 2 and coeff.is_contiguous()
+            and coeff.shape[0] == coeff.shape[1] and coeff.device == w.device):
+        raise ValueError("coeff must be a contiguous square float32 tensor [Kp, Kp] on the weights' device")
+    Kp = int(coeff.shape[0])
+    if Kp < 1 or w.shape[0] % Kp != 0:
+        raise ValueError(f"w has {w.shape[0]} rows, not a multiple of Kp = {Kp}")
+    if out is None:
+        out = torch.empty_like(w)
+    elif not (out.is_cuda and out.device == w.device and out.dtype == torch.float32 and out.is_contiguous() and out.shape == w.shape):
+        raise ValueError("out must be a contiguous float32 HIP tensor of w's shape on w's device")
+    rc = lib().dsph_basis_change(_ptr(w), _ptr(coeff), _ptr(out), int(w.shape[0] // Kp), int(w.shape[1]), Kp, 1 if transpose else 0,
+                                 w.device.index, _stream_ptr(w.device))
+    check(rc, "dsph_basis_change")
     return out

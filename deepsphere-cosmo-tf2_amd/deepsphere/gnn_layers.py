@@ -135,26 +135,32 @@ class _ChebConvFunction(torch.autograd.Function):
       rebuilt by ``dsph_cheb_planes`` and reduced against dy by ``dsph_cheb_wgrad`` (a split-over-pixels MFMA
       kernel with a fixed-order second stage: a library GEMM has no split-K for a 64 x 64 result
       reduced over 5e7 rows and took 150 ms here).
+
+    ``kernel`` is the layer's parameter; the kernels see ``layer._kernel_in(kernel)`` with ``layer._n_terms`` terms and their
+    weight gradient returns through ``layer._wgrad_out`` -- the identity and K for ``Chebyshev`` and ``Monomial``, the change of
+    basis (``dsph_basis_change``) and K + 1 for ``Bernstein``.
     """
 
     @staticmethod
     def forward(ctx, x, kernel, layer):
         plan = layer._get_plan()
         layer._set_f16_scale(plan, x)
+        kd = kernel.detach()
+        w = layer._kernel_in(kd)
         y, layer._workspace = _native.cheb_forward(
-            plan, x, kernel.detach(), None, layer.K, act=_native.ACT_NONE,
+            plan, x, w, None, layer._n_terms, act=_native.ACT_NONE,
             precision=layer._prec_code(), algo=_ALGOS[layer.algo], workspace=layer._workspace,
             basis=layer._basis)
         layer._wkey = None  # (training: the weights change between steps; the inference path re-packs once afterwards)
         ctx.layer = layer
-        ctx.save_for_backward(x, kernel)
+        ctx.save_for_backward(x, kernel if w is kd else w)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         layer = ctx.layer
-        x, kernel = ctx.saved_tensors
-        K = layer.K
+        x, kernel = ctx.saved_tensors  # (the weights the kernels saw)
+        K = layer._n_terms
         N, M, Fin = x.shape
         Fout = kernel.shape[1]
         dy = dy.contiguous()
@@ -171,6 +177,7 @@ class _ChebConvFunction(torch.autograd.Function):
             dk, layer._workspace_w = _native.cheb_backward_weights(
                 plan, x, dy, K, basis=layer._basis, algo=_ALGOS[layer.algo], workspace=getattr(layer, "_workspace_w", None),
                 precision=_PRECISIONS[resolve_wgrad_precision(layer.precision, N * M)])
+            dk = layer._wgrad_out(dk)
         return dx, dk, None
 
 
@@ -185,8 +192,27 @@ class Chebyshev(torch.nn.Module):
     _basis = _native.BASIS_CHEBYSHEV
     _scale = 0.75  # rescale_L(L, lmax, scale=0.75), gnn_layers.py:67
 
-    def _default_stddev(self, Fin):
+    def _default_stddev(self, Fin, Fout=None):
         return 1.0 / np.sqrt(Fin * (self.K + 0.5) / 2.0)  # gnn_layers.py:92
+
+    # The two things a subclass in another polynomial basis changes (``Bernstein``): how many terms the kernels run, and the
+    # weights they see.  ``Chebyshev`` and ``Monomial`` take the identity through all of them.
+    @property
+    def _n_terms(self):
+        """Terms of the recurrence the kernels run = rows of ``self.kernel`` per input channel."""
+        return self.K
+
+    def _kernel_in(self, kernel):
+        """Training: the (detached) parameter as the kernels see it."""
+        return kernel
+
+    def _wgrad_out(self, dk):
+        """Training: the kernels' weight gradient as the gradient of ``self.kernel``."""
+        return dk
+
+    def _kernel_image(self):
+        """Inference: ``(weights the kernels see, their version)``; the version keys the kept weight images of the steady state."""
+        return self.kernel.detach(), self.kernel._version
 
     def __init__(
         self,
@@ -272,14 +298,14 @@ class Chebyshev(torch.nn.Module):
         Fin = int(input_shape[-1])
         Fout = Fin if self.Fout is None else int(self.Fout)
         dev = self._resolve_device(None)
-        kernel = torch.empty((self.K * Fin, Fout), dtype=torch.float32)
+        kernel = torch.empty((self._n_terms * Fin, Fout), dtype=torch.float32)
         if self.initializer is None:
-            stddev = self._default_stddev(Fin)
+            stddev = self._default_stddev(Fin, Fout)
             torch.nn.init.trunc_normal_(kernel, mean=0.0, std=stddev, a=-2.0 * stddev, b=2.0 * stddev)
         else:
             res = self.initializer(kernel)
             if res is not None and res is not kernel:
-                kernel = torch.as_tensor(np.asarray(res), dtype=torch.float32).reshape(self.K * Fin, Fout).clone()
+                kernel = torch.as_tensor(np.asarray(res), dtype=torch.float32).reshape(self._n_terms * Fin, Fout).clone()
         self.kernel = torch.nn.Parameter(kernel.to(dev))
         if self.use_bias:
             # the reference creates the bias without an initializer (gnn_layers.py:104), i.e. the
@@ -333,16 +359,16 @@ class Chebyshev(torch.nn.Module):
 
     def _prec_code(self):
         """C-ABI code of the contraction arithmetic of this (built) layer: ``precision="auto"`` resolved with its Fin."""
-        return _PRECISIONS[resolve_precision(self.precision, self._Fin, self.K, self._chained())]
+        return _PRECISIONS[resolve_precision(self.precision, self._Fin, self._n_terms, self._chained())]
 
     def _chained(self, transposed=False):
         """Does the plan run this layer's forward (``transposed``: its input gradient, Fout -> Fin on the transposed plan) as the
         chain of <= 5-term passes?  None below K = 10 (no plan is asked: resolve_precision's rule needs nothing there)."""
-        if self.K <= 9 or getattr(self, "_plan", None) is None:
+        if self._n_terms <= 9 or getattr(self, "_plan", None) is None:
             return None
         if transposed:
-            return self._get_plan(transposed=True).uses_chain(self.Fout, self._Fin, self.K)
-        return self._plan.uses_chain(self._Fin, self.Fout, self.K)
+            return self._get_plan(transposed=True).uses_chain(self.Fout, self._Fin, self._n_terms)
+        return self._plan.uses_chain(self._Fin, self.Fout, self._n_terms)
 
     # -- forward --------------------------------------------------------------------------------
     def forward(self, input_tensor, training=False):
@@ -370,13 +396,13 @@ class Chebyshev(torch.nn.Module):
         wants_grad = torch.is_grad_enabled() and (
             self.kernel.requires_grad or input_tensor.requires_grad or (self.use_bias and self.bias.requires_grad))
         prepared = getattr(self, "_prepared", None)
-        if prepared is None or prepared[:2] != (self.K, Fin) or (wants_grad and not prepared[2]):
+        if prepared is None or prepared[:2] != (self._n_terms, Fin) or (wants_grad and not prepared[2]):
             # tile tables now, not inside the first kernel launch (allocation + synchronisation: dsph_plan_prepare_layer); with
             # autograd on also what the backward needs (DSPH_PREPARE_BACKWARD: the weight-gradient tables and the one-second host
             # pass that decides whether L~ is symmetric) -- otherwise the first training step would stall inside
             # dsph_cheb_backward_weights, mid-capture under a HIP graph
-            plan.prepare(self.K, Fin, Fout=self.Fout, backward=wants_grad)
-            self._prepared = (self.K, Fin, bool(wants_grad) or bool(prepared and prepared[:2] == (self.K, Fin) and prepared[2]))
+            plan.prepare(self._n_terms, Fin, Fout=self.Fout, backward=wants_grad)
+            self._prepared = (self._n_terms, Fin, bool(wants_grad) or bool(prepared and prepared[:2] == (self._n_terms, Fin) and prepared[2]))
         if wants_grad:
             # differentiable path: the linear part through the autograd function above, the epilogue
             # (BN -> bias -> activation, gnn_layers.py:152-159) as ordinary torch ops
@@ -394,8 +420,7 @@ class Chebyshev(torch.nn.Module):
             return y
         x = input_tensor.detach().to(device=self._device, dtype=torch.float32).contiguous()
         bias = self.bias.detach().reshape(-1).contiguous() if self.use_bias else None
-        kernel = self.kernel.detach()
-        kver = self.kernel._version
+        kernel, kver = self._kernel_image()
 
         # Batch norm with the moving statistics (the reference's default call, training=False) is a per-channel scale and
         # shift between the contraction and the bias (gnn_layers.py:152-159: BN -> bias -> activation; center=False,
@@ -417,7 +442,7 @@ class Chebyshev(torch.nn.Module):
             y = self._graph_forward(plan, x, bias if fuse_epilogue else None, act_code, wkey[:4], kernel)
         else:
             y, self._workspace = _native.cheb_forward(
-                plan, x, kernel, bias if fuse_epilogue else None, self.K, act=act_code,
+                plan, x, kernel, bias if fuse_epilogue else None, self._n_terms, act=act_code,
                 precision=self._prec_code(), algo=_ALGOS[self.algo], workspace=self._workspace,
                 basis=self._basis, keep_weights=getattr(self, "_wkey", None) == wkey,
             )
@@ -452,7 +477,7 @@ class Chebyshev(torch.nn.Module):
         if fold is None or fold["key"] != key:
             with torch.no_grad():
                 s = torch.rsqrt(bn.running_var.to(torch.float32) + bn.eps)
-                kf = self.kernel.detach() * s
+                kf = self._kernel_image()[0] * s
                 bf = -bn.running_mean.to(torch.float32) * s
                 if self.use_bias:
                     bf = bf + self.bias.detach().reshape(-1)
@@ -509,17 +534,17 @@ class Chebyshev(torch.nn.Module):
             return None
         plan = self._get_plan()
         Fout = int(self.kernel.shape[1])
-        if not _native.pool_fusable(plan, N, Fin, Fout, self.K, self._act_code):
+        if not _native.pool_fusable(plan, N, Fin, Fout, self._n_terms, self._act_code):
             return None
         x = input_tensor.detach().to(device=self._device, dtype=torch.float32).contiguous()
         bias = self.bias.detach().reshape(-1).contiguous() if self.use_bias else None
-        kernel, kver = self.kernel.detach(), self.kernel._version
+        kernel, kver = self._kernel_image()
         if self.use_bn:  # (inference: the moving statistics folded into weights and bias, as in forward)
             kernel, bias, kver = self._folded_bn()
         wkey = (kernel.data_ptr(), kver, self._prec_code(), (self.algo, N > 1),
                 None if self._workspace is None else self._workspace.data_ptr())
         y, self._workspace = _native.cheb_forward_pool(
-            plan, x, kernel, bias, self.K, pool_type=_native.POOL_MAX if pool_type == "MAX" else _native.POOL_AVG,
+            plan, x, kernel, bias, self._n_terms, pool_type=_native.POOL_MAX if pool_type == "MAX" else _native.POOL_AVG,
             act=self._act_code, precision=self._prec_code(), workspace=self._workspace,
             basis=self._basis, keep_weights=getattr(self, "_wkey", None) == wkey)
         self._wkey = wkey[:4] + (self._workspace.data_ptr() if self._workspace is not None else None,)
@@ -541,7 +566,7 @@ class Chebyshev(torch.nn.Module):
         g = getattr(self, "_graph", None)
         if g is None or g["key"] != key:
             kw = dict(act=act_code, precision=self._prec_code(), algo=_ALGOS[self.algo], basis=self._basis)
-            y, self._workspace = _native.cheb_forward(plan, x, kernel, bias, self.K, workspace=self._workspace, **kw)
+            y, self._workspace = _native.cheb_forward(plan, x, kernel, bias, self._n_terms, workspace=self._workspace, **kw)
             self._wkey = None
             graph = torch.cuda.CUDAGraph()
             out = torch.empty_like(y)
@@ -550,7 +575,7 @@ class Chebyshev(torch.nn.Module):
             side.wait_stream(cur)
             with torch.cuda.stream(side):
                 with torch.cuda.graph(graph, stream=side):
-                    _native.cheb_forward(plan, x, kernel, bias, self.K, workspace=self._workspace, out=out, keep_weights=True, **kw)
+                    _native.cheb_forward(plan, x, kernel, bias, self._n_terms, workspace=self._workspace, out=out, keep_weights=True, **kw)
             cur.wait_stream(side)
             g = self._graph = {"key": key, "graph": graph, "out": out, "hold": (x, kernel, bias, self._workspace)}
         g["graph"].replay()
@@ -615,8 +640,91 @@ class Monomial(Chebyshev):
     _basis = _native.BASIS_MONOMIAL
     _scale = 1.0
 
-    def _default_stddev(self, Fin):
+    def _default_stddev(self, Fin, Fout=None):
         return 0.1
+
+
+def bernstein_to_chebyshev(K):
+    """The (K+1) x (K+1) float64 matrix C whose row i holds the Chebyshev coefficients of plane i of the reference's
+    ``Bernstein.call`` (gnn_layers.py:543-554, read literally) as a polynomial in L~ = t:
+        plane i < K:  theta_i t^i (2 - t)^(K-i),   theta_i = binom(K, i) / 2^K
+        plane K:      theta_K theta_(K-1) t^(K-1) (2 - t)      (the loop over K - i runs zero times: plane K-1 is scaled again)
+    so that plane_i = sum_j C[i, j] T_j(t).  Every entry is an integer over a power of two: exact in float64."""
+    from math import comb
+    from numpy.polynomial import chebyshev as ncheb
+    from numpy.polynomial import polynomial as npoly
+
+    K = int(K)
+    if K < 1:
+        raise ValueError("K must be at least 1")
+    C = np.zeros((K + 1, K + 1))
+    for i in range(K + 1):
+        theta = comb(K, i) / 2.0**K
+        if i < K:
+            p = theta * npoly.polymul(npoly.polypow([0.0, 1.0], i), npoly.polypow([2.0, -1.0], K - i))
+        else:
+            p = theta * (comb(K, K - 1) / 2.0**K) * npoly.polymul(npoly.polypow([0.0, 1.0], K - 1), [2.0, -1.0])
+        c = ncheb.poly2cheb(p)
+        C[i, :c.shape[0]] = c
+    return C
+
+
+class Bernstein(Chebyshev):
+    """A graph convolutional layer using the Bernstein approximation (https://arxiv.org/abs/2106.10994):
+    y = act( BN( sum_f sum_{i=0..K} (B_i(L~) x[n, :, f])[m] * kernel[f*(K+1) + i, o] ) + bias[o] ), L~ as in ``Chebyshev``.
+
+    The B_i are what the reference's loop computes, not the paper's: B_i = binom(K,i)/2^K L~^i (2I - L~)^(K-i) for i < K, but
+    B_K = binom(K,K-1)/4^K L~^(K-1) (2I - L~), a multiple of B_(K-1) (``bernstein_to_chebyshev``), mirrored like the other quirks.
+
+    Mirror of the reference's ``gnn_layers.Bernstein`` (``gnn_layers.py:416-572``): ``K`` is the polynomial order, the kernel
+    has ``(K+1) * Fin`` rows, the default initialiser is a truncated normal of stddev sqrt(6 / (Fin + Fout)).  Each B_i is a
+    polynomial of degree <= K in the same L~ as ``Chebyshev``'s, so the layer IS a Chebyshev layer with K + 1 terms on weights
+    W'_j = sum_i C[i, j] W_i: it runs the same plan and kernels, and ``dsph_basis_change`` maps the weights in (once per weight
+    update at inference, once per step in training) and the weight gradient back out -- in place of the reference's K (K + 1)
+    sparse products per call."""
+
+    def _default_stddev(self, Fin, Fout=None):
+        return float(np.sqrt(6.0 / (Fin + (Fin if Fout is None else Fout))))  # gnn_layers.py:497
+
+    @property
+    def _n_terms(self):
+        return self.K + 1
+
+    def _coeff_on(self, device):
+        """C rounded once to fp32, on ``device``: a plain tensor, neither a parameter nor in ``state_dict``."""
+        c = getattr(self, "_coeff", None)
+        if c is None or c.device != device:
+            c = self._coeff = torch.as_tensor(bernstein_to_chebyshev(self.K).astype(np.float32)).to(device)
+        return c
+
+    def _kernel_in(self, kernel):
+        return _native.basis_change(kernel, self._coeff_on(kernel.device))
+
+    def _wgrad_out(self, dk):
+        return _native.basis_change(dk, self._coeff_on(dk.device), transpose=True)
+
+    def _kernel_image(self):
+        """The weights in the kernels' basis, in ONE buffer that is rewritten (one launch) only when ``self.kernel`` moves or
+        its version counter does, with a rebuild counter as its version (``self._basis_image["count"]``) -- as ``_folded_bn``
+        keeps its fold, which is computed from this image (the two maps commute: one mixes the rows of a channel, the other
+        scales columns).  In the steady state nothing is launched and the kept weight images stay valid."""
+        kernel = self.kernel.detach()
+        key = (kernel.data_ptr(), self.kernel._version)
+        img = getattr(self, "_basis_image", None)
+        if img is None or img["key"] != key or img["kernel"].device != kernel.device:
+            if img is None or img["kernel"].device != kernel.device or img["kernel"].shape != kernel.shape:
+                img = {"kernel": torch.empty_like(kernel), "count": 0 if img is None else img["count"]}
+            _native.basis_change(kernel, self._coeff_on(kernel.device), out=img["kernel"])
+            img["key"] = key
+            img["count"] += 1
+            self._basis_image = img
+        return img["kernel"], ("basis", img["count"])
+
+    def invalidate_weights(self):
+        super().invalidate_weights()
+        for name in ("_basis_image", "_bn_fold"):  # (both are keyed on the version counter a write through .data does not move)
+            if getattr(self, name, None) is not None:
+                getattr(self, name)["key"] = None
 
 
 class GCNN_ResidualLayer(torch.nn.Module):
@@ -711,4 +819,4 @@ class GCNN_ResidualLayer(torch.nn.Module):
     call = forward
 
 
-__all__ = ["Chebyshev", "Monomial", "GCNN_ResidualLayer"]
+__all__ = ["Chebyshev", "Monomial", "Bernstein", "GCNN_ResidualLayer"]

@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import _native, healpix
-from .gnn_layers import Chebyshev, GCNN_ResidualLayer, Monomial
+from .gnn_layers import Bernstein, Chebyshev, GCNN_ResidualLayer, Monomial
 from .gnn_transformers import Graph_Transformer, Graph_ViT
 
 
@@ -201,6 +201,14 @@ class HealpyMonomial(HealpyChebyshev):
     def _get_layer(self, L, n_matmul_splits=1):
         return Monomial(L=L, K=self.K, Fout=self.Fout, initializer=self.initializer, activation=self.activation,
                         use_bias=self.use_bias, use_bn=self.use_bn, n_matmul_splits=n_matmul_splits, **self.kwargs)
+
+
+class HealpyBernstein(HealpyChebyshev):
+    """Deferred spec of a Bernstein graph convolution of order ``K`` (reference ``healpy_layers.py:462``)."""
+
+    def _get_layer(self, L, n_matmul_splits=1):
+        return Bernstein(L=L, K=self.K, Fout=self.Fout, initializer=self.initializer, activation=self.activation,
+                         use_bias=self.use_bias, use_bn=self.use_bn, n_matmul_splits=n_matmul_splits, **self.kwargs)
 
 
 class Healpy_ResidualLayer:
@@ -584,5 +592,5 @@ class HealpySmoothing(torch.nn.Module):
         return theta * np.pi / (60 * 180)
 
 
-__all__ = ["HealpyPool", "HealpyPseudoConv", "HealpyPseudoConv_Transpose", "HealpyChebyshev", "HealpyMonomial",
+__all__ = ["HealpyPool", "HealpyPseudoConv", "HealpyPseudoConv_Transpose", "HealpyChebyshev", "HealpyMonomial", "HealpyBernstein",
            "Healpy_ResidualLayer", "Healpy_Transformer", "Healpy_ViT", "HealpySmoothing"]

@@ -476,6 +476,25 @@ int dsph_dense_attention_backward(const float* q, const float* k, const float* v
 int dsph_ell_smooth(const int32_t* cols, const float* vals, int64_t M, int32_t W, const float* x, float* y, int64_t N, int32_t C,
                     const int32_t* reps, int32_t pass, const float* mask, int32_t mask_C, int device, void* hip_stream);
 
+/* A change of polynomial basis on a layer's weights (plan-free; csrc/basis_change.hip): what makes gnn_layers.Bernstein a
+ * Chebyshev layer.  With row i of `coeff` the Chebyshev coefficients of the layer's i-th polynomial B_i,
+ *     sum_i B_i(L~) x W_i = sum_j T_j(L~) x W'_j,   W'_j = sum_i coeff[i][j] W_i,
+ * so the layer runs dsph_poly_forward / dsph_cheb_backward_weights with Kp terms on W' (transpose = 0), and the weight gradient
+ * those return goes back through the transposed map (transpose = 1).  Replaces the K (K + 1) sparse products per call of the
+ * reference's Bernstein.call (gnn_layers.py:543-554).
+ *   w, w_out  device fp32 [Fin * Kp, Fout], row index f * Kp + i, contiguous; they must not overlap
+ *   coeff     device fp32 [Kp, Kp], row-major, 1 <= Kp <= 64
+ *     w_out[f*Kp + j, o] = sum_i c(i,j) * w[f*Kp + i, o]
+ *       c(i,j) = coeff[i*Kp + j]   (transpose = 0: weights into the kernels' basis)
+ *       c(i,j) = coeff[j*Kp + i]   (transpose = 1: the weight gradient back out)
+ * Each output is one fp32 fma chain over i = 0 .. Kp - 1 in that order, one writer per element: bitwise reproducible.  Vector
+ * loads and stores of 4 (2) floats where Fout is a multiple of 4 (2) and the pointers are aligned, scalar ones otherwise.
+ * Bad arguments (NULL, Kp outside [1, 64], Fin or Fout < 1, transpose not 0 or 1, w_out overlapping w or coeff): DSPH_E_BADARG
+ * before any launch.  One launch; only enqueues on `hip_stream` (no allocation, no synchronisation, no copy: legal under
+ * stream capture). */
+int dsph_basis_change(const float* w, const float* coeff, float* w_out, int32_t Fin, int32_t Fout, int32_t Kp, int32_t transpose,
+                      int device, void* hip_stream);
+
 const char* dsph_last_error(void);
 int dsph_abi_version(void);
 
