@@ -123,6 +123,12 @@ SIGNATURES = {
     "dsph_ell_smooth": (ctypes.c_int, [_c_vp, _c_vp, _c_i64, _c_i32, _c_vp, _c_vp, _c_i64, _c_i32, _c_vp, _c_i32, _c_vp, _c_i32,
                                         ctypes.c_int, _c_vp]),
     "dsph_basis_change": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, _c_i32, _c_i32, _c_i32, _c_i32, ctypes.c_int, _c_vp]),
+    "dsph_bn_workspace_bytes": (ctypes.c_size_t, [_c_i64, _c_i32]),
+    "dsph_bn_stats": (ctypes.c_int, [_c_vp, _c_i64, _c_i32, ctypes.c_float, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, ctypes.c_float, _c_vp,
+                                      ctypes.c_size_t, ctypes.c_int, _c_vp]),
+    "dsph_bn_apply": (ctypes.c_int, [_c_vp, _c_vp, _c_i64, _c_i32, _c_vp, _c_vp, _c_vp, _c_vp, _c_i32, ctypes.c_int, _c_vp]),
+    "dsph_bn_backward": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i32, _c_i32, _c_vp,
+                                         ctypes.c_size_t, ctypes.c_int, _c_vp]),
 }
 
 
@@ -726,3 +732,104 @@ def basis_change(w, coeff, transpose=False, out=None):
                                  w.device.index, _stream_ptr(w.device))
     check(rc, "dsph_basis_change")
     return out
+
+
+def bn_workspace_bytes(rows, F):
+    """Bytes of scratch ``bn_stats`` and ``bn_backward`` need for a (rows, F) map (``dsph_bn_workspace_bytes``): a function of the
+    shape alone, 16 F (P + 1) with P = max(1, min(2048, rows, ceil(rows F / 8192)))."""
+    return int(lib().dsph_bn_workspace_bytes(int(rows), int(F)))
+
+
+def _bn_map(t, name):
+    import torch
+
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() >= 2 and t.is_contiguous()):
+        raise ValueError(f"{name} must be a contiguous float32 (..., F) HIP tensor")
+    F = int(t.shape[-1])
+    return t.numel() // max(F, 1), F
+
+
+def _bn_vec(t, F, device, name):
+    import torch
+
+    if t is None:
+        return
+    if not (isinstance(t, torch.Tensor) and t.device == device and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == F):
+        raise ValueError(f"{name} must be a contiguous float32 tensor of F = {F} elements on the map's device")
+
+
+def _bn_workspace(rows, F, device, workspace):
+    import torch
+
+    need = bn_workspace_bytes(rows, F)
+    if workspace is None or workspace.device != device or workspace.numel() * workspace.element_size() < need:
+        workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=device)
+    return workspace
+
+
+def bn_stats(y, eps, running_mean=None, running_var=None, momentum=0.0, workspace=None):
+    """Per-channel batch statistics of the channels-last map ``y`` (..., F) over all its rows (``dsph_bn_stats``): -> (stats,
+    workspace) with ``stats`` a float32 [5, F] tensor of mean, biased variance, rstd = 1 / sqrt(var + eps) and what the fp32 mean and
+    rstd rounded away of their float64 values (rows 3 and 4: ``bn_backward`` takes them).  ``running_mean`` /
+    ``running_var`` ([F], optional) are updated in place on the device the way ``torch.nn.BatchNorm1d`` does (unbiased variance).
+    Two launches on the current stream, nothing else."""
+    import torch
+
+    require_gpu()
+    rows, F = _bn_map(y, "y")
+    _bn_vec(running_mean, F, y.device, "running_mean")
+    _bn_vec(running_var, F, y.device, "running_var")
+    workspace = _bn_workspace(rows, F, y.device, workspace)
+    stats = torch.empty((5, F), dtype=torch.float32, device=y.device)
+    rc = lib().dsph_bn_stats(_ptr(y), rows, F, float(eps), _ptr(stats[0]), _ptr(stats[1]), _ptr(stats[2]), _ptr(stats[3]), _ptr(stats[4]), _ptr(running_mean),
+                             _ptr(running_var), float(momentum), _ptr(workspace), workspace.numel() * workspace.element_size(),
+                             y.device.index, _stream_ptr(y.device))
+    check(rc, "dsph_bn_stats")
+    return stats, workspace
+
+
+def bn_apply(y, mean, rstd, gamma=None, shift=None, act=ACT_NONE, out=None):
+    """out = act((y - mean) * rstd * gamma + shift) per channel of the channels-last map ``y`` (``dsph_bn_apply``); ``gamma`` /
+    ``shift`` None mean 1 / 0; ``out`` may be ``y`` itself (in place), allocated when None.  One launch on the current stream."""
+    import torch
+
+    require_gpu()
+    rows, F = _bn_map(y, "y")
+    for t, name in ((mean, "mean"), (rstd, "rstd"), (gamma, "gamma"), (shift, "shift")):
+        _bn_vec(t, F, y.device, name)
+    if mean is None or rstd is None:
+        raise ValueError("mean and rstd are required")
+    if out is None:
+        out = torch.empty_like(y)
+    elif out is not y and (_bn_map(out, "out") != (rows, F) or out.device != y.device):
+        raise ValueError("out must have y's shape and device")
+    rc = lib().dsph_bn_apply(_ptr(y), _ptr(out), rows, F, _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(shift), int(act), y.device.index,
+                             _stream_ptr(y.device))
+    check(rc, "dsph_bn_apply")
+    return out
+
+
+def bn_backward(y, z, dz, mean, rstd, gamma=None, act=ACT_NONE, want_dgamma=True, want_dshift=True, workspace=None, mean_lo=None,
+                rstd_lo=None):
+    """Gradients of ``bn_stats`` + ``bn_apply`` (``dsph_bn_backward``): -> (dy, dgamma or None, dshift or None, workspace) from the
+    forward's input ``y``, output ``z`` (None with ACT_NONE) and the upstream gradient ``dz``.  ``mean_lo`` / ``rstd_lo``: rows 3 and 4
+    of ``bn_stats``' result (the float64 statistics' low parts; None: the fp32 arrays as they are).  Deterministic; three launches."""
+    import torch
+
+    require_gpu()
+    rows, F = _bn_map(y, "y")
+    if _bn_map(dz, "dz") != (rows, F) or dz.device != y.device:
+        raise ValueError("dz must have y's shape and device")
+    if act != ACT_NONE and (z is None or _bn_map(z, "z") != (rows, F) or z.device != y.device):
+        raise ValueError("z (the forward's output, y's shape) is needed for the activation's derivative")
+    for t, name in ((mean, "mean"), (rstd, "rstd"), (gamma, "gamma"), (mean_lo, "mean_lo"), (rstd_lo, "rstd_lo")):
+        _bn_vec(t, F, y.device, name)
+    workspace = _bn_workspace(rows, F, y.device, workspace)
+    dy = torch.empty_like(y)
+    dgamma = torch.empty(F, dtype=torch.float32, device=y.device) if want_dgamma else None
+    dshift = torch.empty(F, dtype=torch.float32, device=y.device) if want_dshift else None
+    rc = lib().dsph_bn_backward(_ptr(y), _ptr(z if act != ACT_NONE else None), _ptr(dz), _ptr(mean), _ptr(rstd), _ptr(mean_lo), _ptr(rstd_lo), _ptr(gamma), _ptr(dy),
+                                _ptr(dgamma), _ptr(dshift), rows, F, int(act), _ptr(workspace),
+                                workspace.numel() * workspace.element_size(), y.device.index, _stream_ptr(y.device))
+    check(rc, "dsph_bn_backward")
+    return dy, dgamma, dshift, workspace

@@ -181,6 +181,62 @@ class _ChebConvFunction(torch.autograd.Function):
         return dx, dk, None
 
 
+def _bn_native_ok(bn, y):
+    """Do the batch-norm kernels (csrc/batch_norm.hip) cover this call?  A float32 map on a HIP device and a module with a fixed
+    momentum and float32 state; everything else (CPU tensors, other dtypes, ``momentum=None``: the cumulative average) keeps the
+    host framework's batch norm."""
+    if not (isinstance(y, torch.Tensor) and y.is_cuda and y.dtype == torch.float32 and y.dim() == 3 and y.shape[-1] >= 1):
+        return False
+    if bn.momentum is None:
+        return False
+    for t in (bn.running_mean, bn.running_var, bn.weight, bn.bias):
+        if t is not None and (t.dtype != torch.float32 or t.device != y.device):
+            return False
+    return True
+
+
+class _BatchNormActFunction(torch.autograd.Function):
+    """z = act(BN(y) * gamma + shift) with batch statistics on a channels-last map (N, M, F), as one differentiable op over
+    ``dsph_bn_stats`` / ``dsph_bn_apply`` / ``dsph_bn_backward``: three passes over the map forward and seven backward, no transposed
+    copy, no map-sized intermediate besides y and z.
+
+    ``gamma`` / ``shift``: tensors of F elements or None (1 / 0); ``bn``: the ``torch.nn.BatchNorm1d`` that holds the moving
+    statistics, eps and momentum -- updated as its own training-mode call would (unbiased variance, ``num_batches_tracked``);
+    ``act``: a ``_native.ACT_*`` code; ``inplace``: write z over y (autograd off: y is the convolution's fresh output)."""
+
+    @staticmethod
+    def forward(ctx, y, gamma, shift, bn, act, inplace):
+        if not y.is_contiguous():
+            y, inplace = y.contiguous(), False
+        N, M, F = y.shape
+        if N * M < 2:  # what torch.nn.functional.batch_norm raises in training
+            raise ValueError(f"Expected more than 1 value per channel when training, got input size {torch.Size([N, F, M])}")
+        g = None if gamma is None else gamma.detach().reshape(-1).contiguous()
+        b = None if shift is None else shift.detach().reshape(-1).contiguous()
+        stats, _ = _native.bn_stats(y, bn.eps, bn.running_mean, bn.running_var, bn.momentum)
+        z = _native.bn_apply(y, stats[0], stats[2], g, b, act, out=y if inplace else None)
+        if bn.num_batches_tracked is not None:
+            bn.num_batches_tracked.add_(1)  # (also what Chebyshev._folded_bn keys its cache on)
+        ctx.act = act
+        ctx.shapes = (None if gamma is None else gamma.shape, None if shift is None else shift.shape)
+        if inplace:
+            ctx.mark_dirty(y)
+        else:
+            ctx.save_for_backward(y, z if act != _native.ACT_NONE else None, stats, g)
+        return z
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dz):
+        y, z, stats, g = ctx.saved_tensors
+        gshape, sshape = ctx.shapes
+        dy, dgamma, dshift, _ = _native.bn_backward(
+            y, z, dz.contiguous(), stats[0], stats[2], g, ctx.act, mean_lo=stats[3], rstd_lo=stats[4],
+            want_dgamma=gshape is not None and ctx.needs_input_grad[1], want_dshift=sshape is not None and ctx.needs_input_grad[2])
+        return (dy, None if dgamma is None else dgamma.reshape(gshape), None if dshift is None else dshift.reshape(sshape),
+                None, None, None)
+
+
 class Chebyshev(torch.nn.Module):
     """A graph convolutional layer using the Chebyshev approximation.
 
@@ -405,9 +461,13 @@ class Chebyshev(torch.nn.Module):
             self._prepared = (self._n_terms, Fin, bool(wants_grad) or bool(prepared and prepared[:2] == (self._n_terms, Fin) and prepared[2]))
         if wants_grad:
             # differentiable path: the linear part through the autograd function above, the epilogue
-            # (BN -> bias -> activation, gnn_layers.py:152-159) as ordinary torch ops
+            # (BN -> bias -> activation, gnn_layers.py:152-159) through _BatchNormActFunction when it normalises with batch
+            # statistics on the GPU, as ordinary torch ops otherwise
             x = input_tensor.to(device=self._device, dtype=torch.float32).contiguous()
             y = _ChebConvFunction.apply(x, self.kernel, self)
+            if self.use_bn and (self.training if training is None else bool(training)) and _bn_native_ok(self.bn, y):
+                # batch statistics, the bias and the activation in the batch-norm kernels (csrc/batch_norm.hip)
+                return self._bn_act(y, self.bias if self.use_bias else None, inplace=False)
             if self.use_bn:
                 was_training = self.bn.training
                 self.bn.train(self.training if training is None else bool(training))
@@ -425,7 +485,8 @@ class Chebyshev(torch.nn.Module):
         # Batch norm with the moving statistics (the reference's default call, training=False) is a per-channel scale and
         # shift between the contraction and the bias (gnn_layers.py:152-159: BN -> bias -> activation; center=False,
         # scale=False): folded into the weights and the bias, the whole epilogue runs inside the kernel -- no transposed
-        # copies, no elementwise pass.  With batch statistics (training=True) the host framework normalises, as before.
+        # copies, no elementwise pass.  With batch statistics (training=True) the batch-norm kernels follow the convolution
+        # (csrc/batch_norm.hip: statistics, then normalisation + bias + activation in one pass, in place).
         bn_training = self.use_bn and (self.training if training is None else bool(training))
         if self.use_bn and not bn_training:
             kernel, bias, kver = self._folded_bn()
@@ -447,7 +508,9 @@ class Chebyshev(torch.nn.Module):
                 basis=self._basis, keep_weights=getattr(self, "_wkey", None) == wkey,
             )
             self._wkey = wkey[:4] + (self._workspace.data_ptr() if self._workspace is not None else None,)
-        if bn_training:  # BN -> bias -> activation, the reference's order (gnn_layers.py:152-159)
+        if bn_training and _bn_native_ok(self.bn, y):  # the same three in one pass over the fresh y, in place
+            y = self._bn_act(y, bias, inplace=True)
+        elif bn_training:  # BN -> bias -> activation, the reference's order (gnn_layers.py:152-159)
             was_training = self.bn.training
             self.bn.train(True)
             y = self.bn(y.transpose(1, 2)).transpose(1, 2).contiguous()
@@ -457,6 +520,15 @@ class Chebyshev(torch.nn.Module):
             if self.activation is not None:
                 y = self.activation(y)
         elif self.activation is not None and self._act_code is None:
+            y = self.activation(y)
+        return y
+
+    def _bn_act(self, y, shift, inplace):
+        """Training batch norm -> bias -> activation (gnn_layers.py:152-159) on the convolution's output through
+        ``_BatchNormActFunction``: the activation inside the kernel when it has a code, after it in the host framework otherwise."""
+        act = self._act_code if (self.activation is not None and self._act_code is not None) else _native.ACT_NONE
+        y = _BatchNormActFunction.apply(y, None, shift, self.bn, act, inplace)
+        if self.activation is not None and self._act_code is None:
             y = self.activation(y)
         return y
 
@@ -778,6 +850,16 @@ class GCNN_ResidualLayer(torch.nn.Module):
                 mod = torch.nn.LayerNorm(shape, eps=1e-3).to(x.device)
                 mod._axes = axes
             setattr(self, which, mod)
+        if self.norm_type == "batch_norm" and _bn_native_ok(mod, x):
+            # channels last as the map is: batch statistics through the batch-norm kernels with the module's scale and shift
+            # (training), the elementwise kernel alone on the moving statistics (inference without autograd)
+            if self.training if training is None else bool(training):
+                return _BatchNormActFunction.apply(x, mod.weight, mod.bias, mod, _native.ACT_NONE, False)
+            if mod.running_mean is not None and not (torch.is_grad_enabled() and (
+                    x.requires_grad or any(p is not None and p.requires_grad for p in (mod.weight, mod.bias)))):
+                w = None if mod.weight is None else mod.weight.detach().contiguous()
+                b = None if mod.bias is None else mod.bias.detach().contiguous()
+                return _native.bn_apply(x.contiguous(), mod.running_mean, torch.rsqrt(mod.running_var + mod.eps), w, b)
         if self.norm_type == "batch_norm":
             was = mod.training
             mod.train(self.training if training is None else bool(training))

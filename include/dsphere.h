@@ -248,7 +248,7 @@ size_t dsph_workspace_bytes(const dsph_plan* plan, int64_t N, int32_t Fin, int32
  * reference.  With the moving statistics (inference; center=False, scale=False) it is a per-channel scale and shift,
  * s[o] = 1 / sqrt(var[o] + eps): the caller passes w[:, o] * s[o] as `w` and bias[o] - mean[o] * s[o] as `bias` and gets
  * act(BN(conv) + bias) from this one call (deepsphere/gnn_layers.py does, keyed on the versions of the statistics); with
- * batch statistics (training) a layer calls this with bias=NULL, act=NONE and finishes in the host framework.
+ * batch statistics (training) a layer calls this with bias=NULL, act=NONE and finishes with dsph_bn_stats and dsph_bn_apply.
  * Asynchronous on `hip_stream` (a hipStream_t; NULL = the default stream).  (Part of a large fused forward may run on a
  * stream the plan owns, forked from and joined back into `hip_stream` inside the call: invisible to the caller, capturable.) */
 int dsph_cheb_forward(const dsph_plan* plan, const float* x, const float* w, const float* bias,
@@ -494,6 +494,53 @@ int dsph_ell_smooth(const int32_t* cols, const float* vals, int64_t M, int32_t W
  * stream capture). */
 int dsph_basis_change(const float* w, const float* coeff, float* w_out, int32_t Fin, int32_t Fout, int32_t Kp, int32_t transpose,
                       int device, void* hip_stream);
+
+/* Batch normalisation with batch statistics over a channels-last map (plan-free; csrc/batch_norm.hip), the epilogue fused:
+ *     z[r, c] = act((y[r, c] - mean[c]) * rstd[c] * gamma[c] + shift[c]),   y, z device (rows, F) fp32, contiguous, rows = N * M
+ * Replaces, in a training step: the Keras BatchNormalization between the contraction and the bias (reference gnn_layers.py:152-159)
+ * and inside GCNN_ResidualLayer.call (:395-405) with the bias add and the activation behind it, and their gradients from
+ * TensorFlow's autodiff.  Three passes over the map forward (statistics: one read; apply: one read, one write), seven backward.
+ * Any F >= 1 (there is no cap on F; 16-byte accesses where F % 4 == 0 and the maps are 16-byte aligned, 8-byte ones for even F
+ * and 8-byte alignment, else scalar); rows up to 2^40 and rows * F up to 2^62 (DSPH_E_UNSUPPORTED beyond); every offset is 64-bit.
+ * Bad arguments (a required pointer NULL, rows < 1, F < 1, an unknown activation, eps <= 0, momentum outside [0, 1], rows = 1
+ * together with running_var): DSPH_E_BADARG with the entry point named in the message, before any HIP call.  Every call only
+ * enqueues on `hip_stream`: no allocation, no synchronisation, no atomics -- legal under stream capture, and two calls on the
+ * same input give the same bits.
+ *
+ * Workspace of the two reducing calls, caller-owned, 8-byte aligned, a function of the shape alone:
+ *     P = max(1, min(2048, rows, ceil(rows * F / 8192)))  partial results per channel,   bytes = 16 * F * (P + 1)
+ * (P workgroups each reduce a contiguous range of rows to one partial per channel; one workgroup per channel merges the P
+ * partials in a fixed order in float64.)
+ *
+ * Statistics: mean[c], var[c] (biased: sum (y - mean)^2 / rows) and rstd[c] = 1 / sqrt(var[c] + eps), device [F] each, all three
+ * required.  Partial (count, mean, M2) triples merged by Chan's formula in float64, never E[y^2] - E[y]^2: a channel whose mean is
+ * large against its spread keeps its digits.  mean_lo, rstd_lo: device [F] or NULL -- what the fp32 mean and rstd rounded away
+ * (mean = mean[c] + mean_lo[c] to 2^-48), for dsph_bn_backward.  running_mean / running_var: device [F] or NULL; when given they are updated on the
+ * device as torch.nn.BatchNorm1d does, running = (1 - momentum) * running + momentum * batch, the variance with the UNBIASED
+ * batch variance var * rows / (rows - 1) (Keras uses the biased one).  Two launches. */
+size_t dsph_bn_workspace_bytes(int64_t rows, int32_t F);
+int dsph_bn_stats(const float* y, int64_t rows, int32_t F, float eps, float* mean, float* var, float* rstd, float* mean_lo, float* rstd_lo,
+                  float* running_mean, float* running_var, float momentum, void* workspace, size_t workspace_bytes, int device, void* hip_stream);
+/* The elementwise pass alone.  mean, rstd: device [F], plain arrays -- the batch statistics of the call above, or the moving mean
+ * and 1 / sqrt(running_var + eps) for the inference form.  gamma, shift: device [F] or NULL (1 and 0).  act: a DSPH_ACT_* code.
+ * z may be y (in place); any other overlap of the two is not allowed.  One launch. */
+int dsph_bn_apply(const float* y, float* z, int64_t rows, int32_t F, const float* mean, const float* rstd, const float* gamma,
+                  const float* shift, int32_t act, int device, void* hip_stream);
+/* The backward of the two calls together, from the forward's input y, its output z and the upstream gradient dz (rows, F):
+ *     g = dz * act'(z)      (from the OUTPUT: relu z > 0, elu z > 0 ? 1 : z + 1, sigmoid z (1 - z), tanh 1 - z^2; with DSPH_ACT_NONE z
+ *                            is not read and may be NULL)
+ *     x^ = (y - mean) * rstd                                  (recomputed)
+ *     dshift[c] = s1 = sum_r g,   dgamma[c] = s2 = sum_r g x^   (device [F] or NULL: not wanted)
+ *     dy = gamma * rstd * (g - s1 / rows - x^ * s2 / rows)      (device (rows, F); must not overlap y, z or dz)
+ * mean_lo, rstd_lo: device [F] or NULL (0): the low parts from dsph_bn_stats.  x^, the sums and dy are evaluated in float64 on mean +
+ * mean_lo and rstd + rstd_lo: with few rows dy is a cancellation (two rows, eps = 1e-5: down to 4e-5 of g) that one fp32 rounding of
+ * either array would swamp; without the low parts the result is only as good as the fp32 arrays.
+ * gamma: device [F] or NULL (1).  Three launches: the reduction of s1 and s2 by the scheme of the statistics (partials, then the
+ * fixed-order merge), then one elementwise pass.  Workspace as above. */
+int dsph_bn_backward(const float* y, const float* z, const float* dz, const float* mean, const float* rstd, const float* mean_lo,
+                     const float* rstd_lo, const float* gamma, float* dy,
+                     float* dgamma, float* dshift, int64_t rows, int32_t F, int32_t act, void* workspace, size_t workspace_bytes, int device,
+                     void* hip_stream);
 
 const char* dsph_last_error(void);
 int dsph_abi_version(void);
