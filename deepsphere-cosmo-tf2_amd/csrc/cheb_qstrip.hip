@@ -24,20 +24,8 @@ __global__ __launch_bounds__(256) void qstrip_wprep_kernel(const float* __restri
   const int j = role == 0 ? K - 1 - lev : 1 - lev;
   const bool have = role == 0 || lev < 2;
   float sc = qs_wsign(cheb != 0, j) * ((cheb != 0 && j == 0) ? 2.f : 1.f);
-  if (f16) {  // (every block finds the same maximum: 20,480 values)
-    __shared__ float smax[256];
-    float m = 0.f;
-    for (int e = threadIdx.x; e < Fin * K * Fout; e += 256) m = fmaxf(m, fabsf(w[(int64_t)(e / Fout) * ld + e % Fout]));
-    smax[threadIdx.x] = m;
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-      if ((int)threadIdx.x < st) smax[threadIdx.x] = fmaxf(smax[threadIdx.x], smax[threadIdx.x + st]);
-      __syncthreads();
-    }
-    int ex = 0;
-    const float mx = smax[0];
-    float pw = 1.f;
-    if (mx > 0.f && mx < 3.0e38f) { (void)frexpf(mx, &ex); pw = ldexpf(1.f, 12 - ex); }  // mx = f 2^ex, f in [0.5, 1): mx pw in [2048, 4096)
+  if (f16) {
+    const float pw = qt_wimg_pow2(w, Fin * K, Fout, ld);
     sc *= pw;
     if (blk == 0 && threadIdx.x == 0) *reinterpret_cast<float*>(out + (size_t)2 * 4 * 3 * 2 * 2 * QS_FRAG) = 1.f / pw;
   }
@@ -46,33 +34,19 @@ __global__ __launch_bounds__(256) void qstrip_wprep_kernel(const float* __restri
     const int l = e >> 3, i = e & 7;
     const int ch = 32 * kb + 8 * (l >> 4) + i, col = 16 * oq + (l & 15);
     const float v = (have && ch < Fin && col < Fout) ? sc * w[((int64_t)ch * K + j) * ld + col] : 0.f;
-    if (f16) {
-      const _Float16 hi = (_Float16)v;
-      const _Float16 lo = (_Float16)(v - (float)hi);
-      reinterpret_cast<_Float16*>(base)[l * 8 + i] = hi;
-      reinterpret_cast<_Float16*>(base + QS_FRAG)[l * 8 + i] = lo;
-    } else {
-      const __bf16 hi = (__bf16)v;
-      const __bf16 lo = (__bf16)(v - (float)hi);
-      reinterpret_cast<__bf16*>(base)[l * 8 + i] = hi;
-      reinterpret_cast<__bf16*>(base + QS_FRAG)[l * 8 + i] = lo;
-    }
+    qt_wimg_put(base, l * 8 + i, v, f16 != 0);
   }
 }
 
 bool qstrip_shape_ok(int32_t Fin, int32_t Fout, int32_t K) { return K == 5 && Fin == 64 && Fout == 64; }
 
-// How the kernel's workgroups share the work (cheb_qstrip_kernel.h): G workgroups (a multiple of 8: the kernel deals XCD by
-// XCD; one per CU, fewer when a workgroup would get under 64 rows), the per-map tape of `tape_rows` rows cut into P pieces, w
-// workgroups per piece taking every w-th map.  w = N (one map each, in step on the same rows of L~) when the batch fits;
-// otherwise the w in {1, 2, 4, ...} with the shortest busiest workgroup.  Returns that workgroup's steps: its rows plus nine
-// run-in steps per run of rows, every run rounded up to whole triples of steps (the step body is unrolled three times).
-int64_t qstrip_split(int num_cu, int64_t tape_rows, int64_t N, int64_t mean_height, int* grid, int* pieces, int* wg_per_piece) {
+// The split rule of the quad-strip kernels (dsphere_common.h)
+int64_t qtape_split(int num_cu, int64_t tape_rows, int64_t N, int64_t mean_height, int run_in, int* grid, int* pieces, int* wg_per_piece) {
   const int g = (int)std::max<int64_t>(8, std::min<int64_t>(num_cu / 8 * 8, tape_rows * N / 64 / 8 * 8));
   auto span_of = [&](int64_t w) {
     const int64_t P = std::max<int64_t>(1, g / w), share = (tape_rows + P - 1) / P, maps = (N + w - 1) / w;
     const int64_t runs = share / std::max<int64_t>(1, mean_height) + 2;
-    return (share + runs * (2 * QS_D + 1 + 1)) * maps;
+    return (share + runs * (run_in + 1)) * maps;
   };
   int64_t best_w = 1, best = -1;
   if (N <= g) { best_w = N; best = span_of(N); }
@@ -86,6 +60,9 @@ int64_t qstrip_split(int num_cu, int64_t tape_rows, int64_t N, int64_t mean_heig
   if (wg_per_piece) *wg_per_piece = (int)best_w;
   return best;
 }
+int64_t qstrip_split(int num_cu, int64_t tape_rows, int64_t N, int64_t mean_height, int* grid, int* pieces, int* wg_per_piece) {
+  return qtape_split(num_cu, tape_rows, N, mean_height, QS_RUNIN, grid, pieces, wg_per_piece);
+}
 
 size_t qstrip_wimg_bytes() { return (size_t)2 * 4 * 3 * 2 * 2 * QS_FRAG + 256; }  // 96 KiB + the f16 image's factor
 
@@ -96,27 +73,9 @@ int launch_cheb_qstrip(const QStripLaunch& s, hipStream_t stream) {
     DSPH_HIP(hipGetLastError());
   }
   QStripArgs a;
-  a.x = s.x;
-  a.bias = s.bias;
-  a.y = s.y;
-  a.wimg = s.wimg;
-  a.gvals8 = s.gvals8;
-  a.gdiag = s.gdiag;
-  a.strips = s.strips;
-  a.tab = s.tab;
-  a.prefix = s.prefix;
-  a.x_rows = s.x_rows;
-  a.y_rows = s.y_rows;
-  a.nstrips = s.nstrips;
-  a.N = (int)s.N;
   a.Fin = s.Fin;
   a.Fout = s.Fout;
-  a.ld = s.ld;
-  a.act = s.act;
-  a.xsc = s.f16 ? ldexpf(1.f, s.f16_xexp) : 1.f;
-  a.xsc_inv = s.f16 ? ldexpf(1.f, -s.f16_xexp) : 1.f;
-  int grid;
-  (void)qstrip_split(s.num_cu, s.tape_rows, s.N, s.tape_rows / std::max(1, s.nstrips), &grid, &a.pieces, &a.wg_per_piece);
+  const int grid = qtape_forward_args(a, s, QS_RUNIN);
   void (*kern)(QStripArgs) = s.f16 ? (s.cheb ? cheb_qstrip5_kernel<true, true> : cheb_qstrip5_kernel<false, true>)
                                    : (s.cheb ? cheb_qstrip5_kernel<true, false> : cheb_qstrip5_kernel<false, false>);
 #ifdef DSPH_QS_STAMPS

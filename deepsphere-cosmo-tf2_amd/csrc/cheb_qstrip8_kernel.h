@@ -3,7 +3,8 @@
 // The reference's loop is order-agnostic (gnn_layers.py:140-143); until this round every K > 5 forward ran on the breadth-first
 // tile kernel with a 7-ring halo (16 x 16 tiles: 3.5 x the stencil work, LDS-bound: 21 ms at configs[3], four rounds flat).
 // This is cheb_qstrip_kernel.h's form -- Clenshaw's recurrence on the MFMA accumulators, y = sum_k T_k(L~)(x W_k), 64-column
-// strips streamed along y, four pixels per lane, rows through the rectangle's table of tile bases -- with the seven stencil
+// strips streamed along y, four pixels per lane, rows through the rectangle's table of tile bases (strips, tape, tables, the
+// hi | lo split and the ring row of L~: cheb_qtape.h; MFMA and stencil units: cheb_qstrip_kernel.h) -- with the seven stencil
 // levels dealt to THREE roles instead of two:
 //
 //   top    levels 7, 6, 5   the H role of the K = 5 kernel as it stands (three levels, nothing comes in);
@@ -74,8 +75,7 @@ __global__ __launch_bounds__(VARIANT == 1 ? 512 : Q8_THREADS, 1) void cheb_qstri
   constexpr int RINGB = RING * ROWB;             // 88 KiB
   constexpr int HAND1 = 2 * 4 * QS_FRAG;         // 8 KiB per (boundary, quarter): [new row | dying row][tile]
   constexpr int HANDB = 2 * 2 * HAND1;           // 32 KiB
-  constexpr int CROWB = 2304;                    // one ring row of L~: [9: the diagonal, directions 0..7][p][tile] floats
-  constexpr int CRINGB = CRING * CROWB;
+  constexpr int CRINGB = CRING * QS_CROWB;       // 22.5 KiB: the ring of rows of L~
   constexpr int LDS_HAND = RINGB, LDS_C = RINGB + HANDB, LDS_FLAG = LDS_C + CRINGB;
   __shared__ __attribute__((aligned(16))) unsigned char smem[LDS_FLAG + 64];
 
@@ -88,57 +88,23 @@ __global__ __launch_bounds__(VARIANT == 1 ? 512 : Q8_THREADS, 1) void cheb_qstri
   // hand-over b (0: top -> middle, 1: middle -> bottom) of this quarter, and its counter
   auto hand_at = [&](int b) __attribute__((always_inline)) -> unsigned { return (unsigned)LDS_HAND + (unsigned)(b * 2 + oq) * HAND1 + lane16; };
   auto flag_at = [&](int b) __attribute__((always_inline)) -> unsigned { return (unsigned)LDS_FLAG + 4u * (unsigned)(b * 2 + oq); };
-  auto flag_set = [&](unsigned addr, int v) __attribute__((always_inline)) { asm volatile("ds_write_b32 %0, %1" : : "v"(addr), "v"(v) : "memory"); };
-  auto flag_get = [&](unsigned addr) __attribute__((always_inline)) -> int {
-    int v;
-    asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(addr) : "memory");
-    return v;
-  };
   for (int i = tid; i < (LDS_FLAG + 64) / 16; i += NTHREADS) reinterpret_cast<qs_f4*>(smem)[i] = qs_f4{0.f, 0.f, 0.f, 0.f};
 
-  const int G = gridDim.x, ord = (blockIdx.x & 7) * (G >> 3) + (blockIdx.x >> 3);
-  const int piece = ord / a.wg_per_piece, map0 = ord - piece * a.wg_per_piece;
-  if (piece >= a.pieces) return;
-  const int64_t tape = (int64_t)a.prefix[a.nstrips];
-  const int64_t tape_begin = tape * piece / a.pieces, tape_end = tape * (piece + 1) / a.pieces;
+  // this workgroup's piece of the tape and its maps
+  const QTapePiece wg = qt_piece(a.wg_per_piece);
+  if (wg.piece >= a.pieces) return;  // (before the first barrier: the whole workgroup leaves)
+  const QTapeRange tape = qt_tape_range(a.prefix, a.nstrips, wg.piece, a.pieces);
   auto locate = [&](int64_t r, int64_t r_end, QStrip& st) __attribute__((always_inline)) -> int {
-    int lo = 0, hi = a.nstrips;
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if ((int64_t)a.prefix[mid] <= r) lo = mid; else hi = mid;
-    }
-    {
-      const QStrip g = a.strips[lo];
-#define QS_U(f) st.f = __builtin_amdgcn_readfirstlane(g.f)
-      QS_U(x0); QS_U(w); QS_U(xs); QS_U(y0); QS_U(y1); QS_U(xlo); QS_U(xhi); QS_U(ylo); QS_U(yhi); QS_U(tab); QS_U(tws);
-#undef QS_U
-    }
-    const int h = st.y1 - st.y0;
-    const int off = (int)(r - (int64_t)a.prefix[lo]);
-    const int len = (int)(((int64_t)(h - off) < r_end - r) ? (int64_t)(h - off) : r_end - r);
-    st.y0 += off;
-    st.y1 = st.y0 + len;
-    return len;
+    return qt_locate(a.prefix, a.strips, a.nstrips, r, r_end, st);
   };
   const unsigned xrowb = 32u * 4u, yrowb = (unsigned)a.ld * 4u;
-  auto step_barrier = [&]() __attribute__((always_inline)) { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
 
-  // ---- rows through the rectangle's table of tile bases (cheb_qstrip_kernel.h) ------------------------------------------------
-  typedef int qs_i4 __attribute__((ext_vector_type(4)));
+  // ---- rows through the rectangle's table of tile bases (cheb_qtape.h) ---------------------------------------------------------
   auto tab_lane = [&](const QStrip& st, unsigned ci, int yrow) __attribute__((always_inline)) -> unsigned {
-    const int yc = min(max(yrow, st.ylo), st.yhi);
-    const int32_t* trow = a.tab + __builtin_amdgcn_readfirstlane(st.tab + (yc >> 4) * st.tws + (max(st.xs, st.xlo) >> 4));
-    qs_i4 b;
-    int b4;
-    asm volatile("s_load_dwordx4 %0, %2, 0x0\n\ts_load_dword %1, %2, 0x10\n\ts_waitcnt lgkmcnt(0)" : "=&s"(b), "=&s"(b4) : "s"(trow) : "memory");
-    return (unsigned)(ci == 0 ? b[0] : ci == 1 ? b[1] : ci == 2 ? b[2] : ci == 3 ? b[3] : b4);
+    return qt_tab_lane(a.tab, st, ci, min(max(yrow, st.ylo), st.yhi));
   };
   auto tab_new_row = [&](const QStrip& st, int yrow) __attribute__((always_inline)) -> bool {
     return yrow > st.ylo && yrow <= st.yhi && (yrow & 15) == 0;
-  };
-  auto row_in = [&](const QStrip& st, unsigned base, unsigned mX, int yrow) __attribute__((always_inline)) -> unsigned {
-    const int yc = min(max(yrow, st.ylo), st.yhi);
-    return base + (mX | (st_spread((unsigned)yc & 15u) << 1));
   };
 
   // ---- x (the two `top` waves; `middle` has no register to spare and `bottom` has the stores): wave q fetches tiles 2 q and
@@ -148,8 +114,6 @@ __global__ __launch_bounds__(VARIANT == 1 ? 512 : Q8_THREADS, 1) void cheb_qstri
   const unsigned x_goff = (unsigned)(lane >> 5) * 64u + (unsigned)(2 * ((lane >> 4) & 1) + (lane & 1)) * 16u;
   auto xw_wait = [&](qs_f4 (&xv)[4]) __attribute__((always_inline)) { asm volatile("" : "+v"(xv[0]), "+v"(xv[1]), "+v"(xv[2]), "+v"(xv[3]) : : "memory"); };
   auto xstore = [&](int slot, const qs_f4 (&xv)[4]) __attribute__((always_inline)) {
-    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
 #pragma unroll
     for (int i = 0; i < 4; ++i) {  // load i: tile 2 oq + (i >> 1), pixels p8 + 8 (i & 1)
       const int pix = ((lane >> 1) & 7) + 8 * (i & 1);
@@ -159,21 +123,9 @@ __global__ __launch_bounds__(VARIANT == 1 ? 512 : Q8_THREADS, 1) void cheb_qstri
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         const float a0 = F16 ? xv[i][2 * j] * a.xsc : xv[i][2 * j], a1 = F16 ? xv[i][2 * j + 1] * a.xsc : xv[i][2 * j + 1];
-        if (F16) {  // (a value beyond the f16 range becomes an infinity here and a NaN row in y: loud, not wrong)
-          typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-          const f16x2 h = __builtin_convertvector(f32x2{a0, a1}, f16x2);
-          const f32x2 hf = __builtin_convertvector(h, f32x2);
-          const f16x2 l = __builtin_convertvector(f32x2{a0 - hf[0], a1 - hf[1]}, f16x2);
-          hi[j] = __builtin_bit_cast(unsigned, h);
-          lo[j] = __builtin_bit_cast(unsigned, l);
-        } else {
-          const bf16x2 h = __builtin_convertvector(f32x2{a0, a1}, bf16x2);
-          const unsigned hu = __builtin_bit_cast(unsigned, h);
-          const float h0 = __builtin_bit_cast(float, hu << 16), h1 = __builtin_bit_cast(float, hu & 0xffff0000u);
-          const bf16x2 l = __builtin_convertvector(f32x2{a0 - h0, a1 - h1}, bf16x2);
-          hi[j] = hu;
-          lo[j] = __builtin_bit_cast(unsigned, l);
-        }
+        const qs_u2 hl = qt_split<F16>(a0, a1);
+        hi[j] = hl[0];
+        lo[j] = hl[1];
       }
       *reinterpret_cast<qs_u2*>(q) = hi;
       *reinterpret_cast<qs_u2*>(q + 4 * QS_FRAG) = lo;
@@ -181,37 +133,16 @@ __global__ __launch_bounds__(VARIANT == 1 ? 512 : Q8_THREADS, 1) void cheb_qstri
   };
   // ---- L~ (the two `top` waves): wave q fetches the row's values of the pixels 4 p + q and 4 p + q + 2 and files them, doubled,
   // in the ring ------------------------------------------------------------------------------------------------------------
+  // (qt_cfetch of cheb_qtape.h written out: there both addresses are formed before the first load, here each load follows its own
+  // address, and the compiler's schedule follows the source -- with the shared form two loads of a step change places.  Kept so that
+  // this kernel compiles to the instructions it had.)
   auto cfetch = [&](unsigned rid, qs_f4& cv, float& cd) __attribute__((always_inline)) {
     cv = *reinterpret_cast<const qs_f4*>(reinterpret_cast<const char*>(a.gvals8) + (size_t)rid * 32u + (unsigned)(q4 & 1) * 16u);
     cd = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(a.gdiag) + (size_t)rid * 4u);
   };
-  auto cstore = [&](int slot, int res, qs_f4 cv, float cd) __attribute__((always_inline)) {
-    cv = cv + cv;
-    cd = cd + cd;
-    unsigned char* q = smem + LDS_C + (unsigned)slot * CROWB + (unsigned)p * 16u + (unsigned)res * 4u;
-    if (q4 < 2) {
-#pragma unroll
-      for (int d = 0; d < 4; ++d) *reinterpret_cast<float*>(q + (unsigned)(1 + 4 * q4 + d) * 256u) = cv[d];
-    }
-    if (q4 == 2) *reinterpret_cast<float*>(q) = cd;
-  };
-  auto cvec = [&](const unsigned char* q, int v) __attribute__((always_inline)) -> qs_f4 { return *reinterpret_cast<const qs_f4*>(q + (unsigned)v * 256u); };
-  auto clo_read = [&](int slot) __attribute__((always_inline)) -> QCoefLo {
-    const unsigned char* q = smem + LDS_C + (unsigned)slot * CROWB + (unsigned)p * 16u;
-    QCoefLo c;
-    c.sw = cvec(q, 8); c.s = cvec(q, 7); c.se = cvec(q, 6);
-    c.w = cvec(q, 1); c.dg = cvec(q, 0); c.e = cvec(q, 5);
-    return c;
-  };
-  auto chi_read = [&](int slot) __attribute__((always_inline)) -> QCoefHi {
-    const unsigned char* q = smem + LDS_C + (unsigned)slot * CROWB + (unsigned)p * 16u;
-    QCoefHi c;
-    c.nw = cvec(q, 2); c.n = cvec(q, 3); c.ne = cvec(q, 4);
-    return c;
-  };
-#define Q8_LO0(c) (c).sw, (c).s, (c).se
-#define Q8_LO1(c) (c).w, (c).dg, (c).e
-#define Q8_HI(c) (c).nw, (c).n, (c).ne
+  auto cstore = [&](int slot, int res, qs_f4 cv, float cd) __attribute__((always_inline)) { qt_cstore<true>(smem + LDS_C, slot, p, q4, res, cv, cd); };
+  auto clo_read = [&](int slot) __attribute__((always_inline)) -> QCoefLo { return qt_clo_read(smem + LDS_C, slot, p); };
+  auto chi_read = [&](int slot) __attribute__((always_inline)) -> QCoefHi { return qt_chi_read(smem + LDS_C, slot, p); };
 
   // The MFMA chain of one level: 12 instructions (2 pairs of tiles x 3 terms x 2 tiles; consecutive ones go to different tiles),
   // each followed by the stencil units that fall to it (NU units over the first nine); the fragments of the second pair are
@@ -227,7 +158,7 @@ __global__ __launch_bounds__(VARIANT == 1 ? 512 : Q8_THREADS, 1) void cheb_qstri
     Q8_FR(0, FADDR, 0)                                                                                                    \
     _Pragma("unroll") for (int s = 0; s < 2; ++s) {                                                                       \
       if ((BUFS) == 2 && s == 0) { Q8_FR((BUFS) == 2 ? 1 : 0, FADDR, 1) }                                                                   \
-      if ((BUFS) == 1 && s == 1) { Q8_FR(0, FADDR, 1) } /* (reloaded from LDS behind their last reader: safe, see cheb_qwgrad_kernel.h) */ \
+      if ((BUFS) == 1 && s == 1) { Q8_FR(0, FADDR, 1) } /* (reloaded from LDS behind their last reader: safe, see the note behind the step's first barrier in cheb_qwgrad_kernel.h) */ \
       _Pragma("unroll") for (int j = 0; j < 3; ++j) {                                                                     \
         _Pragma("unroll") for (int u = 0; u < 2; ++u) {                                                                   \
           const int m = (s * 3 + j) * 2 + u;                                                                              \
@@ -261,10 +192,10 @@ __global__ __launch_bounds__(VARIANT == 1 ? 512 : Q8_THREADS, 1) void cheb_qstri
         for (int h = 0; h < 2; ++h) wr[l][h] = *reinterpret_cast<const qs_bf8*>(wp + (size_t)(l * 2 + h) * QS_FRAG);
     }
     int handed = 0;
-    for (int64_t tr = tape_begin; tr < tape_end;) {
+    for (int64_t tr = tape.begin; tr < tape.end;) {
       QStrip st;
-      tr += locate(tr, tape_end, st);
-      for (int nq = map0; nq < a.N; nq += a.wg_per_piece) {
+      tr += locate(tr, tape.end, st);
+      for (int nq = wg.map0; nq < a.N; nq += a.wg_per_piece) {
         const int tc0 = max(st.xs, st.xlo) >> 4;
         // what this wave fetches: L~ of the pixels 4 p + oq + 2 i; x of the pixels 4 (p8 + 8 (i & 1)) + 2 oq + (i >> 1), i = 0..3
         unsigned pkC[2], pkF[4];  // (tile column - the strip's first) << 8 | Morton bits of the column inside its tile
@@ -288,7 +219,7 @@ __global__ __launch_bounds__(VARIANT == 1 ? 512 : Q8_THREADS, 1) void cheb_qstri
 #pragma unroll
             for (int t = 0; t < 4; ++t) R[i][s].t[t] = qs_f4{0.f, 0.f, 0.f, 0.f};
         int ytop = st.y0 - D, slot_top = 0, cs_top = 0;
-        step_barrier();  // (the previous item's last reads of the rings)
+        qt_step_barrier();  // (the previous item's last reads of the rings)
         unsigned bF[4], bC[2];  // the lane's tile bases of the rows in flight
         auto bases_x = [&](int yrow) __attribute__((always_inline)) {
 #pragma unroll
@@ -300,11 +231,11 @@ __global__ __launch_bounds__(VARIANT == 1 ? 512 : Q8_THREADS, 1) void cheb_qstri
         };
         auto fetch_x = [&](int yrow, qs_f4 (&xv)[4]) __attribute__((always_inline)) {
 #pragma unroll
-          for (int i = 0; i < 4; ++i) xv[i] = *reinterpret_cast<const qs_f4*>(xmap + ((size_t)row_in(st, bF[i], pkF[i] & 255u, yrow) * xrowb + x_goff));  // (64-bit: a map may exceed 4 GiB)
+          for (int i = 0; i < 4; ++i) xv[i] = *reinterpret_cast<const qs_f4*>(xmap + ((size_t)qt_row_in(st, bF[i], pkF[i] & 255u, yrow) * xrowb + x_goff));  // (64-bit: a map may exceed 4 GiB)
         };
         auto fetch_c = [&](int yrow, qs_f4 (&cv)[2], float (&cd)[2]) __attribute__((always_inline)) {
 #pragma unroll
-          for (int i = 0; i < 2; ++i) cfetch(row_in(st, bC[i], pkC[i] & 255u, yrow), cv[i], cd[i]);
+          for (int i = 0; i < 2; ++i) cfetch(qt_row_in(st, bC[i], pkC[i] & 255u, yrow), cv[i], cd[i]);
         };
         auto cw_wait = [&](qs_f4 (&cv)[2], float (&cd)[2]) __attribute__((always_inline)) {
           asm volatile("" : "+v"(cv[0]), "+v"(cv[1]), "+v"(cd[0]), "+v"(cd[1]) : : "memory");
@@ -324,7 +255,7 @@ __global__ __launch_bounds__(VARIANT == 1 ? 512 : Q8_THREADS, 1) void cheb_qstri
           bases_c(ytop);
           bases_x(ytop + 1);
         }
-        step_barrier();
+        qt_step_barrier();
         auto step = [&](auto ph_c) __attribute__((always_inline)) {
           constexpr int PH = decltype(ph_c)::value;
           constexpr int L0 = PH % 3, L1 = (PH + 1) % 3, L2 = (PH + 2) % 3;
@@ -345,26 +276,26 @@ __global__ __launch_bounds__(VARIANT == 1 ? 512 : Q8_THREADS, 1) void cheb_qstri
           const QCoefLo c6 = clo_read(cslot_ix(1));  // row ytop-1: level 6
           // s0: z_7 -> B7[new] | B6[new] = + (B7[-2], B7[-1])                     (level 6 enters with +2 L~)
           Q8_CHAIN(R[0][L2], 1, R[0][L2], 0, f0, 2 * QS_UPR,
-                   { if (qq < QS_UPR) QS_UNIT<true, false>(R[1][L2], R[0][L0], qq, Q8_LO0(c6)); else QS_UNIT<false, false>(R[1][L2], R[0][L1], qq - QS_UPR, Q8_LO1(c6)); })
+                   { if (qq < QS_UPR) QS_UNIT<true, false>(R[1][L2], R[0][L0], qq, QS_LO0(c6)); else QS_UNIT<false, false>(R[1][L2], R[0][L1], qq - QS_UPR, QS_LO1(c6)); })
           qs_settle<9>(R[0][L2]);
           qs_settle<1>(R[1][L2]);
           const QCoefLo c5 = clo_read(cslot_ix(2));  // row ytop-2: level 5
           const QCoefHi c6h = chi_read(cslot_ix(1));
           // s1: z_6 -> B6[new] | B5[new] = B7[-2] - (B6[-2], B6[-1]), in place in R[0][L0]      (level 5 enters with -2 L~)
           Q8_CHAIN(R[1][L2], 0, R[1][L2], 1, f1, 2 * QS_UPR,
-                   { if (qq < QS_UPR) QS_UNIT<false, true>(R[0][L0], R[1][L0], qq, Q8_LO0(c5)); else QS_UNIT<false, true>(R[0][L0], R[1][L1], qq - QS_UPR, Q8_LO1(c5)); })
+                   { if (qq < QS_UPR) QS_UNIT<false, true>(R[0][L0], R[1][L0], qq, QS_LO0(c5)); else QS_UNIT<false, true>(R[0][L0], R[1][L1], qq - QS_UPR, QS_LO1(c5)); })
           qs_settle<9>(R[1][L2]);
           qs_settle<1>(R[0][L0]);
           const QCoefHi c5h = chi_read(cslot_ix(2));
           // s2: z_5 -> B5[new] | B6[new] += B7[new]
-          Q8_CHAIN(R[0][L0], 0, R[0][L0], 2, f2, QS_UPR, { QS_UNIT<false, false>(R[1][L2], R[0][L2], qq, Q8_HI(c6h)); })
+          Q8_CHAIN(R[0][L0], 0, R[0][L0], 2, f2, QS_UPR, { QS_UNIT<false, false>(R[1][L2], R[0][L2], qq, QS_HI(c6h)); })
           qs_settle<9>(R[0][L0]);
           qs_settle<1>(R[1][L2]);
           // s3: B5[new] -= B6[new]
 #pragma unroll
-          for (int qq = 0; qq < QS_UPR; ++qq) QS_UNIT<false, true>(R[0][L0], R[1][L2], qq, Q8_HI(c5h));
+          for (int qq = 0; qq < QS_UPR; ++qq) QS_UNIT<false, true>(R[0][L0], R[1][L2], qq, QS_HI(c5h));
           // hand-over: B5[new] and the dying row of B6 -- once `middle` has taken the previous pair
-          for (int spin = 0; flag_get(flag_at(0)) <= handed && spin < (1 << 22); ++spin) {}
+          for (int spin = 0; qt_flag_get(flag_at(0)) <= handed && spin < (1 << 22); ++spin) {}
           {
             unsigned char* hp = smem + hand_at(0);
 #pragma unroll
@@ -384,7 +315,7 @@ __global__ __launch_bounds__(VARIANT == 1 ? 512 : Q8_THREADS, 1) void cheb_qstri
           slot_top = snew;
           cs_top = cs_top + 1 == CRING ? 0 : cs_top + 1;
           ++ytop;
-          step_barrier();
+          qt_step_barrier();
         };
         for (int t3 = 0; t3 < T3; ++t3) {
           step(std::integral_constant<int, 0>{});
@@ -407,10 +338,10 @@ __global__ __launch_bounds__(VARIANT == 1 ? 512 : Q8_THREADS, 1) void cheb_qstri
         for (int h = 0; h < 2; ++h) wr[l][h] = *reinterpret_cast<const qs_bf8*>(wp + (size_t)(l * 2 + h) * QS_FRAG);
     }
     int handed = 0, taken = 0;
-    for (int64_t tr = tape_begin; tr < tape_end;) {
+    for (int64_t tr = tape.begin; tr < tape.end;) {
       QStrip st;
-      tr += locate(tr, tape_end, st);
-      for (int nq = map0; nq < a.N; nq += a.wg_per_piece) {
+      tr += locate(tr, tape.end, st);
+      for (int nq = wg.map0; nq < a.N; nq += a.wg_per_piece) {
         const int T3 = ((st.y1 - st.y0) + Q8_RUNIN + 2) / 3;
         QRow R[3][3];
 #pragma unroll
@@ -420,8 +351,8 @@ __global__ __launch_bounds__(VARIANT == 1 ? 512 : Q8_THREADS, 1) void cheb_qstri
 #pragma unroll
             for (int t = 0; t < 4; ++t) R[i][s].t[t] = qs_f4{0.f, 0.f, 0.f, 0.f};
         int ytop = st.y0 - D, slot_top = 0, cs_top = 0;
-        step_barrier();
-        step_barrier();
+        qt_step_barrier();
+        qt_step_barrier();
         auto step = [&](auto ph_c) __attribute__((always_inline)) {
           constexpr int PH = decltype(ph_c)::value;
           constexpr int L0 = PH % 3, L1 = (PH + 1) % 3, L2 = (PH + 2) % 3;
@@ -439,7 +370,7 @@ __global__ __launch_bounds__(VARIANT == 1 ? 512 : Q8_THREADS, 1) void cheb_qstri
             }
           }
           ++taken;
-          flag_set(flag_at(0), taken);  // (LDS operations of a wave complete in order: the reads above are done first)
+          qt_flag_set(flag_at(0), taken);  // (LDS operations of a wave complete in order: the reads above are done first)
           const unsigned f4 = (unsigned)slot_ix(4) * ROWB + lane16, f5 = (unsigned)slot_ix(5) * ROWB + lane16, f6 = (unsigned)slot_ix(6) * ROWB + lane16;
           qs_bf8 fr[HELP ? 2 : 1][2][2];  // (six waves: one set of B fragments -- 16 registers that the three windows need; eight: two)
           // Rows of this step: B5 window = rows ytop-5, -4, -3 (R[0][L0..L2]); B4[new] = row ytop-4; B3[new] = row ytop-5;
@@ -453,7 +384,7 @@ __global__ __launch_bounds__(VARIANT == 1 ? 512 : Q8_THREADS, 1) void cheb_qstri
             const QCoefLo c3 = clo_read(cslot_ix(5));  // row ytop-5: level 3
             // m0: z_4 -> B4[new] (onto the B6 row) | B3[new] -= (B4[-2], B4[-1])                  (level 3 enters with -2 L~)
             Q8_CHAINM(R[1][L2], 0, R[1][L2], 0, f4, 2 * QS_UPR,
-                     { if (qq < QS_UPR) QS_UNIT<false, true>(R[2][L2], R[1][L0], qq, Q8_LO0(c3)); else QS_UNIT<false, true>(R[2][L2], R[1][L1], qq - QS_UPR, Q8_LO1(c3)); })
+                     { if (qq < QS_UPR) QS_UNIT<false, true>(R[2][L2], R[1][L0], qq, QS_LO0(c3)); else QS_UNIT<false, true>(R[2][L2], R[1][L1], qq - QS_UPR, QS_LO1(c3)); })
           }
           qs_settle<9>(R[1][L2]);
           qs_settle<1>(R[2][L2]);
@@ -462,16 +393,16 @@ __global__ __launch_bounds__(VARIANT == 1 ? 512 : Q8_THREADS, 1) void cheb_qstri
             const QCoefHi c4h = chi_read(cslot_ix(4));
             // m1: z_3 -> B3[new] | B4[new] += (B5[-1], B5[0], B5[+1])                             (level 4 enters with +2 L~)
             Q8_CHAINM(R[2][L2], 0, R[2][L2], 1, f5, 3 * QS_UPR,
-                     { if (qq < QS_UPR) QS_UNIT<false, false>(R[1][L2], R[0][L0], qq, Q8_LO0(c4));
-                       else if (qq < 2 * QS_UPR) QS_UNIT<false, false>(R[1][L2], R[0][L1], qq - QS_UPR, Q8_LO1(c4));
-                       else QS_UNIT<false, false>(R[1][L2], R[0][L2], qq - 2 * QS_UPR, Q8_HI(c4h)); })
+                     { if (qq < QS_UPR) QS_UNIT<false, false>(R[1][L2], R[0][L0], qq, QS_LO0(c4));
+                       else if (qq < 2 * QS_UPR) QS_UNIT<false, false>(R[1][L2], R[0][L1], qq - QS_UPR, QS_LO1(c4));
+                       else QS_UNIT<false, false>(R[1][L2], R[0][L2], qq - 2 * QS_UPR, QS_HI(c4h)); })
           }
           qs_settle<9>(R[2][L2]);
           qs_settle<1>(R[1][L2]);
           {
             const QCoefHi c3h = chi_read(cslot_ix(5));
             // m2: z_2 -> B2[new], in place on the dying B4 row | B3[new] -= B4[new] (its row y+1)
-            Q8_CHAINM(R[1][L0], 0, R[1][L0], 2, f6, QS_UPR, { QS_UNIT<false, true>(R[2][L2], R[1][L2], qq, Q8_HI(c3h)); })
+            Q8_CHAINM(R[1][L0], 0, R[1][L0], 2, f6, QS_UPR, { QS_UNIT<false, true>(R[2][L2], R[1][L2], qq, QS_HI(c3h)); })
           }
           qs_settle<9>(R[1][L0]);
           qs_settle<1>(R[2][L2]);
@@ -481,13 +412,13 @@ __global__ __launch_bounds__(VARIANT == 1 ? 512 : Q8_THREADS, 1) void cheb_qstri
             // m3: B2[new] += (B3[-1], B3[0], B3[+1])                                               (level 2 enters with +2 L~)
 #pragma unroll
             for (int qq = 0; qq < 3 * QS_UPR; ++qq) {
-              if (qq < QS_UPR) QS_UNIT<false, false>(R[1][L0], R[2][L0], qq, Q8_LO0(c2));
-              else if (qq < 2 * QS_UPR) QS_UNIT<false, false>(R[1][L0], R[2][L1], qq - QS_UPR, Q8_LO1(c2));
-              else QS_UNIT<false, false>(R[1][L0], R[2][L2], qq - 2 * QS_UPR, Q8_HI(c2h));
+              if (qq < QS_UPR) QS_UNIT<false, false>(R[1][L0], R[2][L0], qq, QS_LO0(c2));
+              else if (qq < 2 * QS_UPR) QS_UNIT<false, false>(R[1][L0], R[2][L1], qq - QS_UPR, QS_LO1(c2));
+              else QS_UNIT<false, false>(R[1][L0], R[2][L2], qq - 2 * QS_UPR, QS_HI(c2h));
             }
           }
           // hand-over: B2[new] and the dying row of B3 -- once `bottom` has taken the previous pair
-          for (int spin = 0; flag_get(flag_at(1)) <= handed && spin < (1 << 22); ++spin) {}
+          for (int spin = 0; qt_flag_get(flag_at(1)) <= handed && spin < (1 << 22); ++spin) {}
           {
             unsigned char* hp = smem + hand_at(1);
 #pragma unroll
@@ -501,7 +432,7 @@ __global__ __launch_bounds__(VARIANT == 1 ? 512 : Q8_THREADS, 1) void cheb_qstri
           slot_top = snew;
           cs_top = cs_top + 1 == CRING ? 0 : cs_top + 1;
           ++ytop;
-          step_barrier();
+          qt_step_barrier();
         };
         for (int t3 = 0; t3 < T3; ++t3) {
           step(std::integral_constant<int, 0>{});
@@ -514,10 +445,10 @@ __global__ __launch_bounds__(VARIANT == 1 ? 512 : Q8_THREADS, 1) void cheb_qstri
     // =================================================================================================================
     // helpers (VARIANT 1): fetch, split and file the rows of x and L~ that `top` otherwise fetches -- nothing else.
     // =================================================================================================================
-    for (int64_t tr = tape_begin; tr < tape_end;) {
+    for (int64_t tr = tape.begin; tr < tape.end;) {
       QStrip st;
-      tr += locate(tr, tape_end, st);
-      for (int nq = map0; nq < a.N; nq += a.wg_per_piece) {
+      tr += locate(tr, tape.end, st);
+      for (int nq = wg.map0; nq < a.N; nq += a.wg_per_piece) {
         const int tc0 = max(st.xs, st.xlo) >> 4;
         unsigned pkC[2], pkF[4];
 #pragma unroll
@@ -533,7 +464,7 @@ __global__ __launch_bounds__(VARIANT == 1 ? 512 : Q8_THREADS, 1) void cheb_qstri
         const int T3 = ((st.y1 - st.y0) + Q8_RUNIN + 2) / 3;
         const char* __restrict__ xmap = reinterpret_cast<const char*>(a.x) + (size_t)nq * a.x_rows * xrowb;
         int ytop = st.y0 - D, slot_top = 0, cs_top = 0;
-        step_barrier();
+        qt_step_barrier();
         unsigned bF[4], bC[2];
         auto bases_x = [&](int yrow) __attribute__((always_inline)) {
 #pragma unroll
@@ -545,11 +476,11 @@ __global__ __launch_bounds__(VARIANT == 1 ? 512 : Q8_THREADS, 1) void cheb_qstri
         };
         auto fetch_x = [&](int yrow, qs_f4 (&xv)[4]) __attribute__((always_inline)) {
 #pragma unroll
-          for (int i = 0; i < 4; ++i) xv[i] = *reinterpret_cast<const qs_f4*>(xmap + ((size_t)row_in(st, bF[i], pkF[i] & 255u, yrow) * xrowb + x_goff));
+          for (int i = 0; i < 4; ++i) xv[i] = *reinterpret_cast<const qs_f4*>(xmap + ((size_t)qt_row_in(st, bF[i], pkF[i] & 255u, yrow) * xrowb + x_goff));
         };
         auto fetch_c = [&](int yrow, qs_f4 (&cv)[2], float (&cd)[2]) __attribute__((always_inline)) {
 #pragma unroll
-          for (int i = 0; i < 2; ++i) cfetch(row_in(st, bC[i], pkC[i] & 255u, yrow), cv[i], cd[i]);
+          for (int i = 0; i < 2; ++i) cfetch(qt_row_in(st, bC[i], pkC[i] & 255u, yrow), cv[i], cd[i]);
         };
         bases_x(ytop);
         bases_c(ytop - 1);
@@ -564,7 +495,7 @@ __global__ __launch_bounds__(VARIANT == 1 ? 512 : Q8_THREADS, 1) void cheb_qstri
         }
         bases_c(ytop);
         bases_x(ytop + 1);
-        step_barrier();
+        qt_step_barrier();
         for (int t = 0; t < 3 * T3; ++t) {
           int snew = slot_top + 1;
           snew = snew == RING ? 0 : snew;
@@ -580,7 +511,7 @@ __global__ __launch_bounds__(VARIANT == 1 ? 512 : Q8_THREADS, 1) void cheb_qstri
           slot_top = snew;
           cs_top = cs_top + 1 == CRING ? 0 : cs_top + 1;
           ++ytop;
-          step_barrier();
+          qt_step_barrier();
         }
       }
     }
@@ -601,10 +532,10 @@ __global__ __launch_bounds__(VARIANT == 1 ? 512 : Q8_THREADS, 1) void cheb_qstri
     qs_f4 bv = qs_f4{0.f, 0.f, 0.f, 0.f};
     if (a.bias != nullptr) bv = *reinterpret_cast<const qs_f4*>(a.bias + 16 * oq + 4 * q4);
     int taken = 0;
-    for (int64_t tr = tape_begin; tr < tape_end;) {
+    for (int64_t tr = tape.begin; tr < tape.end;) {
       QStrip st;
-      tr += locate(tr, tape_end, st);
-      for (int nq = map0; nq < a.N; nq += a.wg_per_piece) {
+      tr += locate(tr, tape.end, st);
+      for (int nq = wg.map0; nq < a.N; nq += a.wg_per_piece) {
         const int tc0 = max(st.xs, st.xlo) >> 4;
         const int Xg = st.xs + 4 * p;
         const unsigned ciY = (unsigned)((min(max(Xg, st.xlo), st.xhi) >> 4) - tc0), mXg = st_spread((unsigned)Xg & 12u);
@@ -621,11 +552,11 @@ __global__ __launch_bounds__(VARIANT == 1 ? 512 : Q8_THREADS, 1) void cheb_qstri
 #pragma unroll
         for (int t = 0; t < 4; ++t) Y.t[t] = qs_f4{0.f, 0.f, 0.f, 0.f};
         int ytop = st.y0 - D, slot_top = 0, cs_top = 0;
-        step_barrier();
+        qt_step_barrier();
         unsigned bY = tab_lane(st, ciY, st.y0);
         // (the stored row's Morton bits inside its tile, stepped with the row: cheb_qstrip_kernel.h, my_next)
         unsigned myY = st_spread((unsigned)(ytop - (K + 1)) & 15u) << 1;
-        step_barrier();
+        qt_step_barrier();
         auto step = [&](auto ph_c) __attribute__((always_inline)) {
           constexpr int PH = decltype(ph_c)::value;
           constexpr int L0 = PH % 3, L1 = (PH + 1) % 3, L2 = (PH + 2) % 3;
@@ -645,7 +576,7 @@ __global__ __launch_bounds__(VARIANT == 1 ? 512 : Q8_THREADS, 1) void cheb_qstri
             }
           }
           ++taken;
-          flag_set(flag_at(1), taken);
+          qt_flag_set(flag_at(1), taken);
           const unsigned f1 = (unsigned)slot_ix(8) * ROWB + lane16, f0 = (unsigned)slot_ix(9) * ROWB + lane16;
           qs_bf8 fr[2][2][2];
           const QCoefLo c1 = clo_read(cslot_ix(8));  // row ytop-8: level 1
@@ -655,20 +586,20 @@ __global__ __launch_bounds__(VARIANT == 1 ? 512 : Q8_THREADS, 1) void cheb_qstri
           qs_settle<1>(Y);
           // b0: 2 z_0 + 2 B2[-1] -> Y | B1[new] (= B3 row) -= (B2[-1], B2[0], B2[+1])              (level 1 enters with -2 L~)
           Q8_CHAIN(Y, 0, Y, 1, f0, 3 * QS_UPR,
-                   { if (qq < QS_UPR) QS_UNIT<false, true>(R[1][L2], R[0][L0], qq, Q8_LO0(c1));
-                     else if (qq < 2 * QS_UPR) QS_UNIT<false, true>(R[1][L2], R[0][L1], qq - QS_UPR, Q8_LO1(c1));
-                     else QS_UNIT<false, true>(R[1][L2], R[0][L2], qq - 2 * QS_UPR, Q8_HI(c1h)); })
+                   { if (qq < QS_UPR) QS_UNIT<false, true>(R[1][L2], R[0][L0], qq, QS_LO0(c1));
+                     else if (qq < 2 * QS_UPR) QS_UNIT<false, true>(R[1][L2], R[0][L1], qq - QS_UPR, QS_LO1(c1));
+                     else QS_UNIT<false, true>(R[1][L2], R[0][L2], qq - 2 * QS_UPR, QS_HI(c1h)); })
           qs_settle<9>(Y);
           qs_settle<1>(R[1][L2]);
           const QCoefLo c0 = clo_read(cslot_ix(9));  // row ytop-9: level 0
           const QCoefHi c0h = chi_read(cslot_ix(9));
           // b1: z_1 -> B1[new] | Y += (B1[-2], B1[-1])                                              (level 0 enters with +2 L~ into the doubled Y)
           Q8_CHAIN(R[1][L2], 0, R[1][L2], 0, f1, 2 * QS_UPR,
-                   { if (qq < QS_UPR) QS_UNIT<false, false>(Y, R[1][L0], qq, Q8_LO0(c0)); else QS_UNIT<false, false>(Y, R[1][L1], qq - QS_UPR, Q8_LO1(c0)); })
+                   { if (qq < QS_UPR) QS_UNIT<false, false>(Y, R[1][L0], qq, QS_LO0(c0)); else QS_UNIT<false, false>(Y, R[1][L1], qq - QS_UPR, QS_LO1(c0)); })
           qs_settle<9>(R[1][L2]);
           // b2: Y += B1[new]: y of row ytop - 9
 #pragma unroll
-          for (int qq = 0; qq < QS_UPR; ++qq) QS_UNIT<false, false>(Y, R[1][L2], qq, Q8_HI(c0h));
+          for (int qq = 0; qq < QS_UPR; ++qq) QS_UNIT<false, false>(Y, R[1][L2], qq, QS_HI(c0h));
           {
             const bool row_ok = yr >= st.y0 && yr < st.y1;
             const unsigned rowg = bY + (mXg | myY);
@@ -690,7 +621,7 @@ __global__ __launch_bounds__(VARIANT == 1 ? 512 : Q8_THREADS, 1) void cheb_qstri
           cs_top = cs_top + 1 == CRING ? 0 : cs_top + 1;
           ++ytop;
           myY = ((myY | 0x55u) + 1u) & 0xaau;
-          step_barrier();
+          qt_step_barrier();
         };
         for (int t3 = 0; t3 < T3; ++t3) {
           step(std::integral_constant<int, 0>{});
@@ -705,9 +636,6 @@ __global__ __launch_bounds__(VARIANT == 1 ? 512 : Q8_THREADS, 1) void cheb_qstri
 #undef Q8_CHAINM
 #undef Q8_CHAIN_B
 #undef Q8_FR
-#undef Q8_LO0
-#undef Q8_LO1
-#undef Q8_HI
 }
 
 }  // namespace dsph

@@ -25,18 +25,19 @@
 //   of rows of consecutive strips, each run with its own 9 run-in steps), and w workgroups share a piece, workgroup j of them
 //   taking the maps j, j + w, ... -- for a batch of N <= G maps w = N and P = G / N: every workgroup gets the same number of
 //   rows whatever the strips' heights, and the N workgroups of a piece (neighbours on one XCD) walk the same rows of L~ at the
-//   same time, one map each (the host picks P and w: qstrip_split).
+//   same time, one map each (the host picks P and w: qtape_split).
 // LDS (161,344 B): ring of 7 rows of x as bf16 hi | lo B-operand fragments (16 KiB per row: [32-channel block][hi | lo][tile]
 //   1 KiB fragments), hand-over 4 x 8 KiB, ring of 6 rows of L~ (2,304 B per row: the diagonal and the eight directions, each a
 //   [p][tile] vector: a lane reads the 16 bytes of its four pixels per direction, 9 reads per level-row), counters.
+// The strip record, the walk along the tape, the rows through the tables of tile bases, the hi | lo split and the ring row of L~
+//   are cheb_qtape.h's, shared with the K = 8 forward and the weight gradient; roles, LDS layout, chains and schedule are this file's.
 // x: fetched a step ahead and split into fragments at the end of the step -- by all eight waves, half a tile each (two 16-byte
 //   loads per lane), when level 1's matrix work runs on H (Chebyshev basis); else by the H wave of quarter q, tile q (four loads).  y: straight from the accumulators, 16 pixels x 64 contiguous bytes per instruction.
 #pragma once
 
 #include <type_traits>
 
-#include "cheb_struct_kernel.h"
-#include "dsphere_common.h"
+#include "cheb_qtape.h"
 
 namespace dsph {
 
@@ -44,28 +45,7 @@ constexpr int QS_PX = 64;                       // pixel columns of a strip: 16 
 constexpr int QS_D = 4;                         // halo columns on either side (K = 5)
 constexpr int QS_USE = QS_PX - 2 * QS_D;        // 56 output columns
 constexpr int QS_THREADS = 512;
-constexpr int QS_FRAG = 1024;                   // bytes of one MFMA operand fragment (64 lanes x 16 B)
-
-typedef float qs_f4 __attribute__((ext_vector_type(4)));
-typedef __bf16 qs_bf8 __attribute__((ext_vector_type(8)));
-typedef unsigned qs_u2 __attribute__((ext_vector_type(2)));
-
-// one row of a plane as a wave holds it: tile t = pixel 4 p + t, element e = output channel 16 oq + 4 (lane >> 4) + e
-struct QRow {
-  qs_f4 t[4];
-};
-
-// One work item (with a map of the batch): a strip of up to 56 output columns over rows [y0, y1).
-struct QStrip {
-  int32_t x0, w;      // virtual x of the first output column, output columns (<= QS_USE)
-  int32_t xs;         // virtual x of column 0 (x0 - D; columns are clamped to [xlo, xhi] when loaded)
-  int32_t y0, y1;     // output rows [y0, y1)
-  int32_t xlo, xhi;   // the rectangle and its halo
-  int32_t ylo, yhi;
-  int32_t tab, tws;   // the rectangle's table of tile bases (offset into QStripArgs::tab) and its row stride: pixel (x, y) of the
-                      // strip's plane is row tab[(y >> 4) * tws + (x >> 4)] + morton(x & 15, y & 15)
-  int32_t pad[1];
-};
+constexpr int QS_RUNIN = 2 * QS_D + 1;          // steps before the first output row of a run of rows
 
 struct QStripArgs {
   const float* x;
@@ -221,16 +201,6 @@ __device__ __forceinline__ void qs_unit(QRow& acc, const QRow& src, int e, const
 #define QS_UPR 4  /* units per source row */
 #define QS_UNIT qs_unit
 
-// The values of L~ of the lane's four pixels in one row, as the ring holds them (per tile t: directions 0..3 = W NW N NE,
-// directions 4..7 = E SE S SW; the diagonal and W once more as [tile] vectors), and the three coefficient vectors
-// (west, centre, east by tile) of a source row:  y-1: SW S SE;  y: W diag E;  y+1: NW N NE.
-struct QCoefLo {  // what the rows y-1 and y of a level need: six directions, each a vector by tile
-  qs_f4 sw, s, se, w, dg, e;
-};
-struct QCoefHi {  // what the row y+1 needs
-  qs_f4 nw, n, ne;
-};
-
 // multiplier of L~ in level j and the sign kept with the planes: as in the strip kernel (sp_mult / sp_wsign)
 __host__ __device__ constexpr float qs_wsign(bool cheb, int j) { return cheb && ((j & 3) >= 2) ? -1.f : 1.f; }
 
@@ -252,9 +222,8 @@ __global__ __launch_bounds__(QS_THREADS, 2) void cheb_qstrip5_kernel(QStripArgs 
   constexpr int RINGB = RING * ROWB;            // 112 KiB
   constexpr int HAND1 = 2 * 4 * QS_FRAG;        // 8 KiB per quarter: [b2 row | b3 row][tile]
   constexpr int HANDB = 4 * HAND1;              // 32 KiB
-  constexpr int CROWB = 2304;                   // one ring row of L~: [9: the diagonal, directions 0..7][p][tile] floats
   constexpr int CRING = K + 1;
-  constexpr int CRINGB = CRING * CROWB;         // 13,824 B
+  constexpr int CRINGB = CRING * QS_CROWB;      // 13,824 B: the ring of rows of L~
   constexpr int LDS_HAND = RINGB, LDS_C = RINGB + HANDB, LDS_FLAG = LDS_C + CRINGB;
   __shared__ __attribute__((aligned(16))) unsigned char smem[LDS_FLAG + 64];
 
@@ -266,46 +235,18 @@ __global__ __launch_bounds__(QS_THREADS, 2) void cheb_qstrip5_kernel(QStripArgs 
   const unsigned lane16 = (unsigned)lane * 16u;
   const unsigned hand = (unsigned)LDS_HAND + (unsigned)oq * HAND1 + lane16;
   const unsigned flag_addr = (unsigned)LDS_FLAG + 4u * (unsigned)oq;
-  auto flag_set = [&](int v) __attribute__((always_inline)) {
-    asm volatile("ds_write_b32 %0, %1" : : "v"(flag_addr), "v"(v) : "memory");
-  };
-  auto flag_get = [&]() __attribute__((always_inline)) -> int {
-    int v;
-    asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(v) : "v"(flag_addr) : "memory");
-    return v;
-  };
+  auto flag_set = [&](int v) __attribute__((always_inline)) { qt_flag_set(flag_addr, v); };
+  auto flag_get = [&]() __attribute__((always_inline)) -> int { return qt_flag_get(flag_addr); };
   for (int i = tid; i < (LDS_FLAG + 64) / 16; i += QS_THREADS) reinterpret_cast<qs_f4*>(smem)[i] = qs_f4{0.f, 0.f, 0.f, 0.f};
 
-  // this workgroup's piece of the tape and its maps: the workgroups of one XCD (blockIdx & 7) are neighbours in `ord`
-  const int G = gridDim.x, ord = (blockIdx.x & 7) * (G >> 3) + (blockIdx.x >> 3);  // (the host launches a multiple of 8)
-  const int piece = ord / a.wg_per_piece, map0 = ord - piece * a.wg_per_piece;
-  if (piece >= a.pieces) return;  // (before the first barrier: the whole workgroup leaves)
-  const int64_t tape = (int64_t)a.prefix[a.nstrips];
-  const int64_t tape_begin = tape * piece / a.pieces, tape_end = tape * (piece + 1) / a.pieces;
-  // the piece that starts at tape row r: strip, map, first row and length (wave-uniform arithmetic)
+  // this workgroup's piece of the tape and its maps
+  const QTapePiece wg = qt_piece(a.wg_per_piece);
+  if (wg.piece >= a.pieces) return;  // (before the first barrier: the whole workgroup leaves)
+  const QTapeRange tape = qt_tape_range(a.prefix, a.nstrips, wg.piece, a.pieces);
   auto locate = [&](int64_t r, int64_t r_end, QStrip& st) __attribute__((always_inline)) -> int {
-    int lo = 0, hi = a.nstrips;
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if ((int64_t)a.prefix[mid] <= r) lo = mid; else hi = mid;
-    }
-    {  // (the record through scalar registers: every field is wave-uniform, and the compiler should know -- rows, clamps and the
-       // table look-ups' branches then run on the scalar unit)
-      const QStrip g = a.strips[lo];
-#define QS_U(f) st.f = __builtin_amdgcn_readfirstlane(g.f)
-      QS_U(x0); QS_U(w); QS_U(xs); QS_U(y0); QS_U(y1); QS_U(xlo); QS_U(xhi); QS_U(ylo); QS_U(yhi); QS_U(tab); QS_U(tws);
-#undef QS_U
-    }
-    const int h = st.y1 - st.y0;
-    const int off = (int)(r - (int64_t)a.prefix[lo]);
-    const int len = (int)(((int64_t)(h - off) < r_end - r) ? (int64_t)(h - off) : r_end - r);
-    st.y0 += off;
-    st.y1 = st.y0 + len;
-    return len;
+    return qt_locate(a.prefix, a.strips, a.nstrips, r, r_end, st);
   };
   const unsigned xrowb = (unsigned)a.Fin * 4u, yrowb = (unsigned)a.ld * 4u;
-
-  auto step_barrier = [&]() __attribute__((always_inline)) { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
 
   // ---- x: every wave fetches half a tile of row ytop+1 at the top of a step and files it at the end -------------------
   // wave w: tile xt = w & 3, pixels p8 + 8 (w >> 2) of it; lane: half h = lane & 1, pixel p8 = (lane >> 1) & 7,
@@ -332,21 +273,9 @@ __global__ __launch_bounds__(QS_THREADS, 2) void cheb_qstrip5_kernel(QStripArgs 
                                  : (unsigned)(lane >> 5) * 64u + (unsigned)(2 * ((lane >> 4) & 1) + (lane & 1)) * 16u;
   const unsigned x_loff = (unsigned)xt * QS_FRAG + (unsigned)(lane & 1) * 8u +
                           (X_BY_H ? (unsigned)(xpix + 16 * (lane >> 5)) * 16u : (unsigned)(xpix + 16 * (2 * (lane >> 5) + ((lane >> 4) & 1))) * 16u);
-  // Where a pixel of the strip's plane lives: row = tab[(y >> 4) tws + (x >> 4)] + morton(x & 15, y & 15) -- the rectangle's table
-  // of tile bases (cheb_tiles.hip, build_qtstrips: a rectangle may cross base-pixel borders that continue the pixel grid by a
-  // translation; inside a base pixel the table is the Morton plane itself).  A strip's 64 columns lie in at most five tile
-  // columns, the row y is wave-uniform: the five bases of a tile row come by SCALAR loads (they share no counter with the
-  // vector memory: a vector load here would wait for the previous step's y stores to drain -- measured, 12 % of the forward),
-  // a lane keeps the one of its column (ci = its tile column - the strip's first) -- looked up when a row enters a new tile
-  // row, every sixteenth step.
-  typedef int qs_i4 __attribute__((ext_vector_type(4)));
+  // the lane's tile base of row yrow (cheb_qtape.h: five scalar loads, every sixteenth step)
   auto tab_lane = [&](const QStrip& st, unsigned ci, int yrow) __attribute__((always_inline)) -> unsigned {
-    const int yc = min(max(yrow, st.ylo), st.yhi);
-    const int32_t* trow = a.tab + __builtin_amdgcn_readfirstlane(st.tab + (yc >> 4) * st.tws + (max(st.xs, st.xlo) >> 4));
-    qs_i4 b;
-    int b4;
-    asm volatile("s_load_dwordx4 %0, %2, 0x0\n\ts_load_dword %1, %2, 0x10\n\ts_waitcnt lgkmcnt(0)" : "=&s"(b), "=&s"(b4) : "s"(trow) : "memory");
-    return (unsigned)(ci == 0 ? b[0] : ci == 1 ? b[1] : ci == 2 ? b[2] : ci == 3 ? b[3] : b4);
+    return qt_tab_lane(a.tab, st, ci, min(max(yrow, st.ylo), st.yhi));
   };
   // A row's Morton bits inside its tile, spread(y & 15) << 1, are kept as wave-uniform state and stepped with the row:
   // (m | 0x55) + 1 & 0xaa counts in the odd bits and wraps to zero where a row enters a new tile row -- the moment for the
@@ -356,10 +285,6 @@ __global__ __launch_bounds__(QS_THREADS, 2) void cheb_qstrip5_kernel(QStripArgs 
   // feeds no output.
   auto my_of = [&](int yrow) __attribute__((always_inline)) -> unsigned { return st_spread((unsigned)yrow & 15u) << 1; };
   auto my_next = [&](unsigned m) __attribute__((always_inline)) -> unsigned { return ((m | 0x55u) + 1u) & 0xaau; };
-  auto row_in = [&](const QStrip& st, unsigned base, unsigned mX, int yrow) __attribute__((always_inline)) -> unsigned {
-    const int yc = min(max(yrow, st.ylo), st.yhi);
-    return base + (mX | (st_spread((unsigned)yc & 15u) << 1));
-  };
   auto xfetch = [&](const char* xmap, unsigned xrow, qs_f4 (&xv)[XN]) __attribute__((always_inline)) {
     if (QS_ABL & 8) {
 #pragma unroll
@@ -367,8 +292,8 @@ __global__ __launch_bounds__(QS_THREADS, 2) void cheb_qstrip5_kernel(QStripArgs 
       return;
     }
     // (plain loads: the compiler knows the data is in flight, keeps the registers out of other use and counts vmcnt itself;
-    // the asm statements around them keep the requests where they are written -- see cheb_qwgrad_kernel.h for what loads
-    // inside asm statements did there)
+    // the asm statements around them keep the requests where they are written -- see row_fetch of cheb_qwgrad_kernel.h for
+    // what loads inside asm statements did there)
     const char* src = xmap + (size_t)(xrow * xrowb + x_goff);
 #pragma unroll
     for (int i = 0; i < XN; ++i) xv[i] = *reinterpret_cast<const qs_f4*>(src + (X_BY_H ? 64 : 128) * i);
@@ -389,29 +314,15 @@ __global__ __launch_bounds__(QS_THREADS, 2) void cheb_qstrip5_kernel(QStripArgs 
     for (int i = 0; i < XN; ++i) {
       // fragment of instruction i: block and, with X_BY_H, the upper / lower half of the block's lane slots
       const unsigned fo = X_BY_H ? (unsigned)(i >> 1) * (2 * 4 * QS_FRAG) + (unsigned)(i & 1) * (32u * 16u) : (unsigned)i * (2 * 4 * QS_FRAG);
-      typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-      typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-      typedef float f32x2 __attribute__((ext_vector_type(2)));
       qs_u2 hi, lo;
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         // (f16: times the caller's power of two -- an f16 pair keeps 22 bits only where hi AND lo are normal numbers, i.e. for
         // |x xsc| from 2^-3 up; the store divides it out again, all exact)
         const float a0 = F16 ? xv[i][2 * j] * a.xsc : xv[i][2 * j], a1 = F16 ? xv[i][2 * j + 1] * a.xsc : xv[i][2 * j + 1];
-        if (F16) {  // (a value beyond the f16 range becomes an infinity here and a NaN row in y: loud, not wrong)
-          const f16x2 h = __builtin_convertvector(f32x2{a0, a1}, f16x2);
-          const f32x2 hf = __builtin_convertvector(h, f32x2);
-          const f16x2 l = __builtin_convertvector(f32x2{a0 - hf[0], a1 - hf[1]}, f16x2);
-          hi[j] = __builtin_bit_cast(unsigned, h);
-          lo[j] = __builtin_bit_cast(unsigned, l);
-        } else {
-          const bf16x2 h = __builtin_convertvector(f32x2{a0, a1}, bf16x2);
-          const unsigned hu = __builtin_bit_cast(unsigned, h);
-          const float h0 = __builtin_bit_cast(float, hu << 16), h1 = __builtin_bit_cast(float, hu & 0xffff0000u);
-          const bf16x2 l = __builtin_convertvector(f32x2{a0 - h0, a1 - h1}, bf16x2);
-          hi[j] = hu;
-          lo[j] = __builtin_bit_cast(unsigned, l);
-        }
+        const qs_u2 hl = qt_split<F16>(a0, a1);
+        hi[j] = hl[0];
+        lo[j] = hl[1];
       }
       *reinterpret_cast<qs_u2*>(q + fo) = hi;
       *reinterpret_cast<qs_u2*>(q + fo + 4 * QS_FRAG) = lo;
@@ -419,47 +330,24 @@ __global__ __launch_bounds__(QS_THREADS, 2) void cheb_qstrip5_kernel(QStripArgs 
   };
   // ---- L~: the H wave of quarter oq fetches the row's values of the pixels 4 p + oq (lanes q4 = 0: directions 0..3,
   // q4 = 1: directions 4..7, every lane the diagonal) and files them, doubled (Chebyshev), in the ring -----------------
-  auto cfetch = [&](unsigned rid, qs_f4& cv, float& cd) __attribute__((always_inline)) {
-    const char* pv = reinterpret_cast<const char*>(a.gvals8) + (size_t)rid * 32u + (unsigned)(q4 & 1) * 16u;
-    const char* pd = reinterpret_cast<const char*>(a.gdiag) + (size_t)rid * 4u;
-    cv = *reinterpret_cast<const qs_f4*>(pv);
-    cd = *reinterpret_cast<const float*>(pd);
-  };
+  auto cfetch = [&](unsigned rid, qs_f4& cv, float& cd) __attribute__((always_inline)) { qt_cfetch(a.gvals8, a.gdiag, rid, q4, cv, cd); };
   auto cw_wait = [&](qs_f4& cv, float& cd) __attribute__((always_inline)) {
     asm volatile("" : "+v"(cv), "+v"(cd) : : "memory");
   };
-  // ring row: vector v = 0 the diagonal, v = 1 + d direction d (W NW N NE E SE S SW), each [p][tile] -- what a lane reads is
-  // the 16 bytes of its four pixels of one direction
+  // (qt_cstore<CHEB> of cheb_qtape.h with res = oq, written out: through the shared function the compiler emits the four stores of a
+  // step in the opposite order and one address add changes its place.  Kept so that this kernel compiles to the instructions it had.)
   auto cstore = [&](int slot, qs_f4 cv, float cd) __attribute__((always_inline)) {
     if (CHEB) { cv = cv + cv; cd = cd + cd; }
-    unsigned char* q = smem + LDS_C + (unsigned)slot * CROWB + (unsigned)p * 16u + (unsigned)oq * 4u;
+    unsigned char* q = smem + LDS_C + (unsigned)slot * QS_CROWB + (unsigned)p * 16u + (unsigned)oq * 4u;
     if (q4 < 2) {
 #pragma unroll
       for (int d = 0; d < 4; ++d) *reinterpret_cast<float*>(q + (unsigned)(1 + 4 * q4 + d) * 256u) = cv[d];
     }
     if (q4 == 2) *reinterpret_cast<float*>(q) = cd;
   };
-  auto cvec = [&](const unsigned char* q, int v) __attribute__((always_inline)) -> qs_f4 {
-    if (QS_ABL & 1024) { qs_f4 c = qs_f4{0.1f, 0.1f, 0.1f, 0.1f}; asm volatile("" : "+v"(c)); return c; }
-    return *reinterpret_cast<const qs_f4*>(q + (unsigned)v * 256u);
-  };
-  auto clo_read = [&](int slot) __attribute__((always_inline)) -> QCoefLo {
-    const unsigned char* q = smem + LDS_C + (unsigned)slot * CROWB + (unsigned)p * 16u;
-    QCoefLo c;
-    c.sw = cvec(q, 8); c.s = cvec(q, 7); c.se = cvec(q, 6);
-    c.w = cvec(q, 1); c.dg = cvec(q, 0); c.e = cvec(q, 5);
-    return c;
-  };
-  auto chi_read = [&](int slot) __attribute__((always_inline)) -> QCoefHi {
-    const unsigned char* q = smem + LDS_C + (unsigned)slot * CROWB + (unsigned)p * 16u;
-    QCoefHi c;
-    c.nw = cvec(q, 2); c.n = cvec(q, 3); c.ne = cvec(q, 4);
-    return c;
-  };
-// coefficient vectors of the three source rows
-#define QS_LO0(c) (c).sw, (c).s, (c).se
-#define QS_LO1(c) (c).w, (c).dg, (c).e
-#define QS_HI(c) (c).nw, (c).n, (c).ne
+  constexpr bool C_OFF = (QS_ABL & 1024) != 0;
+  auto clo_read = [&](int slot) __attribute__((always_inline)) -> QCoefLo { return qt_clo_read<C_OFF>(smem + LDS_C, slot, p); };
+  auto chi_read = [&](int slot) __attribute__((always_inline)) -> QCoefHi { return qt_chi_read<C_OFF>(smem + LDS_C, slot, p); };
 
   // The MFMA chain of one level (24 MFMAs: 2 channel blocks x 2 pairs of tiles x 3 terms x 2 tiles) beside NU stencil units:
   // MFMA m is followed by the units that fall to it.  Consecutive MFMAs go to different tiles; the fragments of the next
@@ -531,10 +419,10 @@ __global__ __launch_bounds__(QS_THREADS, 2) void cheb_qstrip5_kernel(QStripArgs 
           for (int h = 0; h < 2; ++h) wr[l][kb][h] = *reinterpret_cast<const qs_bf8*>(wp + ((size_t)(l * 2 + kb) * 2 + h) * QS_FRAG);
     }
     int handed = 0;
-    for (int64_t tr = tape_begin; tr < tape_end;) {
+    for (int64_t tr = tape.begin; tr < tape.end;) {
       QStrip st;
-      tr += locate(tr, tape_end, st);
-      for (int nq = map0; nq < a.N; nq += a.wg_per_piece) {
+      tr += locate(tr, tape.end, st);
+      for (int nq = wg.map0; nq < a.N; nq += a.wg_per_piece) {
       const int Xc = min(max(st.xs + 4 * p + oq, st.xlo), st.xhi);         // L~: pixel 4 p + oq
       const int Xf = min(max(st.xs + 4 * xpix + xt, st.xlo), st.xhi);      // x: pixel 4 xpix + xt
       const int tc0 = max(st.xs, st.xlo) >> 4;  // the strip's first tile column
@@ -550,12 +438,12 @@ __global__ __launch_bounds__(QS_THREADS, 2) void cheb_qstrip5_kernel(QStripArgs 
 #pragma unroll
           for (int t = 0; t < 4; ++t) R[i][s].t[t] = qs_f4{0.f, 0.f, 0.f, 0.f};
       int ytop = st.y0 - D, slot_top = 0, cs_top = 0;
-      step_barrier();  // (the previous item's last reads of the rings)
+      qt_step_barrier();  // (the previous item's last reads of the rings)
       {
         qs_f4 cv, xv[XN];
         float cd;
-        cfetch(row_in(st, tab_lane(st, ciC, ytop - 1), mXc, ytop - 1), cv, cd);
-        xfetch(xmap, row_in(st, tab_lane(st, ciF, ytop), mXf, ytop), xv);
+        cfetch(qt_row_in(st, tab_lane(st, ciC, ytop - 1), mXc, ytop - 1), cv, cd);
+        xfetch(xmap, qt_row_in(st, tab_lane(st, ciF, ytop), mXf, ytop), xv);
         cw_wait(cv, cd);
         cstore(CRING - 1, cv, cd);
         xw_wait(xv);
@@ -564,7 +452,7 @@ __global__ __launch_bounds__(QS_THREADS, 2) void cheb_qstrip5_kernel(QStripArgs 
       // the lane's tile bases of the rows the steps ask for: x of row ytop + 1, L~ of row ytop
       unsigned bXf = tab_lane(st, ciF, ytop + 1), bXc = tab_lane(st, ciC, ytop);
       unsigned myX = my_of(ytop + 1), myC = my_of(ytop);
-      step_barrier();
+      qt_step_barrier();
       auto step = [&](auto ph_c) __attribute__((always_inline)) {
         constexpr int PH = decltype(ph_c)::value;
         constexpr int L0 = PH % 3, L1 = (PH + 1) % 3, L2 = (PH + 2) % 3;
@@ -649,7 +537,7 @@ __global__ __launch_bounds__(QS_THREADS, 2) void cheb_qstrip5_kernel(QStripArgs 
         ++ytop;
         myX = my_next(myX);
         myC = my_next(myC);
-        step_barrier();
+        qt_step_barrier();
         QS_STAMP(8);
       };
       for (int t3 = 0; t3 < T3; ++t3) {
@@ -686,10 +574,10 @@ __global__ __launch_bounds__(QS_THREADS, 2) void cheb_qstrip5_kernel(QStripArgs 
     qs_f4 bv = qs_f4{0.f, 0.f, 0.f, 0.f};
     if (a.bias != nullptr) bv = *reinterpret_cast<const qs_f4*>(a.bias + 16 * oq + 4 * q4);
     int taken = 0;
-    for (int64_t tr = tape_begin; tr < tape_end;) {
+    for (int64_t tr = tape.begin; tr < tape.end;) {
       QStrip st;
-      tr += locate(tr, tape_end, st);
-      for (int nq = map0; nq < a.N; nq += a.wg_per_piece) {
+      tr += locate(tr, tape.end, st);
+      for (int nq = wg.map0; nq < a.N; nq += a.wg_per_piece) {
       const int Xf = min(max(st.xs + 4 * xpix + xt, st.xlo), st.xhi);
       const int tc0 = max(st.xs, st.xlo) >> 4;  // the strip's first tile column
       const unsigned ciF = (unsigned)((Xf >> 4) - tc0), mXf = st_spread((unsigned)Xf & 15u);
@@ -711,17 +599,17 @@ __global__ __launch_bounds__(QS_THREADS, 2) void cheb_qstrip5_kernel(QStripArgs 
 #pragma unroll
       for (int t = 0; t < 4; ++t) Y.t[t] = qs_f4{0.f, 0.f, 0.f, 0.f};
       int ytop = st.y0 - D, slot_top = 0, cs_top = 0;
-      step_barrier();  // (the previous item's last reads of the rings)
+      qt_step_barrier();  // (the previous item's last reads of the rings)
       if (!X_BY_H) {
         qs_f4 xv[XN];
-        xfetch(xmap, row_in(st, tab_lane(st, ciF, ytop), mXf, ytop), xv);
+        xfetch(xmap, qt_row_in(st, tab_lane(st, ciF, ytop), mXf, ytop), xv);
         xw_wait(xv);
         xstore(0, xv);
       }
       // the lane's tile bases: x of row ytop + 1 (when all eight waves fetch x), y of row ytop - K
       unsigned bXf = X_BY_H ? 0u : tab_lane(st, ciF, ytop + 1), bY = tab_lane(st, ciY, st.y0);
       unsigned myX = my_of(ytop + 1), myY = my_of(ytop - K);
-      step_barrier();
+      qt_step_barrier();
       auto step = [&](auto ph_c) __attribute__((always_inline)) {
         constexpr int PH = decltype(ph_c)::value;
         constexpr int L0 = PH % 3, L1 = (PH + 1) % 3, L2 = (PH + 2) % 3;
@@ -871,7 +759,7 @@ __global__ __launch_bounds__(QS_THREADS, 2) void cheb_qstrip5_kernel(QStripArgs 
         ++ytop;
         myX = my_next(myX);
         myY = my_next(myY);
-        step_barrier();
+        qt_step_barrier();
         QS_STAMP(8);
       };
       for (int t3 = 0; t3 < T3; ++t3) {

@@ -49,30 +49,15 @@ __global__ __launch_bounds__(256) void qwgrad_reduce_kernel(const float* __restr
 
 bool qwgrad_shape_ok(int32_t Fin, int32_t Fout, int32_t K) { return K == 5 && Fin == 64 && Fout == 64; }
 
-static int qwgrad_grid(const QWgradLaunch& s, int* pieces, int* wg_per_piece) {
-  int grid;
-  (void)qstrip_split(s.num_cu, s.tape_rows, s.N, s.tape_rows / std::max(1, s.nstrips), &grid, pieces, wg_per_piece);
-  return grid;
-}
-
 size_t qwgrad_slab_bytes(int num_cu) { return (size_t)std::max(8, num_cu / 8 * 8) * QW_SLAB * sizeof(float); }
 
 int launch_cheb_qwgrad(const QWgradLaunch& s, hipStream_t stream) {
   QWgradArgs a;
-  a.x = s.x;
   a.dy = s.dy;
   a.slabs = s.slabs;
-  a.gvals8 = s.gvals8;
-  a.gdiag = s.gdiag;
-  a.strips = s.strips;
-  a.tab = s.tab;
-  a.prefix = s.prefix;
-  a.x_rows = s.x_rows;
   a.dy_rows = s.dy_rows;
-  a.nstrips = s.nstrips;
-  a.N = (int)s.N;
   a.lddy = s.lddy;
-  const int grid = qwgrad_grid(s, &a.pieces, &a.wg_per_piece);
+  const int grid = qtape_args(a, s, QS_RUNIN);
   if (s.cheb) hipLaunchKernelGGL(cheb_qwgrad5_kernel<true>, dim3(grid), dim3(QS_THREADS), 0, stream, a);
   else hipLaunchKernelGGL(cheb_qwgrad5_kernel<false>, dim3(grid), dim3(QS_THREADS), 0, stream, a);
   DSPH_HIP(hipGetLastError());

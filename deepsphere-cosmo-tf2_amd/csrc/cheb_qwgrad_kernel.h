@@ -1,5 +1,5 @@
 // Quad-strip form of the weight gradient (round 5): dW[f K + k, o] = sum over maps and pixels of T_k(L~)x [., f] * dy[., o]
-// (the gradient TF's autodiff derives from gnn_layers.py:131-150) for K = 5, 64 -> 64, on the strips of cheb_qstrip_kernel.h.
+// (the gradient TF's autodiff derives from gnn_layers.py:131-150) for K = 5, 64 -> 64, on the strips of the quad-strip forward (cheb_qtape.h).
 //
 // The contraction runs over PIXELS, and a matrix instruction's inner index lives in a lane's registers while the stencil wants
 // the pixels across the lanes (DPP) -- so every plane row has to cross the LDS once, from "lane = pixel group" to "lane =
@@ -17,7 +17,8 @@
 // vector work is the forward's (four stencil applications of 64 channels per row), and the two operands' recurrences are the
 // SAME code: waves 0..3 run it on x, waves 4..7 on dy, a wave per 16 channels, no hand-over between roles.
 //
-// One workgroup = eight waves = one strip row per step (lane layout, strips, tape and work split: cheb_qstrip_kernel.h).
+// One workgroup = eight waves = one strip row per step (strips, tape, work split, tables and the ring row of L~: cheb_qtape.h; lane
+// layout and stencil units: cheb_qstrip_kernel.h).
 // Step with top row t:  S0[t] arrives (global -> registers, requested a step ahead), S1[t-1] = L~ S0, S2[t-2] = 2 L~ S1 - S0
 //   (12 + 12 stencil units), while the matrix pipe contracts the row staged by the previous step; barrier; the planes of row
 //   t-2 are split hi + lo into bf16 and staged; barrier.
@@ -62,7 +63,7 @@ struct QWgradArgs {
   const float* gvals8;
   const float* gdiag;
   const QStrip* strips;
-  const int32_t* tab;         // the rectangles' tables of tile bases (cheb_qstrip_kernel.h: QStrip::tab, ::tws)
+  const int32_t* tab;         // the rectangles' tables of tile bases (cheb_qtape.h: QStrip::tab, ::tws)
   const int32_t* prefix;
   int64_t x_rows, dy_rows;    // rows per map
   int nstrips, N, lddy;       // lddy: row stride of dy in floats (x: 64)
@@ -72,9 +73,9 @@ struct QWgradArgs {
 template <bool CHEB>
 __global__ __launch_bounds__(QS_THREADS, 2) void cheb_qwgrad5_kernel(QWgradArgs a) {
   constexpr int D = QS_D;                 // rows of run-in on either side: two rings for the products' domain, two more for P2 on it
-  constexpr int CROWB = 2304, CRING = 3;  // rows of L~ as in cheb_qstrip_kernel.h: [9][p][tile] floats
+  constexpr int CRING = 3;                // ring rows of L~ (cheb_qtape.h)
   constexpr int LDS_C = QW_NPLANES * QW_PLANE;
-  __shared__ __attribute__((aligned(16))) unsigned char smem[LDS_C + CRING * CROWB];
+  __shared__ __attribute__((aligned(16))) unsigned char smem[LDS_C + CRING * QS_CROWB];
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -84,44 +85,25 @@ __global__ __launch_bounds__(QS_THREADS, 2) void cheb_qwgrad5_kernel(QWgradArgs 
   const int p = lane & 15, q4 = lane >> 4;
   for (int i = tid; i < (int)sizeof(smem) / 16; i += QS_THREADS) reinterpret_cast<qs_f4*>(smem)[i] = qs_f4{0.f, 0.f, 0.f, 0.f};
 
-  const int G = gridDim.x, ord = (blockIdx.x & 7) * (G >> 3) + (blockIdx.x >> 3);
-  const int piece = ord / a.wg_per_piece, map0 = ord - piece * a.wg_per_piece;
+  const QTapePiece wg = qt_piece(a.wg_per_piece);
   float* __restrict__ slab = a.slabs + (size_t)blockIdx.x * QW_SLAB;
   // Every second workgroup runs on -dy and hands in -G (qwgrad_reduce_kernel subtracts its slab).  Why: the matrix pipe adds
   // the 32 products of an instruction to an accumulator hundreds of times their size, and what it drops when it aligns them
   // is dropped towards minus infinity -- measured at the headline size (tests/diag_dw_by_order.py): every element of dW low by the
   // same 2e-5 of max |dW| whatever its sign, growing with the length of the sum (the same in the BFS-tile kernel's bf16 mode).
   // A bias that does not depend on the sign of the data cancels between a workgroup and its mirror.
-  const float sgn = (sideQ && (ord & 1)) ? -1.f : 1.f;
+  const float sgn = (sideQ && (wg.ord & 1)) ? -1.f : 1.f;
   qs_f4 acc[QW_PAIRS][2];
 #pragma unroll
   for (int i = 0; i < QW_PAIRS; ++i)
 #pragma unroll
     for (int j = 0; j < 2; ++j) acc[i][j] = qs_f4{0.f, 0.f, 0.f, 0.f};
 
-  const int64_t tape = (int64_t)a.prefix[a.nstrips];
-  const int64_t tape_begin = piece < a.pieces ? tape * piece / a.pieces : 0, tape_end = piece < a.pieces ? tape * (piece + 1) / a.pieces : 0;
+  // (a workgroup beyond the last piece walks an empty range: its slab must still be written)
+  const QTapeRange tape = qt_tape_range(a.prefix, a.nstrips, wg.piece, a.pieces);
   auto locate = [&](int64_t r, int64_t r_end, QStrip& st) __attribute__((always_inline)) -> int {
-    int lo = 0, hi = a.nstrips;
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if ((int64_t)a.prefix[mid] <= r) lo = mid; else hi = mid;
-    }
-    {  // (the record through scalar registers: every field is wave-uniform, and the compiler should know -- rows, clamps and the
-       // table look-ups' branches then run on the scalar unit)
-      const QStrip g = a.strips[lo];
-#define QS_U(f) st.f = __builtin_amdgcn_readfirstlane(g.f)
-      QS_U(x0); QS_U(w); QS_U(xs); QS_U(y0); QS_U(y1); QS_U(xlo); QS_U(xhi); QS_U(ylo); QS_U(yhi); QS_U(tab); QS_U(tws);
-#undef QS_U
-    }
-    const int h = st.y1 - st.y0;
-    const int off = (int)(r - (int64_t)a.prefix[lo]);
-    const int len = (int)(((int64_t)(h - off) < r_end - r) ? (int64_t)(h - off) : r_end - r);
-    st.y0 += off;
-    st.y1 = st.y0 + len;
-    return len;
+    return qt_locate(a.prefix, a.strips, a.nstrips, r, r_end, st);
   };
-  auto step_barrier = [&]() __attribute__((always_inline)) { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
 
   const unsigned srowb = sideQ ? (unsigned)a.lddy * 4u : 256u;  // bytes of a pixel's row of this wave's operand
   const int64_t srows = sideQ ? a.dy_rows : a.x_rows;
@@ -139,35 +121,12 @@ __global__ __launch_bounds__(QS_THREADS, 2) void cheb_qwgrad5_kernel(QWgradArgs 
   const unsigned wr_a = wr_com + ((QW_SWZ && (kgw & 1)) ? 32u : 0u), wr_b = wr_com + ((QW_SWZ && (kgw & 1)) ? 0u : 32u);
   const unsigned rd_off = (unsigned)(lane >> 4) * QW_SK + (unsigned)((lane & 15) ^ (QW_SWZ ? 2 * (lane >> 4) : 0)) * 16u;
 
-  // ---- L~ (waves 0..3): the row's values of the pixels 4 p + cq, filed as cheb_qstrip_kernel.h files them ---------------
-  auto cfetch = [&](const char* gv, const char* gd, unsigned offv, unsigned offd, qs_f4& cv, float& cd) __attribute__((always_inline)) {
-    cv = *reinterpret_cast<const qs_f4*>(gv + offv);
-    cd = *reinterpret_cast<const float*>(gd + offd);
-  };
-  auto cstore = [&](int slot, qs_f4 cv, float cd) __attribute__((always_inline)) {
-    unsigned char* q = smem + LDS_C + (unsigned)slot * CROWB + (unsigned)p * 16u + (unsigned)cq * 4u;
-    if (q4 < 2) {
-#pragma unroll
-      for (int d = 0; d < 4; ++d) *reinterpret_cast<float*>(q + (unsigned)(1 + 4 * q4 + d) * 256u) = cv[d];
-    }
-    if (q4 == 2) *reinterpret_cast<float*>(q) = cd;
-  };
-  auto cvec = [&](int slot, int v) __attribute__((always_inline)) -> qs_f4 {
-    return *reinterpret_cast<const qs_f4*>(smem + LDS_C + (unsigned)slot * CROWB + (unsigned)p * 16u + (unsigned)v * 256u);
-  };
-  struct C3 { qs_f4 w, c, e; };
+  // ---- L~ (waves 0..3): the row's values of the pixels 4 p + cq, filed as they are (the recurrence doubles: S2 below) ----------
+  auto cstore = [&](int slot, qs_f4 cv, float cd) __attribute__((always_inline)) { qt_cstore<false>(smem + LDS_C, slot, p, q4, cq, cv, cd); };
   // coefficient vectors (west, centre, east by tile) of the source row y-1 (which = 0), y (1), y+1 (2)
-  auto crow = [&](int slot, int which) __attribute__((always_inline)) -> C3 {
-    C3 r;
-    if (which == 0) { r.w = cvec(slot, 8); r.c = cvec(slot, 7); r.e = cvec(slot, 6); }
-    else if (which == 1) { r.w = cvec(slot, 1); r.c = cvec(slot, 0); r.e = cvec(slot, 5); }
-    else { r.w = cvec(slot, 2); r.c = cvec(slot, 3); r.e = cvec(slot, 4); }
-    return r;
-  };
+  auto crow = [&](int slot, int which) __attribute__((always_inline)) -> QCoef3 { return qt_cvec3(qt_crow(smem + LDS_C, slot, p), which); };
 
   // one plane row of this wave, split hi + lo into bf16 and staged
-  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-  typedef float f32x2 __attribute__((ext_vector_type(2)));
   auto stage = [&](int plane, const QRow& R) __attribute__((always_inline)) {
     if (QS_ABL & 8192) { asm volatile("" : : "v"(R.t[0]), "v"(R.t[1]), "v"(R.t[2]), "v"(R.t[3])); return; }  // (tuning builds: QS_ABL)
     unsigned char* qa = smem + (unsigned)plane * QW_PLANE + wr_a;
@@ -179,12 +138,9 @@ __global__ __launch_bounds__(QS_THREADS, 2) void cheb_qwgrad5_kernel(QWgradArgs 
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         const float a0 = R.t[2 * j][cc], a1 = R.t[2 * j + 1][cc];
-        const bf16x2 h = __builtin_convertvector(f32x2{a0, a1}, bf16x2);
-        const unsigned hu = __builtin_bit_cast(unsigned, h);
-        const float h0 = __builtin_bit_cast(float, hu << 16), h1 = __builtin_bit_cast(float, hu & 0xffff0000u);
-        const bf16x2 l = __builtin_convertvector(f32x2{a0 - h0, a1 - h1}, bf16x2);
-        hi[j] = hu;
-        lo[j] = __builtin_bit_cast(unsigned, l);
+        const qs_u2 hl = qt_split<false>(a0, a1);
+        hi[j] = hl[0];
+        lo[j] = hl[1];
       }
       *reinterpret_cast<qs_u2*>(q) = hi;
       *reinterpret_cast<qs_u2*>(q + QW_HL) = lo;
@@ -197,10 +153,10 @@ __global__ __launch_bounds__(QS_THREADS, 2) void cheb_qwgrad5_kernel(QWgradArgs 
 
   __syncthreads();
 
-  for (int64_t tr = tape_begin; tr < tape_end;) {
+  for (int64_t tr = tape.begin; tr < tape.end;) {
     QStrip st;
-    tr += locate(tr, tape_end, st);
-    for (int nq = map0; nq < a.N; nq += a.wg_per_piece) {
+    tr += locate(tr, tape.end, st);
+    for (int nq = wg.map0; nq < a.N; nq += a.wg_per_piece) {
       // byte offsets of this lane's four pixels in a row of the map (+ its channels), of its pixel of L~
       unsigned voff[4];
       bool colk[4];
@@ -216,19 +172,12 @@ __global__ __launch_bounds__(QS_THREADS, 2) void cheb_qwgrad5_kernel(QWgradArgs 
       }
       // (one register for the lane's tile columns, counted from the strip's first: the operand's pixels [0, 4), the pixel of L~
       // [4, 8), its Morton bits [8, 15); the five tile bases of a tile row come by scalar loads when a row enters a new tile row,
-      // as in cheb_qstrip_kernel.h)
+      // qt_tab_lane of cheb_qtape.h)
       const int Xc = min(max(st.xs + 4 * p + cq, st.xlo), st.xhi);
       const int tc0 = max(st.xs, st.xlo) >> 4;
       const unsigned pk = (unsigned)((min(max(st.xs + 4 * p, xclo), xchi) >> 4) - tc0) | ((unsigned)((Xc >> 4) - tc0) << 4) | (st_spread((unsigned)Xc & 15u) << 8);
       const char* smap = sbase + (size_t)nq * srows * srowb;
-      typedef int qs_i4 __attribute__((ext_vector_type(4)));
-      auto tab_lane = [&](unsigned ci, int yc) __attribute__((always_inline)) -> unsigned {
-        const int32_t* trow = a.tab + __builtin_amdgcn_readfirstlane(st.tab + (yc >> 4) * st.tws + tc0);
-        qs_i4 b;
-        int b4;
-        asm volatile("s_load_dwordx4 %0, %2, 0x0\n\ts_load_dword %1, %2, 0x10\n\ts_waitcnt lgkmcnt(0)" : "=&s"(b), "=&s"(b4) : "s"(trow) : "memory");
-        return (unsigned)(ci == 0 ? b[0] : ci == 1 ? b[1] : ci == 2 ? b[2] : ci == 3 ? b[3] : b4);
-      };
+      auto tab_lane = [&](unsigned ci, int yc) __attribute__((always_inline)) -> unsigned { return qt_tab_lane(a.tab, st, ci, yc); };
       const int rlo = sideQ ? st.y0 : st.ylo, rhi = sideQ ? st.y1 - 1 : st.yhi;
       // the lane's tile bases of the rows in flight: the operand's (row clamped to [rlo, rhi]) and L~'s (to [ylo, yhi])
       unsigned bV = tab_lane(pk & 15u, min(max(st.y0 - D, rlo), rhi)), bC = sideQ ? 0u : tab_lane((pk >> 4) & 15u, min(max(st.y0 - D, st.ylo), st.yhi));
@@ -259,7 +208,7 @@ __global__ __launch_bounds__(QS_THREADS, 2) void cheb_qwgrad5_kernel(QWgradArgs 
         const int yc = min(max(yrow, st.ylo), st.yhi);
         if (yrow > st.ylo && yrow <= st.yhi && (yrow & 15) == 0) bC = tab_lane((pk >> 4) & 15u, yc);
         const size_t rid = bC + ((pk >> 8) | (st_spread((unsigned)yc & 15u) << 1));
-        cfetch(reinterpret_cast<const char*>(a.gvals8) + rid * 32u, reinterpret_cast<const char*>(a.gdiag) + rid * 4u, (unsigned)(q4 & 1) * 16u, 0u, cv, cd);
+        qt_cfetch(a.gvals8, a.gdiag, rid, q4, cv, cd);
       };
       if (!sideQ) coef_fetch(ytop);
 
@@ -269,7 +218,7 @@ __global__ __launch_bounds__(QS_THREADS, 2) void cheb_qwgrad5_kernel(QWgradArgs 
         const int cs1 = cs == 0 ? 2 : cs - 1, cs2 = cs1 == 0 ? 2 : cs1 - 1;  // slots of the rows ytop-1, ytop-2
         QRow A2;  // L~ S1 at row ytop-2
         // -------- the stencil units, in the order their sources become available ------------------------------------------
-        C3 ca = crow(cs2, 0), cb = crow(cs2, 1);
+        QCoef3 ca = crow(cs2, 0), cb = crow(cs2, 1);
         auto unit = [&](auto u_c) __attribute__((always_inline)) {
           constexpr int u = decltype(u_c)::value;
           if (u < 4) QS_UNIT<true, false>(A2, S1[L0], u, ca.w, ca.c, ca.e);
@@ -351,7 +300,7 @@ __global__ __launch_bounds__(QS_THREADS, 2) void cheb_qwgrad5_kernel(QWgradArgs 
         for (int t = 0; t < 4; ++t)
 #pragma unroll
           for (int e = 0; e < 4; ++e) S2.t[t][e] = CHEB ? fmaf(2.f, A2.t[t][e], -S0[L0].t[t][e]) : A2.t[t][e];
-        step_barrier();  // every wave has read the staged row
+        qt_step_barrier();  // every wave has read the staged row
         // (the operands of the last group stay allocated until here: the compiler does not know the asm statements above are
         // matrix instructions, and a vector instruction that reuses an operand register right behind one corrupts it -- seen)
         // (fb[0] died with the last-but-one group: listed as well -- a register set that is reloaded from LDS is safe, the data
@@ -370,7 +319,7 @@ __global__ __launch_bounds__(QS_THREADS, 2) void cheb_qwgrad5_kernel(QWgradArgs 
         if (!sideQ) coef_fetch(ytop + 1);
         cs = cs == 2 ? 0 : cs + 1;
         ++ytop;
-        step_barrier();
+        qt_step_barrier();
       };
       for (int t3 = 0; t3 < T3; ++t3) {
         step(std::integral_constant<int, 0>{});

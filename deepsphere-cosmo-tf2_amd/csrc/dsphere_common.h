@@ -218,33 +218,39 @@ bool strip_shape_ok(int32_t Fin, int32_t Fout, int32_t K);
 size_t strip_wimg_bytes(int32_t Fin, int32_t Fout, int32_t K);
 int launch_cheb_strip(const StripLaunch& s, hipStream_t stream);
 
-// quad-strip kernel (cheb_qstrip.hip, round 5): the same rectangles in 64-column strips, four pixels per lane
+// quad-strip kernels (round 5, 6): the same rectangles in 64-column strips, four pixels per lane.  What the launches of the two
+// forwards share:
 struct QStrip;
-struct QStripLaunch : LaunchBase {
-  unsigned char* wimg;       // workspace: qstrip_wimg_bytes()
+struct QTapeLaunch : LaunchBase {
+  unsigned char* wimg;       // workspace: qstrip_wimg_bytes() / qstrip8_wimg_bytes()
   const QStrip* strips;      // device list of strips (uncut along y: the kernel cuts the tape of their rows by workgroup)
   const int32_t* tab = nullptr;  // device: the rectangles' tables of tile bases (QStrip::tab, ::tws)
   const int32_t* prefix;     // device [nstrips + 1]: rows of the strips before each one
   int64_t tape_rows;         // prefix[nstrips]
-  int32_t nstrips, Fin, Fout;
+  int32_t nstrips;
   bool f16 = false;          // DSPH_PREC_F16X3: the three-term split on f16 pairs instead of bf16 pairs
   int f16_xexp = 0;          // f16: x is split as x 2^f16_xexp, the store takes the factor out again (DSPH_OPT_F16_XEXP)
   bool prep_weights = true;
 };
+// How the kernels' workgroups share the work (cheb_qtape.h): G workgroups (a multiple of 8: the kernels deal XCD by XCD; one
+// per CU, fewer when a workgroup would get under 64 rows), the per-map tape of `tape_rows` rows cut into P pieces, w workgroups
+// per piece taking every w-th map.  w = N (one map each, in step on the same rows of L~) when the batch fits; otherwise the w in
+// {1, 2, 4, ...} with the shortest busiest workgroup.  Returns that workgroup's steps: its rows plus the kernel's `run_in` steps
+// per run of rows, every run rounded up to whole triples of steps (the step bodies are unrolled three times).
+int64_t qtape_split(int num_cu, int64_t tape_rows, int64_t N, int64_t mean_height, int run_in, int* grid, int* pieces, int* wg_per_piece);
+
+// K = 5, 64 -> 64 (cheb_qstrip.hip, round 5)
+struct QStripLaunch : QTapeLaunch {
+  int32_t Fin, Fout;
+};
 bool qstrip_shape_ok(int32_t Fin, int32_t Fout, int32_t K);
 size_t qstrip_wimg_bytes();
-int64_t qstrip_split(int num_cu, int64_t tape_rows, int64_t N, int64_t mean_height, int* grid, int* pieces, int* wg_per_piece);
+int64_t qstrip_split(int num_cu, int64_t tape_rows, int64_t N, int64_t mean_height, int* grid, int* pieces, int* wg_per_piece);  // qtape_split with this kernel's run-in
 int launch_cheb_qstrip(const QStripLaunch& s, hipStream_t stream);
 
-// K = 8, 32 -> 32 quad strips (cheb_qstrip8.hip, round 6)
-struct QStrip8Launch : LaunchBase {  // (Chebyshev basis only: `cheb` is not read)
-  unsigned char* wimg;       // workspace: qstrip8_wimg_bytes()
-  const QStrip* strips; const int32_t* tab; const int32_t* prefix;
-  int64_t tape_rows;
-  int32_t nstrips, ld_w;
-  bool f16 = false;          // DSPH_PREC_F16X3
-  int f16_xexp = 0;
-  bool prep_weights = true;
+// K = 8, 32 -> 32 (cheb_qstrip8.hip, round 6)
+struct QStrip8Launch : QTapeLaunch {  // (Chebyshev basis only: `cheb` is not read)
+  int32_t ld_w;
 };
 bool qstrip8_shape_ok(int32_t Fin, int32_t Fout, int32_t K);
 size_t qstrip8_wimg_bytes();
