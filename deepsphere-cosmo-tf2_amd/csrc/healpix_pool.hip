@@ -4,7 +4,13 @@
 // consecutive rows 4^p m .. 4^p (m + 1) - 1, so a pooled row reads one contiguous run of 4^p * F floats.  HBM-bound byte
 // work: a lane owns four channels of one output row (16-byte loads, consecutive lanes = consecutive channel quads, then
 // consecutive rows), nothing is staged.  Backward: mean -> dy / 4^p to every child; max -> dy to the FIRST child that holds
-// the maximum (the children are compared in row order).
+// the maximum (the children are compared in row order), every other child gets 0.
+//
+// NaN: the maximum propagates it, as the mean does by itself and as the CPU branch of HealpyPool (amax) does.  A group with a
+// NaN child yields NaN, and the backward sends dy to the first NaN child: a NaN child "holds" a NaN output.  Hence the
+// compare-selects below in place of fmaxf, which would drop a NaN (one NaN child -> a finite number, four -> -inf) and turn
+// the non-finite rows by which DSPH_PREC_F16X3 reports an out-of-range input back into finite numbers.  This is a property of
+// the stand-alone kernels only; the pooled epilogues of dsph_poly_forward_pool reduce behind a ReLU that already floors NaN.
 #include <algorithm>
 
 #include "dsphere_common.h"
@@ -33,7 +39,7 @@ __global__ __launch_bounds__(256) void healpix_pool_kernel(const float* __restri
         t[0] = src[(int64_t)i * F];
       }
 #pragma unroll
-      for (int v = 0; v < V; ++v) acc[v] = MAXP ? fmaxf(acc[v], t[v]) : acc[v] + t[v];
+      for (int v = 0; v < V; ++v) acc[v] = MAXP ? ((t[v] > acc[v] || t[v] != t[v]) ? t[v] : acc[v]) : acc[v] + t[v];  // (a NaN stays)
     }
     if (!MAXP) {
 #pragma unroll
@@ -63,7 +69,7 @@ __global__ __launch_bounds__(256) void healpix_pool_backward_kernel(const float*
       int arg = 0;
       for (int i = 0; i < group; ++i) {
         const float t = x[base + (int64_t)i * F];
-        if (t > m) { m = t; arg = i; }
+        if (t > m || (t != t && m == m)) { m = t; arg = i; }  // strictly larger, or the first NaN
       }
       for (int i = 0; i < group; ++i) dx[base + (int64_t)i * F] = i == arg ? g : 0.f;
     }

@@ -41,7 +41,13 @@ class HealpyPool(torch.nn.Module):
     """Pooling over the 4^p NEST children of a HEALPix pixel (reference ``healpy_layers.py:20-78``: a Keras
     MaxPool1D / AveragePooling1D with size = stride = 4^p on (batch, pixels, channels)).  On a HIP device: the
     ``dsph_healpix_pool`` kernels (one contiguous run of 4^p rows per output row); on the CPU (shape checks, tests without a
-    GPU) the same reduction as a strided op of the host framework.  It only works for NEST ordering."""
+    GPU) the same reduction as a strided op of the host framework.  It only works for NEST ordering.
+
+    NaN propagates on both branches, for both pooling types: a group with a NaN child pools to NaN (as ``amax`` / ``mean`` on the
+    CPU), and the gradient of the maximum goes to the first NaN child.  A layer that reports an out-of-range input as non-finite
+    rows (``DSPH_PREC_F16X3``) therefore stays loud behind a ``HealpyPool("MAX")``.  This is a property of this stand-alone layer:
+    the convolution + pooling fused in one pass (``dsph_poly_forward_pool``) reduces behind a ReLU that already floors NaN.
+    Among equal maxima the gradient goes to the first child in row order."""
 
     def __init__(self, p, pool_type="MAX", **kwargs):
         super().__init__()

@@ -1,5 +1,6 @@
-"""Float64 numpy restatement of HealpySmoothing for the tests (not collected by pytest): the passes on a given table, the
-all-pairs construction of the kernel, and the dense matrix of a table for the gradient."""
+"""Float64 numpy restatement of HealpySmoothing for the tests (not collected by pytest): the passes on a given table, one pass
+as ``_native.ell_smooth`` documents it (empty slots included), the all-pairs construction of the kernel, and the dense matrix of a
+table for the gradient."""
 
 import numpy as np
 
@@ -22,6 +23,28 @@ def apply(cols, vals, x, reps=None, mask=None):
     if mask is not None:
         m = np.asarray(mask, dtype=np.float64)
         y = y * (m[None, :, None] if m.ndim == 1 else m[None])
+    return y
+
+
+def apply_pass(cols, vals, x, reps=None, pass_index=0, mask=None):
+    """ONE pass as ``_native.ell_smooth`` documents it, with float64 sums: out[n, m, c] = sum_j vals[m, j] x[n, cols[m, j], c] for
+    the channels with reps[c] > pass_index (all of them when reps is None), x[n, m, c] for the others, times the mask ((M, 1) or
+    (M, C)) when one is given.  A table entry outside [0, M) is an empty slot: weight 0, whatever ``vals`` holds there (``apply``
+    indexes with the raw columns, where a -1 wraps to the last pixel)."""
+    cols, vals = np.asarray(cols).astype(np.int64), np.asarray(vals, dtype=np.float64)
+    x = np.asarray(x, dtype=np.float64)
+    N, M, C = x.shape
+    ok = (cols >= 0) & (cols < M)
+    w = np.where(ok, vals, 0.0)
+    safe = np.where(ok, cols, 0)
+    y = x.copy()
+    for c in range(C):
+        if reps is None or int(reps[c]) > pass_index:
+            y[:, :, c] = (x[:, :, c][:, safe] * w[None]).sum(axis=-1)
+    if mask is not None:
+        m = np.asarray(mask, dtype=np.float64)
+        assert m.shape in ((M, 1), (M, C))
+        y = y * m[None]
     return y
 
 

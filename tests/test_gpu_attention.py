@@ -5,6 +5,12 @@ Reference: tests/attention_ref.py, the reference's edge-list algorithm restated 
 sits at 2e-7 on these inputs); 1e-4 for the large-logit case, where the rounding of a logit of size 150 alone is
 150 * 2^-23 * a few = 5e-5 (torch fp32 on the CPU: 1.7e-6); the whole layer, whose GEMMs and norms are the library's, ten times
 the error the same layer shows in torch fp32 on the CPU, computed in the test.  N = 2 throughout.
+
+Lane layouts.  A row takes lpr = d / 4 lanes and a wave rpw = floor(64 / lpr) rows; a head takes LPH = depth / 4 lanes, summed
+by log2(LPH) xor shuffles.  The cases visit every instantiated depth, forward and backward (LPH 1, 2, 4, 8, 16: the shuffle loop
+has zero to four trips), and with them lpr in {1, 2, 5, 6, 12, 16, 32, 64}: rows that divide the wave (1, 2, 16, 32, 64), rows that
+leave idle lanes (5 -> 12 rows and 4 idle lanes, 6 -> 10 rows and 4 idle lanes, 12 -> 5 rows and 4 idle lanes), and d = 256 both
+as 8 heads of 32 and as 64 heads of 4 (a head per lane).
 """
 
 import functools
@@ -17,12 +23,15 @@ import attention_ref as ref
 import deepsphere
 from deepsphere import _native, gnn_transformers, healpix
 from deepsphere.healpy_layers import Healpy_Transformer, HealpyChebyshev, HealpyPool
-from helpers import rel_err
+from helpers import offset_view, padded_view, rel_err
 
 pytestmark = pytest.mark.gpu
 
 N = 2
 SHAPES = [(1, 4), (4, 16), (2, 64), (3, 16), (4, 64)]  # (3, 16): 12 lanes per row, idle lanes; (4, 64): one row per wave
+# the depths 8 and 32, and depth 4 past one lane per row: (heads, depth) -> lanes per row, rows per wave
+OTHER_DEPTHS = {(1, 8): (2, 32), (3, 8): (6, 10), (2, 32): (16, 4), (8, 32): (64, 1), (5, 4): (5, 12), (64, 4): (64, 1)}
+BACKWARD_OTHER_DEPTHS = [(1, 4), (5, 4), (3, 8), (2, 32), (8, 32)]
 
 
 @functools.lru_cache(maxsize=None)
@@ -83,6 +92,29 @@ def test_forward_parity(name, heads, depth):
     e_out, e_lse = rel_err(out, want), rel_err(lse, np.log(den))
     print(f"{name} heads {heads} depth {depth}: out {e_out:.2e} lse {e_lse:.2e}")
     assert e_out <= 1e-5 and e_lse <= 1e-5
+
+
+@pytest.mark.parametrize("heads,depth", list(OTHER_DEPTHS))
+@pytest.mark.parametrize("name", ["n4_knn", "n8_nb20", "n8_cap", "asym"])
+def test_forward_parity_at_every_depth_and_lane_layout(name, heads, depth):
+    """Depths 8 and 32 (head_sum over 2 and 8 lanes), depth 4 with several heads (no shuffle at all), rows of 2, 5, 6, 16 and 64
+    lanes; ``asym`` adds the empty row, the one-neighbour row and the 40-wide row to each."""
+    lpr, rpw = heads * depth // 4, 64 // (heads * depth // 4)
+    assert (lpr, rpw) == OTHER_DEPTHS[(heads, depth)]
+    _, rows, cols, nbr, _ = graph(name)
+    M = nbr.shape[0]
+    q, k, v, _ = inputs(M, heads * depth)
+    want, s = ref.attention_np(q, k, v, rows, cols, heads)
+    out, lse = run_forward(q, k, v, nbr, heads)
+    den = np.zeros((N, M, heads))
+    np.add.at(den, (slice(None), rows), np.exp(s))
+    want_lse = np.log(np.where(den > 0, den, 1.0))  # (a row without neighbours: 0, as the kernel's header says)
+    e_out, e_lse = rel_err(out, want), rel_err(lse, want_lse)
+    print(f"{name} heads {heads} depth {depth} lpr {lpr} rpw {rpw}: out {e_out:.2e} lse {e_lse:.2e}")
+    assert out.shape == (N, M, heads * depth) and lse.shape == (N, M, heads)
+    assert e_out <= 1e-5 and e_lse <= 1e-5
+    if name == "asym":
+        assert (out[:, 5] == 0).all() and (lse[:, 5] == 0).all()  # the empty row, exactly
 
 
 def test_strided_views_are_bitwise_the_contiguous_result():
@@ -152,6 +184,89 @@ def test_backward_parity_and_reproducibility(name, heads, depth):
     assert errs[0] <= 1e-5 and max(errs[1:]) <= 2e-5
     for a, b in zip(runs[0], runs[1]):
         assert torch.equal(a, b)  # no atomics: bit for bit
+
+
+@pytest.mark.parametrize("heads,depth", BACKWARD_OTHER_DEPTHS)
+@pytest.mark.parametrize("name", ["n4_knn", "asym"])
+def test_backward_parity_and_reproducibility_at_every_depth(name, heads, depth):
+    """The backward at the depths 4, 8 and 32: same reference, same tolerances, same bit-for-bit repeat as the test above.
+    On ``asym`` the second pass walks a table (nbrT) that is not the first pass's."""
+    _, rows, cols, nbr, nbrT = graph(name)
+    q, k, v, g = inputs(nbr.shape[0], heads * depth)
+    want = ref.attention_grads64(q, k, v, rows, cols, heads, g)
+    runs = []
+    for _ in range(2):
+        t = [torch.as_tensor(a).cuda().requires_grad_(True) for a in (q, k, v)]
+        out = gnn_transformers.scaled_dot_product_sparse_attention(t[0], t[1], t[2], nbr, nbrT, heads)
+        out.backward(torch.as_tensor(g).cuda())
+        torch.cuda.synchronize()
+        runs.append([out.detach()] + [a.grad for a in t])
+    errs = [rel_err(a.cpu().numpy(), b) for a, b in zip(runs[0], want)]
+    print(f"{name} heads {heads} depth {depth}: out {errs[0]:.2e} dq {errs[1]:.2e} dk {errs[2]:.2e} dv {errs[3]:.2e}")
+    assert errs[0] <= 1e-5 and max(errs[1:]) <= 2e-5
+    for a, b in zip(runs[0], runs[1]):
+        assert torch.equal(a, b)  # no atomics: bit for bit
+    if name == "asym":
+        assert nbrT is not nbr and (runs[0][1][:, 5] == 0).all()  # dq of the row without neighbours
+
+
+def test_misaligned_views_are_refused_before_any_launch():
+    """Storage offset of one float, and a row stride that is no multiple of four floats: the kernels read 16 bytes per lane, so
+    the C ABI refuses both, in the forward and in the backward, and launches nothing (the pre-filled outputs keep their
+    contents).  ``_native.nbr_attention`` passes the refusal on as a ValueError.  The differentiable op copies what a copy
+    can mend (the stride: a copy is a fresh, aligned allocation) and gives the contiguous call's bits; an offset view is
+    already contiguous, ``.contiguous()`` returns it unchanged, and the op raises the C ABI's error."""
+    _, _, _, nbr, nbrT = graph("asym")
+    M, heads, depth = nbr.shape[0], 2, 8
+    d = heads * depth
+    q, k, v, g = (torch.as_tensor(a).cuda() for a in inputs(M, d))
+    out, lse = _native.nbr_attention(q, k, v, nbr, heads)
+    off = [offset_view(a, 1) for a in (q, k, v)]
+    pad = [padded_view(a, 2) for a in (q, k, v)]
+    assert _native.rows_layout(pad[0]) == d + 2 and (d + 2) % 4 != 0
+    with pytest.raises(ValueError, match="must be 16-byte aligned"):
+        _native.nbr_attention(off[0], off[1], off[2], nbr, heads)
+    with pytest.raises(ValueError, match="row stride 18 must be a multiple of 4 floats"):
+        _native.nbr_attention(pad[0], pad[1], pad[2], nbr, heads)
+    with pytest.raises(ValueError, match="must be 16-byte aligned"):
+        _native.nbr_attention_backward(off[0], off[1], off[2], out, lse, g, nbr, nbrT, heads)
+    with pytest.raises(ValueError, match="row stride 18 must be a multiple of 4 floats"):
+        _native.nbr_attention_backward(pad[0], pad[1], pad[2], out, lse, g, nbr, nbrT, heads)
+
+    # the C ABI itself, on outputs filled beforehand
+    L, p, stream = _native.lib(), _native._ptr, _native._stream_ptr(q.device)
+    o_fill, l_fill = torch.full_like(out, 7.0), torch.full_like(lse, 7.0)
+    grads = [torch.full_like(out, 7.0) for _ in range(3)]
+    delta = torch.full_like(lse, 7.0)
+    W, WT = int(nbr.shape[1]), int(nbrT.shape[1])
+    for views, ld, text in ((off, d, "16-byte aligned"), (pad, d + 2, "multiple of 4 floats")):
+        rc = L.dsph_nbr_attention_forward(p(views[0]), p(views[1]), p(views[2]), ld, p(o_fill), p(l_fill), p(nbr), W, N, M, heads, depth,
+                                          0, stream)
+        assert rc == -1 and text in _native.last_error()
+        rc = L.dsph_nbr_attention_backward(p(views[0]), p(views[1]), p(views[2]), ld, p(out), p(lse), p(g), p(nbr), W, p(nbrT), WT,
+                                           p(delta), p(grads[0]), p(grads[1]), p(grads[2]), d, N, M, heads, depth, 0, stream)
+        assert rc == -1 and text in _native.last_error()
+    # misaligned gradients, everything else in order
+    goff = [offset_view(a, 1) for a in grads]
+    rc = L.dsph_nbr_attention_backward(p(q), p(k), p(v), d, p(out), p(lse), p(g), p(nbr), W, p(nbrT), WT, p(delta), p(goff[0]),
+                                       p(goff[1]), p(goff[2]), d, N, M, heads, depth, 0, stream)
+    assert rc == -1 and "16-byte aligned" in _native.last_error()
+    torch.cuda.synchronize()
+    for t in [o_fill, l_fill, delta] + grads + goff:
+        assert bool((t == 7.0).all())  # nothing ran
+
+    # the differentiable op
+    with pytest.raises(ValueError, match="must be 16-byte aligned"):
+        gnn_transformers.scaled_dot_product_sparse_attention(off[0], off[1], off[2], nbr, nbrT, heads)
+    results = []
+    for src in ((q, k, v), pad):
+        t = [a.detach().requires_grad_(True) for a in src]
+        o = gnn_transformers.scaled_dot_product_sparse_attention(t[0], t[1], t[2], nbr, nbrT, heads)
+        o.backward(g)
+        results.append([o.detach()] + [a.grad for a in t])
+    assert torch.equal(results[0][0], out)
+    for a, b in zip(results[0], results[1]):
+        assert torch.equal(a, b)  # the copies: bit for bit the contiguous call
 
 
 def test_bad_shapes_raise():

@@ -395,39 +395,9 @@ def test_kept_weight_images_and_graph_replay(Fin, Fout, K):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# the callers either side of the convolution on the device -- NEST pooling kernels, pseudo-convolutions as GEMMs
+# the callers either side of the convolution on the device -- pseudo-convolutions as GEMMs (the NEST pooling
+# kernels: tests/test_gpu_pooling.py)
 # ---------------------------------------------------------------------------------------------------------------------
-
-
-@pytest.mark.parametrize("p,F,pool_type", [(1, 16, "MAX"), (1, 16, "AVG"), (2, 5, "MAX"), (3, 7, "AVG"), (1, 64, "MAX")])
-def test_nest_pooling_kernels(p, F, pool_type):
-    """HealpyPool on the GPU (dsph_healpix_pool) against the oracle restatement of healpy_layers.py:20-85, bit for bit for
-    the maximum, to rounding for the mean; the input gradient (dsph_healpix_pool_backward) against the host framework's
-    autograd of the same reduction."""
-    from deepsphere import healpy_layers
-
-    nside, N = 16, 3
-    M = 12 * nside * nside
-    rng = np.random.default_rng(p * 100 + F)
-    x = rng.standard_normal((N, M, F)).astype(np.float32)
-    layer = healpy_layers.HealpyPool(p, pool_type)
-    xt = _dev(x).requires_grad_(True)
-    y = layer(xt)
-    ref = orc.healpy_pool(x.astype(np.float64), p, pool_type)
-    assert y.shape == ref.shape
-    if pool_type == "MAX":
-        assert np.array_equal(y.detach().cpu().numpy(), ref.astype(np.float32))
-    else:
-        assert rel_err(y.detach().cpu().numpy(), ref) < 1e-6
-    dy = rng.standard_normal(ref.shape).astype(np.float32)
-    y.backward(_dev(dy))
-    xr = torch.from_numpy(x).requires_grad_(True)
-    g = 4 ** p
-    blocks = xr.reshape(N, M // g, g, F)
-    (blocks.amax(dim=2) if pool_type == "MAX" else blocks.mean(dim=2)).backward(torch.from_numpy(dy))
-    assert rel_err(xt.grad.cpu().numpy(), xr.grad.numpy()) < 1e-6
-    with pytest.raises(IOError):
-        layer(_dev(x[:, : M - 1]))
 
 
 def test_pseudo_convolutions_against_the_oracle():

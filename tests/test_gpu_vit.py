@@ -6,6 +6,10 @@ tolerances (torch fp32 on the CPU sits at <= 1.2e-6 on these inputs); 1e-4 for t
 <= 1.1e-5); the whole layer, whose GEMMs and norms are the library's, ten times the error the same layer shows in torch fp32 on
 the CPU, computed in the test.  N = 2 throughout (N = 1 in the memory test).  The kernels' tiles are 64 rows: M = 48 is less than
 one, 65 one past one (the 260-pixel cap of nside 8 at p = 1), 192 an exact multiple, 331 several plus a ragged tail.
+
+The kernels have three code paths by depth: float4 fragments for D >= 16, float2 fragments and zero-padded A rows for D = 8,
+scalar fragments and a 4-float LDS row for D = 4.  Each is run forward and backward, off the tile grid (65, 331) and, backward, at
+M = 2, the smallest map whose dq and dk are not identically zero (with one row the softmax is the constant 1).
 """
 
 import functools
@@ -18,7 +22,7 @@ import deepsphere
 import dense_attention_ref as ref
 from deepsphere import _native, gnn_transformers
 from deepsphere.healpy_layers import Healpy_Transformer, Healpy_ViT, HealpyChebyshev
-from helpers import rel_err
+from helpers import offset_view, padded_view, rel_err
 
 pytestmark = pytest.mark.gpu
 
@@ -70,6 +74,45 @@ def test_forward_single_row_exact_tile_and_the_other_depths(M, heads, depth):
     assert e_out <= 1e-5 and e_lse <= 1e-5
 
 
+@pytest.mark.parametrize("heads,depth", [(3, 8), (2, 32)])
+@pytest.mark.parametrize("M", [48, 65, 331])
+def test_forward_depths_8_and_32_off_the_tile_grid(M, heads, depth):
+    """The float2 path (D = 8) and two 16-channel blocks (D = 32) with a ragged tail and more than one key tile."""
+    q, k, v, _ = inputs(M, heads * depth)
+    want, _, want_lse = forward_reference(M, heads, depth)
+    out, lse = run_forward(q, k, v, heads)
+    e_out, e_lse = rel_err(out, want), rel_err(lse, want_lse)
+    print(f"M {M} heads {heads} depth {depth}: out {e_out:.2e} lse {e_lse:.2e}")
+    assert e_out <= 1e-5 and e_lse <= 1e-5
+
+
+def _backward_twice(q, k, v, g, heads):
+    runs = []
+    for _ in range(2):
+        t = [torch.as_tensor(a).cuda().requires_grad_(True) for a in (q, k, v)]
+        out = gnn_transformers.scaled_dot_product_attention(t[0], t[1], t[2], heads)
+        out.backward(torch.as_tensor(g).cuda())
+        torch.cuda.synchronize()
+        runs.append([out.detach()] + [a.grad for a in t])
+    return runs
+
+
+@pytest.mark.parametrize("heads,depth", [(1, 4), (3, 4), (3, 8), (1, 8), (2, 32)])
+@pytest.mark.parametrize("M", [2, 65, 331])
+def test_backward_parity_and_reproducibility_on_the_narrow_paths(M, heads, depth):
+    """The backward of the D = 4 and D = 8 paths (and of D = 32), never compared with anything before: same reference, same
+    tolerances and the same bit-for-bit repeat as the test below."""
+    q, k, v, g = inputs(M, heads * depth)
+    want = ref.attention_grads64(q, k, v, heads, g)
+    runs = _backward_twice(q, k, v, g, heads)
+    errs = [rel_err(a.cpu().numpy(), b) for a, b in zip(runs[0], want)]
+    print(f"M {M} heads {heads} depth {depth}: out {errs[0]:.2e} dq {errs[1]:.2e} dk {errs[2]:.2e} dv {errs[3]:.2e}")
+    assert np.abs(want[1]).max() > 0 and np.abs(want[2]).max() > 0
+    assert errs[0] <= 1e-5 and max(errs[1:]) <= 2e-5
+    for a, b in zip(runs[0], runs[1]):
+        assert torch.equal(a, b)  # no atomics: bit for bit
+
+
 @pytest.mark.parametrize("heads,depth", [(4, 16), (2, 64)])
 @pytest.mark.parametrize("M", [65, 331])
 def test_backward_parity_and_reproducibility(M, heads, depth):
@@ -112,6 +155,86 @@ def test_strided_views_are_bitwise_the_contiguous_result():
     leaf2 = buf.clone().requires_grad_(True)
     gnn_transformers.scaled_dot_product_attention(leaf2[..., :d], leaf2[..., d:2 * d], leaf2[..., 2 * d:], heads).backward(g)
     assert torch.equal(leaf2.grad, leaf.grad)
+
+
+@pytest.mark.parametrize("heads,depth", [(3, 8), (1, 4)])
+def test_packed_op_on_the_narrow_paths_is_bitwise_the_contiguous_result(heads, depth):
+    """``_DenseAttentionPacked`` on a (N, M, 3 d) buffer: the D = 8 path reads float2 and the D = 4 path scalars through the
+    strided views; one gradient tensor, equal bit for bit to the three gradients of the contiguous copies side by side."""
+    M, d = 65, heads * depth
+    buf = torch.as_tensor(np.random.default_rng(1).standard_normal((N, M, 3 * d)).astype(np.float32)).cuda()
+    q, k, v = buf[..., :d], buf[..., d:2 * d], buf[..., 2 * d:]
+    assert _native.rows_layout(k) == 3 * d and not k.is_contiguous() and all(a.data_ptr() % 16 == 0 for a in (q, k, v))
+    o_view, l_view = _native.dense_attention(q, k, v, heads)
+    o_copy, l_copy = _native.dense_attention(q.contiguous(), k.contiguous(), v.contiguous(), heads)
+    assert torch.equal(o_view, o_copy) and torch.equal(l_view, l_copy)
+    g = torch.as_tensor(inputs(M, d)[3]).cuda()
+    leaf = buf.clone().requires_grad_(True)
+    out_p = gnn_transformers._DenseAttentionPacked.apply(leaf, heads)
+    out_p.backward(g)
+    t = [a.clone().contiguous().requires_grad_(True) for a in (q, k, v)]
+    out_c = gnn_transformers.scaled_dot_product_attention(t[0], t[1], t[2], heads)
+    out_c.backward(g)
+    assert torch.equal(out_p, out_c) and torch.equal(out_p, o_view)
+    assert tuple(leaf.grad.shape) == (N, M, 3 * d) and torch.equal(leaf.grad, torch.cat([a.grad for a in t], dim=2))
+    # and the packed result is the right one, not merely the same one
+    want = ref.attention_grads64(*(a.cpu().numpy() for a in (q, k, v)), heads, g.cpu().numpy())
+    errs = [rel_err(out_p.detach().cpu().numpy(), want[0])] + [rel_err(leaf.grad[..., i * d:(i + 1) * d].cpu().numpy(), want[1 + i])
+                                                               for i in range(3)]
+    print(f"packed heads {heads} depth {depth}: out {errs[0]:.2e} dq {errs[1]:.2e} dk {errs[2]:.2e} dv {errs[3]:.2e}")
+    assert errs[0] <= 1e-5 and max(errs[1:]) <= 2e-5
+
+
+def test_misaligned_views_are_refused_before_any_launch():
+    """As test_gpu_attention's: a storage offset of one float and a row stride that is no multiple of four floats are refused by
+    the C ABI, forward and backward, before anything is launched.  ``_native.dense_attention`` raises the C ABI's error; the
+    differentiable op copies a badly strided view (and then gives the contiguous call's bits) and raises on an offset view,
+    which is contiguous already, so that a copy changes nothing."""
+    M, heads, depth = 65, 2, 8
+    d = heads * depth
+    q, k, v, g = (torch.as_tensor(a).cuda() for a in inputs(M, d))
+    out, lse = _native.dense_attention(q, k, v, heads)
+    off = [offset_view(a, 1) for a in (q, k, v)]
+    pad = [padded_view(a, 2) for a in (q, k, v)]
+    assert _native.rows_layout(pad[0]) == d + 2 and (d + 2) % 4 != 0
+    with pytest.raises(ValueError, match="must be 16-byte aligned"):
+        _native.dense_attention(off[0], off[1], off[2], heads)
+    with pytest.raises(ValueError, match="row stride 18 must be a multiple of 4 floats"):
+        _native.dense_attention(pad[0], pad[1], pad[2], heads)
+    with pytest.raises(ValueError, match="must be 16-byte aligned"):
+        _native.dense_attention_backward(off[0], off[1], off[2], out, lse, g, heads)
+    with pytest.raises(ValueError, match="row stride 18 must be a multiple of 4 floats"):
+        _native.dense_attention_backward(pad[0], pad[1], pad[2], out, lse, g, heads)
+
+    L, p, stream = _native.lib(), _native._ptr, _native._stream_ptr(q.device)
+    o_fill, l_fill = torch.full_like(out, 7.0), torch.full_like(lse, 7.0)
+    grads = [torch.full_like(out, 7.0) for _ in range(3)]
+    delta = torch.full_like(lse, 7.0)
+    for views, ld, text in ((off, d, "16-byte aligned"), (pad, d + 2, "multiple of 4 floats")):
+        rc = L.dsph_dense_attention_forward(p(views[0]), p(views[1]), p(views[2]), ld, p(o_fill), p(l_fill), N, M, heads, depth, 0, stream)
+        assert rc == -1 and text in _native.last_error()
+        rc = L.dsph_dense_attention_backward(p(views[0]), p(views[1]), p(views[2]), ld, p(out), p(lse), p(g), p(delta), p(grads[0]),
+                                             p(grads[1]), p(grads[2]), d, N, M, heads, depth, 0, stream)
+        assert rc == -1 and text in _native.last_error()
+    goff = [offset_view(a, 1) for a in grads]
+    rc = L.dsph_dense_attention_backward(p(q), p(k), p(v), d, p(out), p(lse), p(g), p(delta), p(goff[0]), p(goff[1]), p(goff[2]), d, N, M,
+                                         heads, depth, 0, stream)
+    assert rc == -1 and "16-byte aligned" in _native.last_error()
+    torch.cuda.synchronize()
+    for t in [o_fill, l_fill, delta] + grads + goff:
+        assert bool((t == 7.0).all())  # nothing ran
+
+    with pytest.raises(ValueError, match="must be 16-byte aligned"):
+        gnn_transformers.scaled_dot_product_attention(off[0], off[1], off[2], heads)
+    results = []
+    for src in ((q, k, v), pad):
+        t = [a.detach().requires_grad_(True) for a in src]
+        o = gnn_transformers.scaled_dot_product_attention(t[0], t[1], t[2], heads)
+        o.backward(g)
+        results.append([o.detach()] + [a.grad for a in t])
+    assert torch.equal(results[0][0], out)
+    for a, b in zip(results[0], results[1]):
+        assert torch.equal(a, b)  # the copies: bit for bit the contiguous call
 
 
 def test_large_logits_do_not_overflow():

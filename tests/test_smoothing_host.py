@@ -154,3 +154,36 @@ def test_in_a_healpy_gcnn():
     model = HealpyGCNN(8, idx, [smooth, HealpyChebyshev(K=3, Fout=4, device="cpu")])
     assert model[0] is smooth and np.array_equal(model.indices_out, idx) and model.nside_out == 8
     assert "HealpySmoothing" in healpy_layers.__all__
+
+
+def test_single_pass_helper_against_the_dense_matrix_with_empty_slots():
+    """``smoothing_ref.apply_pass`` (the reference of the GPU tests on synthetic tables) against ``dense()``: entries outside
+    [0, M) carry weight 0 wherever they stand in a row, a row of nothing else gives 0, and ``reps`` / ``pass_index`` / mask select
+    and scale as ``_native.ell_smooth`` documents."""
+    rng = np.random.default_rng(0)
+    M, W, C = 37, 49, 4
+    cols = rng.integers(0, M, size=(M, W)).astype(np.int32)
+    vals = rng.random((M, W)).astype(np.float32)
+    bad = rng.random((M, W)) < 1 / 3
+    bad[11] = True                                                   # a row without a valid entry
+    cols[bad] = rng.choice(np.array([-1, M, M + 5, 2**31 - 1], dtype=np.int32), size=int(bad.sum()))
+    assert bad[:, 0].any() and bad[:, W // 2].any() and not bad[:, -1].all()  # anywhere in the row, not only at its end
+    x = rng.standard_normal((2, M, C))
+    K = ref.dense(np.where(bad, 0, cols), np.where(bad, 0.0, vals))  # the valid entries alone
+    want = np.einsum("mk,nkc->nmc", K, x)
+    got = ref.apply_pass(cols, vals, x)
+    assert np.abs(got - want).max() <= 1e-12 * W and (got[:, 11] == 0).all()
+    # the raw-column helper is a different function on such a table (a -1 wraps to the last pixel)
+    wrapped = np.where(cols == -1, cols, np.where(bad, 0, cols))
+    assert np.abs(ref.apply(wrapped, np.where(bad & (cols != -1), 0.0, vals), x) - want).max() > 1e-3
+    # on a table without empty slots the two helpers agree
+    clean = rng.integers(0, M, size=(M, W)).astype(np.int32)
+    assert np.array_equal(ref.apply_pass(clean, vals, x), ref.apply(clean, vals, x))
+    # reps, pass_index and masks
+    reps = [0, 1, 3, 2]
+    for mask in (rng.random((M, 1)), rng.random((M, C))):
+        for pass_index in range(3):
+            out = ref.apply_pass(cols, vals, x, reps, pass_index, mask)
+            for c in range(C):
+                src = want if reps[c] > pass_index else x
+                assert np.abs(out[:, :, c] - src[:, :, c] * mask[None, :, c % mask.shape[1]]).max() <= 1e-12 * W
