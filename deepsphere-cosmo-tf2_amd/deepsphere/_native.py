@@ -129,6 +129,10 @@ SIGNATURES = {
     "dsph_bn_apply": (ctypes.c_int, [_c_vp, _c_vp, _c_i64, _c_i32, _c_vp, _c_vp, _c_vp, _c_vp, _c_i32, ctypes.c_int, _c_vp]),
     "dsph_bn_backward": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i32, _c_i32, _c_vp,
                                          ctypes.c_size_t, ctypes.c_int, _c_vp]),
+    "dsph_ln_workspace_bytes": (ctypes.c_size_t, [_c_i64, _c_i32]),
+    "dsph_ln_forward": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i32, ctypes.c_float, _c_vp, _c_vp, ctypes.c_int, _c_vp]),
+    "dsph_ln_backward": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, _c_vp, ctypes.c_float, _c_vp, _c_vp, _c_vp, _c_i64, _c_i32, _c_vp, ctypes.c_size_t,
+                                         ctypes.c_int, _c_vp]),
 }
 
 
@@ -833,3 +837,82 @@ def bn_backward(y, z, dz, mean, rstd, gamma=None, act=ACT_NONE, want_dgamma=True
                                 workspace.numel() * workspace.element_size(), y.device.index, _stream_ptr(y.device))
     check(rc, "dsph_bn_backward")
     return dy, dgamma, dshift, workspace
+
+
+LN_MAX_D = 1024  # the widest row the layer-norm kernels hold in registers (csrc/layer_norm.hip)
+
+
+def ln_workspace_bytes(rows, d):
+    """Bytes of scratch ``ln_backward`` needs for the parameter gradients of a (rows, d) map (``dsph_ln_workspace_bytes``): a
+    function of the shape alone, 16 d P with P = max(1, min(2048, ceil(rows / 4), ceil(rows d / 8192))); 0 for rows = 0."""
+    return int(lib().dsph_ln_workspace_bytes(int(rows), int(d)))
+
+
+def _ln_map(t, name, like=None):
+    import torch
+
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() >= 1 and t.is_contiguous()):
+        raise ValueError(f"{name} must be a contiguous float32 (..., d) HIP tensor")
+    if like is not None and (t.shape != like.shape or t.device != like.device):
+        raise ValueError(f"{name} must have x's shape and device")
+    d = int(t.shape[-1])
+    return t.numel() // max(d, 1), d
+
+
+def ln_forward(x, gamma, beta, eps, res=None, out=None, sum_out=None):
+    """Layer norm over the trailing axis of ``x`` (..., d), the residual add in front fused (``dsph_ln_forward``): without ``res``
+    -> z = LN(x) * gamma + beta; with ``res`` (x's shape) -> (z, sum) with sum = x + res and z = LN(sum) * gamma + beta.  ``gamma`` /
+    ``beta``: [d] or None (1 / 0).  ``out``: where z goes (allocated when None); ``sum_out``: where the sum goes -- ``x`` or ``res``
+    themselves for in place, allocated when None.  One launch on the current stream."""
+    import torch
+
+    require_gpu()
+    rows, d = _ln_map(x, "x")
+    _bn_vec(gamma, d, x.device, "gamma")
+    _bn_vec(beta, d, x.device, "beta")
+    if res is not None:
+        _ln_map(res, "res", x)
+        if sum_out is None:
+            sum_out = torch.empty_like(x)
+        else:
+            _ln_map(sum_out, "sum_out", x)
+    elif sum_out is not None:
+        raise ValueError("sum_out without res")
+    if out is None:
+        out = torch.empty_like(x)
+    else:
+        _ln_map(out, "out", x)
+    if rows:  # (a map without rows has no address to pass)
+        rc = lib().dsph_ln_forward(_ptr(x), _ptr(res), _ptr(sum_out), _ptr(out), rows, d, float(eps), _ptr(gamma), _ptr(beta), x.device.index,
+                                   _stream_ptr(x.device))
+        check(rc, "dsph_ln_forward")
+    return out if res is None else (out, sum_out)
+
+
+def ln_backward(a, dz, gamma, eps, dsum=None, want_dgamma=True, want_dbeta=True, workspace=None):
+    """Gradients of ``ln_forward`` (``dsph_ln_backward``): -> (da, dgamma or None, dbeta or None, workspace) from the forward's
+    normalised input ``a`` (its sum output, or x when there was no res), the gradient ``dz`` of z and the gradient ``dsum`` that
+    reached the sum output (None: none).  ``da`` is the gradient of x and of res alike.  Deterministic; two launches (one when no
+    parameter gradient is wanted)."""
+    import torch
+
+    require_gpu()
+    rows, d = _ln_map(a, "a")
+    _ln_map(dz, "dz", a)
+    if dsum is not None:
+        _ln_map(dsum, "dsum", a)
+    _bn_vec(gamma, d, a.device, "gamma")
+    if want_dgamma or want_dbeta:
+        need = ln_workspace_bytes(rows, d)
+        if workspace is None or workspace.device != a.device or workspace.numel() * workspace.element_size() < need:
+            workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=a.device)
+    da = torch.empty_like(a)
+    new = torch.zeros if rows == 0 else torch.empty  # (the sums over no rows are zero)
+    dgamma = new(d, dtype=torch.float32, device=a.device) if want_dgamma else None
+    dbeta = new(d, dtype=torch.float32, device=a.device) if want_dbeta else None
+    if rows:  # (a map without rows has no address to pass)
+        rc = lib().dsph_ln_backward(_ptr(a), _ptr(dz), _ptr(dsum), _ptr(gamma), float(eps), _ptr(da), _ptr(dgamma), _ptr(dbeta), rows, d,
+                                    _ptr(workspace), 0 if workspace is None else workspace.numel() * workspace.element_size(),
+                                    a.device.index, _stream_ptr(a.device))
+        check(rc, "dsph_ln_backward")
+    return da, dgamma, dbeta, workspace

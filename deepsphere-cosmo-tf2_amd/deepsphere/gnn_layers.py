@@ -237,6 +237,74 @@ class _BatchNormActFunction(torch.autograd.Function):
                 None, None, None)
 
 
+def _ln_native_ok(mod, x):
+    """Do the layer-norm kernels (csrc/layer_norm.hip) cover this call of the ``torch.nn.LayerNorm`` ``mod``?  A float32 map on a
+    HIP device, normalised over its single trailing axis of 1 <= d <= 1024 channels, parameters (if any) float32 on the same
+    device.  Everything else keeps the host framework's layer norm: CPU tensors, other dtypes, the joint norm over pixels and
+    channels (``bn_kwargs={"axis": (1, 2)}``), d > 1024 (a row no longer fits the registers of one wave)."""
+    if not (isinstance(mod, torch.nn.LayerNorm) and isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32):
+        return False
+    if len(mod.normalized_shape) != 1 or x.dim() < 2 or x.shape[-1] != mod.normalized_shape[0]:
+        return False
+    if not (1 <= x.shape[-1] <= _native.LN_MAX_D) or not mod.eps > 0:
+        return False
+    for t in (mod.weight, mod.bias):
+        if t is not None and (t.dtype != torch.float32 or t.device != x.device):
+            return False
+    return True
+
+
+class _LayerNormFunction(torch.autograd.Function):
+    """z = LN(x + res) * weight + bias over the trailing axis, as one differentiable op over ``dsph_ln_forward`` /
+    ``dsph_ln_backward``: one launch forward (x and res read once, z and the sum written once), two backward.
+
+    ``apply(x, res, weight, bias, eps)``: ``res`` None -> z = LN(x); with ``res`` -> (z, sum), sum = x + res being the block's next
+    residual.  ``weight`` / ``bias``: tensors of d elements or None (no affine).  The backward takes the gradients of both outputs
+    and returns the one input gradient for x and for res; mean and rstd are recomputed there from the saved sum (or x): nothing
+    else is kept."""
+
+    @staticmethod
+    def forward(ctx, x, res, weight, bias, eps):
+        x = x.contiguous()
+        g = None if weight is None else weight.detach().reshape(-1).contiguous()
+        b = None if bias is None else bias.detach().reshape(-1).contiguous()
+        ctx.eps = float(eps)
+        ctx.set_materialize_grads(False)  # (an output nothing used arrives as None, not as a map of zeros to read)
+        ctx.shapes = (None if weight is None else weight.shape, None if bias is None else bias.shape)
+        ctx.has_res = res is not None
+        if res is None:
+            z = _native.ln_forward(x, g, b, eps)
+            ctx.save_for_backward(x, g)
+            return z
+        z, a = _native.ln_forward(x, g, b, eps, res=res.contiguous())
+        ctx.save_for_backward(a, g)
+        return z, a
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dz, dsum=None):
+        a, g = ctx.saved_tensors
+        wshape, bshape = ctx.shapes
+        if dz is None:  # (only the sum was used downstream)
+            dz = torch.zeros_like(a)
+        da, dgamma, dbeta, _ = _native.ln_backward(
+            a, dz.contiguous(), g, ctx.eps, dsum=None if dsum is None else dsum.contiguous(),
+            want_dgamma=wshape is not None and ctx.needs_input_grad[2], want_dbeta=bshape is not None and ctx.needs_input_grad[3])
+        return (da if ctx.needs_input_grad[0] else None, da if ctx.has_res and ctx.needs_input_grad[1] else None,
+                None if dgamma is None else dgamma.reshape(wshape), None if dbeta is None else dbeta.reshape(bshape), None)
+
+
+def _layer_norm(mod, x, res=None):
+    """``mod`` (a ``torch.nn.LayerNorm``) of x, or of x + res -> z, or (z, x + res): through the kernels where ``_ln_native_ok``
+    says so, by the host framework otherwise."""
+    if _ln_native_ok(mod, x) and (res is None or (res.shape == x.shape and res.dtype == x.dtype and res.device == x.device)):
+        return _LayerNormFunction.apply(x, res, mod.weight, mod.bias, mod.eps)
+    if res is None:
+        return mod(x)
+    a = x + res
+    return mod(a), a
+
+
 class Chebyshev(torch.nn.Module):
     """A graph convolutional layer using the Chebyshev approximation.
 
@@ -868,7 +936,8 @@ class GCNN_ResidualLayer(torch.nn.Module):
             return y
         axes = [a % x.dim() for a in mod._axes]
         if axes == list(range(x.dim() - len(axes), x.dim())):
-            return mod(x)
+            # the trailing axis alone (the default): the layer-norm kernels, in training and in inference; the module holds the parameters
+            return _layer_norm(mod, x)
         raise NotImplementedError("layer_norm over non-trailing axes")
 
     def forward(self, input_tensor, training=False):

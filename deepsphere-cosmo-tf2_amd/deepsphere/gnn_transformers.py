@@ -6,8 +6,9 @@ embedding lookups that materialise q, k and v per edge, ``exp`` and two segment 
 and two backward (``csrc/nbr_attention.hip``) working on channels-last (N, M, d) maps and a padded neighbour table.  The dense
 attention of ``Graph_ViT`` -- in the reference two ``matmul``s around a softmax over a materialised (N, heads, M, M) tensor
 (``:14-51``) -- is a flash-style kernel on the exact-fp32 MFMA (``csrc/dense_attention.hip``: key tiles through LDS, online
-softmax, no logit in memory; two deterministic backward launches) on the same layout.  The dense layers and layer norms around
-both are the host framework's, like the GEMM of ``HealpyPseudoConv``.
+softmax, no logit in memory; two deterministic backward launches) on the same layout.  The layer norms around both, with the add
+between them, run on the layer-norm kernels (``csrc/layer_norm.hip``); the dense layers are the host framework's, like the GEMM of
+``HealpyPseudoConv``.
 """
 
 import numpy as np
@@ -15,7 +16,7 @@ import torch
 from scipy import sparse
 
 from . import _native
-from .gnn_layers import _resolve_activation
+from .gnn_layers import _layer_norm, _resolve_activation
 from .utils import adjacency_to_ell
 
 
@@ -251,7 +252,7 @@ class MultiHeadAttention(torch.nn.Module):
         self.d_model, self.num_heads, self.use_norm = int(d_model), int(num_heads), bool(use_norm)
         self.depth = self.d_model // self.num_heads
         self.dense_attention = bool(dense)
-        self.activation, _ = _resolve_activation(activation)
+        self.activation, self._act_code = _resolve_activation(activation)
         if sparse_A_indices is not None:
             nbr, nbrT = _tables_from_indices(sparse_A_indices)
             self.register_buffer("nbr", nbr, persistent=False)
@@ -285,14 +286,24 @@ class MultiHeadAttention(torch.nn.Module):
             raise NotImplementedError("MultiHeadAttention without neighbour tables is dense attention over all pixels (the "
                                       "reference's Graph_ViT path): construct the block with dense=True to run it")
         _require_hip(inputs)
-        x = self.layer_norm1(inputs)
+        # the norms run on the layer-norm kernels (csrc/layer_norm.hip), the add between them inside the second one's launch
+        x = _layer_norm(self.layer_norm1, inputs) if self.use_norm else inputs
         qkv = self.wqkv(x)  # (N, M, 3 d): q | k | v
         if self.dense_attention:
             att = _DenseAttentionPacked.apply(qkv, self.num_heads)
         else:
             att = _SparseAttentionPacked.apply(qkv, nbr, nbrT, self.num_heads)
-        att = x + att
-        out = self.dense(self.layer_norm2(att))
+        if self.use_norm:
+            y, att = _layer_norm(self.layer_norm2, att, x)  # att <- x + att, y = LN(att): one pass
+        else:
+            att = x + att
+            y = att
+        out = self.dense(y)
+        # without autograd the tail act(out) + att is ONE pass in place over the GEMM's fresh output (dsph_residual_epilogue);
+        # with autograd on, or an activation the kernels have no code for, the host framework composes it
+        if (not (torch.is_grad_enabled() and (out.requires_grad or att.requires_grad)) and out.dtype == torch.float32
+                and (self.activation is None or self._act_code is not None) and out.is_contiguous()):
+            return _native.residual_epilogue(out, att.contiguous(), 1.0, _native.ACT_NONE if self.activation is None else self._act_code, True)
         if self.activation is not None:
             out = self.activation(out)
         return out + att

@@ -542,6 +542,40 @@ int dsph_bn_backward(const float* y, const float* z, const float* dz, const floa
                      float* dgamma, float* dshift, int64_t rows, int32_t F, int32_t act, void* workspace, size_t workspace_bytes, int device,
                      void* hip_stream);
 
+/* Layer normalisation over the trailing axis of a channels-last map (plan-free; csrc/layer_norm.hip), the residual add in front of
+ * it fused:
+ *     a[r, :] = x[r, :] + res[r, :]   (written to sum; res and sum both NULL: a = x)
+ *     z[r, c] = (a[r, c] - mean[r]) * rstd[r] * gamma[c] + beta[c],   mean, var (biased) over the d channels of row r,
+ *                                                                      rstd = 1 / sqrt(var + eps)
+ * x, res, sum, z device (rows, d) fp32, contiguous, rows = N * M; gamma, beta device [d] or NULL (1 and 0).  Replaces the Keras
+ * LayerNormalization(axis=-1) of GCNN_ResidualLayer (reference gnn_layers.py:373-374) and the two of a transformer block with
+ * the add between them (gnn_transformers.py:149-245), and their gradients from TensorFlow's autodiff.
+ * 1 <= d <= 1024 (a row lives in the registers of 1 .. 64 lanes; 16-byte accesses where d % 4 == 0 and every map of the call is
+ * 16-byte aligned, scalar ones otherwise); rows up to 2^40 (DSPH_E_UNSUPPORTED beyond); every offset is 64-bit; rows == 0 succeeds
+ * without a launch.  The row's mean, its centred sum of squares (never E[a^2] - E[a]^2), rstd and x^ are float64.
+ * Bad arguments (a required pointer NULL, res without sum or sum without res, rows < 0, d outside [1, 1024], eps <= 0, a written
+ * map overlapping another map of the call, a workspace that is NULL or misaligned): DSPH_E_BADARG with the entry point named in
+ * the message; a workspace that is too small: DSPH_E_WORKSPACE; both before any HIP call.  The one overlap allowed is sum == x or
+ * sum == res (in place, the same pointer).  Every call only enqueues on `hip_stream`: no allocation, no synchronisation, no
+ * atomics -- legal under stream capture, and two calls on the same input give the same bits.  A row that holds a NaN or Inf gives
+ * a non-finite row of z and da (and non-finite dgamma, dbeta) and leaves every other row as it would be without it.
+ * The forward is ONE launch: every input is read once, every output written once. */
+int dsph_ln_forward(const float* x, const float* res, float* sum, float* z, int64_t rows, int32_t d, float eps, const float* gamma,
+                    const float* beta, int device, void* hip_stream);
+/* The backward, from the forward's normalised input a (sum, or x when there was no res), the upstream gradient dz of z and the
+ * gradient dsum that reached the sum output (NULL: none):
+ *     x^ = (a - mean) * rstd   (mean and rstd recomputed from a in float64: nothing is saved between the two calls)
+ *     g = dz * gamma,   da = rstd * (g - mean_d(g) - x^ * mean_d(g x^)) + dsum      (the gradient of x and of res alike)
+ *     dbeta[c] = sum_r dz,   dgamma[c] = sum_r dz x^                                 (device [d] or NULL: not wanted)
+ * da: device (rows, d), overlapping none of a, dz, dsum (those three are only read and may coincide).  Two launches: the row
+ * pass, whose P = max(1, min(2048, ceil(rows / 4), ceil(rows * d / 8192))) workgroups each leave one float64 partial per channel
+ * in the workspace, and the merge of the P partials in a fixed order (skipped, and no workspace needed, when neither dgamma nor
+ * dbeta is wanted).  Workspace: caller-owned, 8-byte aligned, dsph_ln_workspace_bytes(rows, d) = 16 * d * P bytes, a function of
+ * the shape alone (0 for a shape the entry points do not take, and for rows == 0). */
+size_t dsph_ln_workspace_bytes(int64_t rows, int32_t d);
+int dsph_ln_backward(const float* a, const float* dz, const float* dsum, const float* gamma, float eps, float* da, float* dgamma,
+                     float* dbeta, int64_t rows, int32_t d, void* workspace, size_t workspace_bytes, int device, void* hip_stream);
+
 const char* dsph_last_error(void);
 int dsph_abi_version(void);
 
