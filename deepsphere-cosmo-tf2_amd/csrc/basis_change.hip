@@ -10,24 +10,11 @@
 // per step (deterministic; the tests' bound is derived from this order), the Kp rows of w it reads are Kp coalesced row
 // segments, its Kp coefficients one column (or row) of a table of at most 16 KB that stays in the caches.  One writer per
 // element, no atomics, no shared memory.  Every element offset is 64-bit.
-#include "dsphere_common.h"
+#include "dsphere_mapops.h"
 
 namespace dsph {
 
 namespace {
-
-__device__ __forceinline__ void ldv(const float* p, float (&r)[1]) { r[0] = *p; }
-__device__ __forceinline__ void ldv(const float* p, float (&r)[2]) {
-  const float2 t = *reinterpret_cast<const float2*>(p);
-  r[0] = t.x; r[1] = t.y;
-}
-__device__ __forceinline__ void ldv(const float* p, float (&r)[4]) {
-  const float4 t = *reinterpret_cast<const float4*>(p);
-  r[0] = t.x; r[1] = t.y; r[2] = t.z; r[3] = t.w;
-}
-__device__ __forceinline__ void stv(float* p, const float (&r)[1]) { *p = r[0]; }
-__device__ __forceinline__ void stv(float* p, const float (&r)[2]) { *reinterpret_cast<float2*>(p) = make_float2(r[0], r[1]); }
-__device__ __forceinline__ void stv(float* p, const float (&r)[4]) { *reinterpret_cast<float4*>(p) = make_float4(r[0], r[1], r[2], r[3]); }
 
 // total = Fin * Kp * (Fout / VEC) threads do work; thread t: column vector q = t % nv of output row r = t / nv = f * Kp + j
 template <int VEC>
@@ -71,25 +58,20 @@ int dsph_basis_change(const float* w, const float* coeff, float* w_out, int32_t 
   if (transpose != 0 && transpose != 1) { set_error("basis_change: transpose = %d, must be 0 or 1", (int)transpose); return DSPH_E_BADARG; }
   const int64_t elems = (int64_t)Fin * Kp * Fout;  // < 2^31 * 64 * 2^31: fits
   if (elems > ((int64_t)1 << 40)) { set_error("basis_change: Fin * Kp * Fout = %lld elements", (long long)elems); return DSPH_E_UNSUPPORTED; }
-  const uintptr_t bytes = (uintptr_t)elems * sizeof(float), wa = reinterpret_cast<uintptr_t>(w), oa = reinterpret_cast<uintptr_t>(w_out);
-  if (wa < oa + bytes && oa < wa + bytes) {
+  const size_t bytes = (size_t)elems * sizeof(float);
+  if (ranges_overlap(w, bytes, w_out, bytes)) {
     set_error("basis_change: w and w_out overlap; every output row reads Kp input rows and the map cannot run in place");
     return DSPH_E_BADARG;
   }
-  const uintptr_t ca = reinterpret_cast<uintptr_t>(coeff), cbytes = (uintptr_t)Kp * Kp * sizeof(float);
-  if (ca < oa + bytes && oa < ca + cbytes) { set_error("basis_change: coeff and w_out overlap"); return DSPH_E_BADARG; }
-  const int VEC = (Fout % 4 == 0 && ((wa | oa) & 15) == 0) ? 4 : (Fout % 2 == 0 && ((wa | oa) & 7) == 0) ? 2 : 1;
+  if (ranges_overlap(coeff, (size_t)Kp * Kp * sizeof(float), w_out, bytes)) { set_error("basis_change: coeff and w_out overlap"); return DSPH_E_BADARG; }
+  const int VEC = vec_width(Fout, ptr_bits({w, w_out}), true);
   const int64_t total = elems / VEC;
   const int64_t nblk = (total + 255) / 256;
   if (nblk > 0x7fffffffLL) { set_error("basis_change: grid too large (%lld workgroups)", (long long)nblk); return DSPH_E_UNSUPPORTED; }
   DeviceGuard guard(device);
-  if (!guard.ok) { set_error("basis_change: cannot select device %d", device); return DSPH_E_BADARG; }
-  hipStream_t stream = (hipStream_t)hip_stream;
-  switch (VEC) {
-    case 4: hipLaunchKernelGGL((basis_change_kernel<4>), dim3((unsigned)nblk), dim3(256), 0, stream, w, coeff, w_out, (int)Fout, (int)Kp, (int)transpose, total); break;
-    case 2: hipLaunchKernelGGL((basis_change_kernel<2>), dim3((unsigned)nblk), dim3(256), 0, stream, w, coeff, w_out, (int)Fout, (int)Kp, (int)transpose, total); break;
-    default: hipLaunchKernelGGL((basis_change_kernel<1>), dim3((unsigned)nblk), dim3(256), 0, stream, w, coeff, w_out, (int)Fout, (int)Kp, (int)transpose, total); break;
-  }
+  if (!select_device("basis_change", device, guard)) return DSPH_E_BADARG;
+  DSPH_LAUNCH_BY_VEC(VEC, basis_change_kernel, dim3((unsigned)nblk), dim3(256), (hipStream_t)hip_stream, w, coeff, w_out, (int)Fout, (int)Kp,
+                     (int)transpose, total);
   DSPH_HIP(hipGetLastError());
   return DSPH_OK;
 }

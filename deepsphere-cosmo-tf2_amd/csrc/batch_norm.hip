@@ -29,7 +29,7 @@
 //     down to (g1 - g2) / 2 * (1 - x^2), 4e-5 of the gradient at eps = 1e-5 -- one fp32 rounding of mean or rstd is 5 % of that.
 //
 // Nothing here allocates, synchronises or reads the host: every launch goes on the caller's stream and is legal under capture.
-#include "dsphere_common.h"
+#include "dsphere_mapops.h"
 
 namespace dsph {
 
@@ -57,23 +57,6 @@ struct BnGeo {
   int64_t nblk;  // workgroups along the rows (grid.y): the reductions' P, or the elementwise kernels' own count
   int32_t F, nv, cw, rpi;
 };
-
-template <int VEC> __device__ __forceinline__ void ldv(const float* p, float (&r)[VEC]);
-template <> __device__ __forceinline__ void ldv<1>(const float* p, float (&r)[1]) { r[0] = *p; }
-template <> __device__ __forceinline__ void ldv<2>(const float* p, float (&r)[2]) {
-  const float2 t = *reinterpret_cast<const float2*>(p);
-  r[0] = t.x; r[1] = t.y;
-}
-template <> __device__ __forceinline__ void ldv<4>(const float* p, float (&r)[4]) {
-  const float4 t = *reinterpret_cast<const float4*>(p);
-  r[0] = t.x; r[1] = t.y; r[2] = t.z; r[3] = t.w;
-}
-template <int VEC> __device__ __forceinline__ void stv(float* p, const float (&r)[VEC]);
-template <> __device__ __forceinline__ void stv<1>(float* p, const float (&r)[1]) { *p = r[0]; }
-template <> __device__ __forceinline__ void stv<2>(float* p, const float (&r)[2]) { *reinterpret_cast<float2*>(p) = make_float2(r[0], r[1]); }
-template <> __device__ __forceinline__ void stv<4>(float* p, const float (&r)[4]) {
-  *reinterpret_cast<float4*>(p) = make_float4(r[0], r[1], r[2], r[3]);
-}
 
 // this lane's place: row slot r, first channel c0 (of VEC), whether it holds a column at all
 struct BnLane {
@@ -467,13 +450,6 @@ __global__ __launch_bounds__(BN_THREADS) void bn_bwd_apply_kernel(const float* y
   }
 }
 
-// VEC by the channel count and the alignment of every map pointer of the call
-int bn_vec(int32_t F, uintptr_t ptr_bits) {
-  if (F % 4 == 0 && (ptr_bits & 15) == 0) return 4;
-  if (F % 2 == 0 && (ptr_bits & 7) == 0) return 2;
-  return 1;
-}
-
 // `nblk` <= 0: the elementwise kernels' own split of the rows (one workgroup per 4 chunks, at most 16,384 workgroups)
 BnGeo bn_geo(int64_t rows, int32_t F, int vec, int64_t nblk) {
   BnGeo g;
@@ -538,23 +514,15 @@ int dsph_bn_stats(const float* y, int64_t rows, int32_t F, float eps, float* mea
     set_error("bn_stats: rows = 1 has no unbiased variance to update running_var with");
     return DSPH_E_BADARG;
   }
-  if (workspace_bytes < bn_workspace_bytes(rows, F)) {
-    set_error("bn_stats: workspace of %zu bytes, %zu needed", workspace_bytes, bn_workspace_bytes(rows, F));
-    return DSPH_E_WORKSPACE;
-  }
-  if (reinterpret_cast<uintptr_t>(workspace) & 7) { set_error("bn_stats: workspace is not 8-byte aligned"); return DSPH_E_BADARG; }
+  if (!workspace_ok("bn_stats", workspace, workspace_bytes, bn_workspace_bytes(rows, F), &rc)) return rc;
   const int64_t P = bn_partials(rows, F);
-  const int vec = bn_vec(F, reinterpret_cast<uintptr_t>(y));
+  const int vec = vec_width(F, ptr_bits({y}), true);
   const BnGeo g = bn_geo(rows, F, vec, P);
   double* part = static_cast<double*>(workspace);
   DeviceGuard guard(device);
-  if (!guard.ok) { set_error("bn_stats: cannot select device %d", device); return DSPH_E_BADARG; }
+  if (!select_device("bn_stats", device, guard)) return DSPH_E_BADARG;
   hipStream_t stream = (hipStream_t)hip_stream;
-  switch (vec) {
-    case 4: hipLaunchKernelGGL((bn_stats_partial_kernel<4>), bn_grid(g), dim3(BN_THREADS), 0, stream, y, part, g); break;
-    case 2: hipLaunchKernelGGL((bn_stats_partial_kernel<2>), bn_grid(g), dim3(BN_THREADS), 0, stream, y, part, g); break;
-    default: hipLaunchKernelGGL((bn_stats_partial_kernel<1>), bn_grid(g), dim3(BN_THREADS), 0, stream, y, part, g); break;
-  }
+  DSPH_LAUNCH_BY_VEC(vec, bn_stats_partial_kernel, bn_grid(g), dim3(BN_THREADS), stream, y, part, g);
   DSPH_HIP(hipGetLastError());
   hipLaunchKernelGGL(bn_stats_final_kernel, dim3((unsigned)F), dim3(BN_THREADS), 0, stream, (const double*)part, rows, P, F, eps, mean, var,
                      rstd, mean_lo, rstd_lo, running_mean, running_var, momentum);
@@ -569,16 +537,12 @@ int dsph_bn_apply(const float* y, float* z, int64_t rows, int32_t F, const float
   if (!y || !z || !mean || !rstd) { set_error("bn_apply: NULL pointer (y, z, mean and rstd are required)"); return DSPH_E_BADARG; }
   if (!bn_shape_ok("bn_apply", rows, F, &rc)) return rc;
   if (act < DSPH_ACT_NONE || act > DSPH_ACT_TANH) { set_error("bn_apply: unknown activation %d", (int)act); return DSPH_E_BADARG; }
-  const int vec = bn_vec(F, reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(z));
+  const int vec = vec_width(F, ptr_bits({y, z}), true);
   const BnGeo g = bn_geo(rows, F, vec, 0);
   DeviceGuard guard(device);
-  if (!guard.ok) { set_error("bn_apply: cannot select device %d", device); return DSPH_E_BADARG; }
+  if (!select_device("bn_apply", device, guard)) return DSPH_E_BADARG;
   hipStream_t stream = (hipStream_t)hip_stream;
-  switch (vec) {
-    case 4: hipLaunchKernelGGL((bn_apply_kernel<4>), bn_grid(g), dim3(BN_THREADS), 0, stream, y, z, mean, rstd, gamma, shift, (int)act, g); break;
-    case 2: hipLaunchKernelGGL((bn_apply_kernel<2>), bn_grid(g), dim3(BN_THREADS), 0, stream, y, z, mean, rstd, gamma, shift, (int)act, g); break;
-    default: hipLaunchKernelGGL((bn_apply_kernel<1>), bn_grid(g), dim3(BN_THREADS), 0, stream, y, z, mean, rstd, gamma, shift, (int)act, g); break;
-  }
+  DSPH_LAUNCH_BY_VEC(vec, bn_apply_kernel, bn_grid(g), dim3(BN_THREADS), stream, y, z, mean, rstd, gamma, shift, (int)act, g);
   DSPH_HIP(hipGetLastError());
   return DSPH_OK;
 }
@@ -599,34 +563,23 @@ int dsph_bn_backward(const float* y, const float* z, const float* dz, const floa
     set_error("bn_backward: z is NULL; the derivative of activation %d is taken from the forward's output", (int)act);
     return DSPH_E_BADARG;
   }
-  if (workspace_bytes < bn_workspace_bytes(rows, F)) {
-    set_error("bn_backward: workspace of %zu bytes, %zu needed", workspace_bytes, bn_workspace_bytes(rows, F));
-    return DSPH_E_WORKSPACE;
-  }
-  if (reinterpret_cast<uintptr_t>(workspace) & 7) { set_error("bn_backward: workspace is not 8-byte aligned"); return DSPH_E_BADARG; }
+  if (!workspace_ok("bn_backward", workspace, workspace_bytes, bn_workspace_bytes(rows, F), &rc)) return rc;
   const int64_t P = bn_partials(rows, F);
-  const uintptr_t zbits = act != DSPH_ACT_NONE ? reinterpret_cast<uintptr_t>(z) : 0;
-  const int vec = bn_vec(F, reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(dz) | reinterpret_cast<uintptr_t>(dy) | zbits);
+  const int vec = vec_width(F, ptr_bits({y, dz, dy, act != DSPH_ACT_NONE ? z : nullptr}), true);  // (z is read only behind an activation)
   const BnGeo gr = bn_geo(rows, F, vec, P), ge = bn_geo(rows, F, vec, 0);
   double* part = static_cast<double*>(workspace);
   double* sums = part + 2 * P * F;  // s1[F], s2[F]
   const double inv_rows = 1.0 / (double)rows;
   DeviceGuard guard(device);
-  if (!guard.ok) { set_error("bn_backward: cannot select device %d", device); return DSPH_E_BADARG; }
+  if (!select_device("bn_backward", device, guard)) return DSPH_E_BADARG;
   hipStream_t stream = (hipStream_t)hip_stream;
-  switch (vec) {
-    case 4: hipLaunchKernelGGL((bn_bwd_partial_kernel<4>), bn_grid(gr), dim3(BN_THREADS), 0, stream, y, z, dz, mean, rstd, mean_lo, rstd_lo, part, (int)act, gr); break;
-    case 2: hipLaunchKernelGGL((bn_bwd_partial_kernel<2>), bn_grid(gr), dim3(BN_THREADS), 0, stream, y, z, dz, mean, rstd, mean_lo, rstd_lo, part, (int)act, gr); break;
-    default: hipLaunchKernelGGL((bn_bwd_partial_kernel<1>), bn_grid(gr), dim3(BN_THREADS), 0, stream, y, z, dz, mean, rstd, mean_lo, rstd_lo, part, (int)act, gr); break;
-  }
+  DSPH_LAUNCH_BY_VEC(vec, bn_bwd_partial_kernel, bn_grid(gr), dim3(BN_THREADS), stream, y, z, dz, mean, rstd, mean_lo, rstd_lo, part,
+                     (int)act, gr);
   DSPH_HIP(hipGetLastError());
   hipLaunchKernelGGL(bn_bwd_final_kernel, dim3((unsigned)F), dim3(BN_THREADS), 0, stream, (const double*)part, P, F, sums, dgamma, dshift);
   DSPH_HIP(hipGetLastError());
-  switch (vec) {
-    case 4: hipLaunchKernelGGL((bn_bwd_apply_kernel<4>), bn_grid(ge), dim3(BN_THREADS), 0, stream, y, z, dz, mean, rstd, mean_lo, rstd_lo, gamma, (const double*)sums, dy, inv_rows, (int)act, ge); break;
-    case 2: hipLaunchKernelGGL((bn_bwd_apply_kernel<2>), bn_grid(ge), dim3(BN_THREADS), 0, stream, y, z, dz, mean, rstd, mean_lo, rstd_lo, gamma, (const double*)sums, dy, inv_rows, (int)act, ge); break;
-    default: hipLaunchKernelGGL((bn_bwd_apply_kernel<1>), bn_grid(ge), dim3(BN_THREADS), 0, stream, y, z, dz, mean, rstd, mean_lo, rstd_lo, gamma, (const double*)sums, dy, inv_rows, (int)act, ge); break;
-  }
+  DSPH_LAUNCH_BY_VEC(vec, bn_bwd_apply_kernel, bn_grid(ge), dim3(BN_THREADS), stream, y, z, dz, mean, rstd, mean_lo, rstd_lo, gamma,
+                     (const double*)sums, dy, inv_rows, (int)act, ge);
   DSPH_HIP(hipGetLastError());
   return DSPH_OK;
 }

@@ -28,7 +28,7 @@
 // Two launches on the caller's stream; every output element has one writer and a fixed order of summation.
 #include <cmath>
 
-#include "dsphere_common.h"
+#include "dsphere_mapops.h"
 
 namespace dsph {
 
@@ -402,14 +402,33 @@ static int dense_grid(const char* who, int64_t N, int64_t M, int32_t heads, int6
     default: CALL(64); break;       \
   }
 
-int launch_dense_attention_forward(const float* q, const float* k, const float* v, int64_t ld, float* out, float* lse, int64_t N, int64_t M,
-                                   int32_t heads, int32_t depth, hipStream_t stream) {
+// the shape limits of the kernels above, each named in its message
+static int dense_attention_args_ok(const char* who, int64_t ld, int64_t N, int64_t M, int32_t heads, int32_t depth) {
+  if (N < 0) { set_error("%s: negative batch size N = %lld", who, (long long)N); return DSPH_E_BADARG; }
+  if (M < 1) { set_error("%s: M = %lld rows, must be at least 1", who, (long long)M); return DSPH_E_BADARG; }
+  const int rc = attention_shape_ok(who, heads, depth, "");
+  return rc != DSPH_OK ? rc : attention_stride_ok(who, ld, heads, depth);
+}
+
+}  // namespace dsph
+
+extern "C" {
+
+int dsph_dense_attention_forward(const float* q, const float* k, const float* v, int64_t ld, float* out, float* lse, int64_t N, int64_t M,
+                                 int32_t heads, int32_t depth, int device, void* hip_stream) {
+  using namespace dsph;
+  if (!q || !k || !v || !out) { set_error("dense_attention_forward: NULL pointer"); return DSPH_E_BADARG; }
+  int rc = dense_attention_args_ok("dense_attention_forward", ld, N, M, heads, depth);
+  if (rc != DSPH_OK) return rc;
+  if (!aligned16({q, k, v, out})) { set_error("dense_attention_forward: q, k, v and out must be 16-byte aligned"); return DSPH_E_BADARG; }
+  DeviceGuard guard(device);
   if (N <= 0 || M <= 0) return DSPH_OK;
   int64_t nblk;
   unsigned grid;
-  const int rc = dense_grid("dense_attention_forward", N, M, heads, &nblk, &grid);
+  rc = dense_grid("dense_attention_forward", N, M, heads, &nblk, &grid);
   if (rc != DSPH_OK) return rc;
   const float scale = (float)(1.0 / std::sqrt((double)depth));
+  hipStream_t stream = (hipStream_t)hip_stream;
 #define DENSE_FWD(DD) \
   hipLaunchKernelGGL(dense_attention_forward_kernel<DD>, dim3(grid), dim3(256), 0, stream, q, k, v, ld, out, lse, M, (int)heads, nblk, scale)
   DENSE_BY_DEPTH(depth, DENSE_FWD)
@@ -418,15 +437,29 @@ int launch_dense_attention_forward(const float* q, const float* k, const float* 
   return DSPH_OK;
 }
 
-int launch_dense_attention_backward(const float* q, const float* k, const float* v, int64_t ld, const float* out, const float* lse,
-                                    const float* dout, float* delta, float* dq, float* dk, float* dv, int64_t ld_grad, int64_t N,
-                                    int64_t M, int32_t heads, int32_t depth, hipStream_t stream) {
+int dsph_dense_attention_backward(const float* q, const float* k, const float* v, int64_t ld, const float* out, const float* lse,
+                                  const float* dout, float* delta, float* dq, float* dk, float* dv, int64_t ld_grad, int64_t N, int64_t M,
+                                  int32_t heads, int32_t depth, int device, void* hip_stream) {
+  using namespace dsph;
+  if (!q || !k || !v || !out || !lse || !dout || !delta || !dq || !dk || !dv) {
+    set_error("dense_attention_backward: NULL pointer");
+    return DSPH_E_BADARG;
+  }
+  int rc = dense_attention_args_ok("dense_attention_backward", ld, N, M, heads, depth);
+  if (rc == DSPH_OK) rc = dense_attention_args_ok("dense_attention_backward (gradients)", ld_grad, N, M, heads, depth);
+  if (rc != DSPH_OK) return rc;
+  if (!aligned16({q, k, v, out, dout, dq, dk, dv})) {
+    set_error("dense_attention_backward: q, k, v, out, dout, dq, dk and dv must be 16-byte aligned");
+    return DSPH_E_BADARG;
+  }
+  DeviceGuard guard(device);
   if (N <= 0 || M <= 0) return DSPH_OK;
   int64_t nblk;
   unsigned grid;
-  const int rc = dense_grid("dense_attention_backward", N, M, heads, &nblk, &grid);
+  rc = dense_grid("dense_attention_backward", N, M, heads, &nblk, &grid);
   if (rc != DSPH_OK) return rc;
   const float scale = (float)(1.0 / std::sqrt((double)depth));
+  hipStream_t stream = (hipStream_t)hip_stream;
 #define DENSE_BWD(DD)                                                                                                                  \
   hipLaunchKernelGGL(dense_attention_dq_kernel<DD>, dim3(grid), dim3(256), 0, stream, q, k, v, ld, out, lse, dout, delta, dq, ld_grad, M, \
                      (int)heads, nblk, scale);                                                                                         \
@@ -438,4 +471,4 @@ int launch_dense_attention_backward(const float* q, const float* k, const float*
   return DSPH_OK;
 }
 
-}  // namespace dsph
+}  // extern "C"

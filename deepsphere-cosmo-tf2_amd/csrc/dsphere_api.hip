@@ -3,7 +3,6 @@
 #include <stdio.h>
 #include <string.h>
 
-#include <initializer_list>
 #include <new>
 
 #include "dsphere_common.h"
@@ -600,166 +599,12 @@ int dsph_rows_unpack(float* dst, int64_t dst_rows, const int32_t* idx, int64_t n
   return launch_rows_pack(dst, dst_rows, idx, n_idx, const_cast<float*>(buf), N, F, true, (hipStream_t)hip_stream);
 }
 
-static int pool_args_ok(const void* a, const void* b, int64_t N, int64_t rows_out, int32_t F, int32_t group, int32_t type) {
-  if (!a || !b || N < 0 || rows_out < 0 || F <= 0 || group <= 0 || (type != DSPH_POOL_MAX && type != DSPH_POOL_AVG)) {
-    set_error("healpix_pool: bad arguments (NULL pointer, negative size or unknown pooling type %d)", (int)type);
-    return DSPH_E_BADARG;
-  }
-  if (group > (1 << 20)) { set_error("healpix_pool: group %d too large", (int)group); return DSPH_E_UNSUPPORTED; }
-  return DSPH_OK;
-}
-
-int dsph_healpix_pool(const float* x, float* y, int64_t N, int64_t rows_out, int32_t F, int32_t group, int32_t type, int device,
-                      void* hip_stream) {
-  const int rc = pool_args_ok(x, y, N, rows_out, F, group, type);
-  if (rc != DSPH_OK) return rc;
-  DeviceGuard guard(device);
-  return launch_healpix_pool(x, y, N * rows_out, F, group, type == DSPH_POOL_MAX, (hipStream_t)hip_stream);
-}
-
-int dsph_healpix_pool_backward(const float* x, const float* dy, float* dx, int64_t N, int64_t rows_out, int32_t F, int32_t group,
-                               int32_t type, int device, void* hip_stream) {
-  const int rc = pool_args_ok(dy, dx, N, rows_out, F, group, type);
-  if (rc != DSPH_OK) return rc;
-  if (type == DSPH_POOL_MAX && !x) { set_error("healpix_pool_backward: max pooling needs the forward input"); return DSPH_E_BADARG; }
-  DeviceGuard guard(device);
-  return launch_healpix_pool_backward(x, dy, dx, N * rows_out, F, group, type == DSPH_POOL_MAX, (hipStream_t)hip_stream);
-}
-
 int dsph_residual_epilogue(float* y, const float* skip, int64_t n, float alpha, int32_t act, int32_t act_before,
                            int device, void* hip_stream) {
   if (!y || !skip || n < 0) { set_error("residual_epilogue: bad arguments"); return DSPH_E_BADARG; }
   if (act < DSPH_ACT_NONE || act > DSPH_ACT_TANH) { set_error("residual_epilogue: unknown activation %d", act); return DSPH_E_BADARG; }
   DeviceGuard guard(device);
   return launch_residual_epilogue(y, skip, n, alpha, act, act_before != 0, (hipStream_t)hip_stream);
-}
-
-// the shape limits of csrc/nbr_attention.hip, each named in its message
-static int nbr_attention_args_ok(const char* who, int64_t ld, int32_t width, int64_t N, int64_t M, int32_t heads, int32_t depth) {
-  if (N < 0 || M < 0) { set_error("%s: negative size (N %lld, M %lld)", who, (long long)N, (long long)M); return DSPH_E_BADARG; }
-  if (M > 0x7fffffffLL) { set_error("%s: M = %lld exceeds the int32 row indices of the neighbour table", who, (long long)M); return DSPH_E_BADARG; }
-  if (depth != 4 && depth != 8 && depth != 16 && depth != 32 && depth != 64) {
-    set_error("%s: depth %d per head is not one of 4, 8, 16, 32, 64", who, (int)depth);
-    return DSPH_E_BADARG;
-  }
-  if (heads < 1 || (int64_t)heads * depth > 256) {
-    set_error("%s: heads * depth = %d * %d must lie in [depth, 256] (one wave holds a row)", who, (int)heads, (int)depth);
-    return DSPH_E_BADARG;
-  }
-  if (width < 1) { set_error("%s: neighbour table width %d, must be at least 1", who, (int)width); return DSPH_E_BADARG; }
-  if (ld % 4 != 0 || ld < (int64_t)heads * depth) {
-    set_error("%s: row stride %lld must be a multiple of 4 floats and at least heads * depth = %d", who, (long long)ld, (int)(heads * depth));
-    return DSPH_E_BADARG;
-  }
-  return DSPH_OK;
-}
-
-static bool aligned16(std::initializer_list<const void*> ps) {
-  uintptr_t a = 0;
-  for (const void* p : ps) a |= reinterpret_cast<uintptr_t>(p);
-  return (a & 15) == 0;
-}
-
-int dsph_nbr_attention_forward(const float* q, const float* k, const float* v, int64_t ld, float* out, float* lse, const int32_t* nbr,
-                               int32_t width, int64_t N, int64_t M, int32_t heads, int32_t depth, int device, void* hip_stream) {
-  if (!q || !k || !v || !out || !nbr) { set_error("nbr_attention_forward: NULL pointer"); return DSPH_E_BADARG; }
-  const int rc = nbr_attention_args_ok("nbr_attention_forward", ld, width, N, M, heads, depth);
-  if (rc != DSPH_OK) return rc;
-  if (!aligned16({q, k, v, out})) { set_error("nbr_attention_forward: q, k, v and out must be 16-byte aligned"); return DSPH_E_BADARG; }
-  DeviceGuard guard(device);
-  return launch_nbr_attention_forward(q, k, v, ld, out, lse, nbr, width, N, M, heads, depth, (hipStream_t)hip_stream);
-}
-
-int dsph_nbr_attention_backward(const float* q, const float* k, const float* v, int64_t ld, const float* out, const float* lse,
-                                const float* dout, const int32_t* nbr, int32_t width, const int32_t* nbrT, int32_t widthT, float* delta,
-                                float* dq, float* dk, float* dv, int64_t ld_grad, int64_t N, int64_t M, int32_t heads, int32_t depth,
-                                int device, void* hip_stream) {
-  if (!q || !k || !v || !out || !lse || !dout || !nbr || !nbrT || !delta || !dq || !dk || !dv) {
-    set_error("nbr_attention_backward: NULL pointer");
-    return DSPH_E_BADARG;
-  }
-  int rc = nbr_attention_args_ok("nbr_attention_backward", ld, width, N, M, heads, depth);
-  if (rc == DSPH_OK) rc = nbr_attention_args_ok("nbr_attention_backward (gradients, transposed table)", ld_grad, widthT, N, M, heads, depth);
-  if (rc != DSPH_OK) return rc;
-  if (!aligned16({q, k, v, out, dout, dq, dk, dv})) {
-    set_error("nbr_attention_backward: q, k, v, out, dout, dq, dk and dv must be 16-byte aligned");
-    return DSPH_E_BADARG;
-  }
-  DeviceGuard guard(device);
-  return launch_nbr_attention_backward(q, k, v, ld, out, lse, dout, nbr, width, nbrT, widthT, delta, dq, dk, dv, ld_grad, N, M, heads,
-                                       depth, (hipStream_t)hip_stream);
-}
-
-// the shape limits of csrc/dense_attention.hip, each named in its message
-static int dense_attention_args_ok(const char* who, int64_t ld, int64_t N, int64_t M, int32_t heads, int32_t depth) {
-  if (N < 0) { set_error("%s: negative batch size N = %lld", who, (long long)N); return DSPH_E_BADARG; }
-  if (M < 1) { set_error("%s: M = %lld rows, must be at least 1", who, (long long)M); return DSPH_E_BADARG; }
-  if (depth != 4 && depth != 8 && depth != 16 && depth != 32 && depth != 64) {
-    set_error("%s: depth %d per head is not one of 4, 8, 16, 32, 64", who, (int)depth);
-    return DSPH_E_BADARG;
-  }
-  if (heads < 1 || (int64_t)heads * depth > 256) {
-    set_error("%s: heads * depth = %d * %d must lie in [depth, 256]", who, (int)heads, (int)depth);
-    return DSPH_E_BADARG;
-  }
-  if (ld % 4 != 0 || ld < (int64_t)heads * depth) {
-    set_error("%s: row stride %lld must be a multiple of 4 floats and at least heads * depth = %d", who, (long long)ld, (int)(heads * depth));
-    return DSPH_E_BADARG;
-  }
-  return DSPH_OK;
-}
-
-int dsph_dense_attention_forward(const float* q, const float* k, const float* v, int64_t ld, float* out, float* lse, int64_t N, int64_t M,
-                                 int32_t heads, int32_t depth, int device, void* hip_stream) {
-  if (!q || !k || !v || !out) { set_error("dense_attention_forward: NULL pointer"); return DSPH_E_BADARG; }
-  const int rc = dense_attention_args_ok("dense_attention_forward", ld, N, M, heads, depth);
-  if (rc != DSPH_OK) return rc;
-  if (!aligned16({q, k, v, out})) { set_error("dense_attention_forward: q, k, v and out must be 16-byte aligned"); return DSPH_E_BADARG; }
-  DeviceGuard guard(device);
-  return launch_dense_attention_forward(q, k, v, ld, out, lse, N, M, heads, depth, (hipStream_t)hip_stream);
-}
-
-int dsph_dense_attention_backward(const float* q, const float* k, const float* v, int64_t ld, const float* out, const float* lse,
-                                  const float* dout, float* delta, float* dq, float* dk, float* dv, int64_t ld_grad, int64_t N, int64_t M,
-                                  int32_t heads, int32_t depth, int device, void* hip_stream) {
-  if (!q || !k || !v || !out || !lse || !dout || !delta || !dq || !dk || !dv) {
-    set_error("dense_attention_backward: NULL pointer");
-    return DSPH_E_BADARG;
-  }
-  int rc = dense_attention_args_ok("dense_attention_backward", ld, N, M, heads, depth);
-  if (rc == DSPH_OK) rc = dense_attention_args_ok("dense_attention_backward (gradients)", ld_grad, N, M, heads, depth);
-  if (rc != DSPH_OK) return rc;
-  if (!aligned16({q, k, v, out, dout, dq, dk, dv})) {
-    set_error("dense_attention_backward: q, k, v, out, dout, dq, dk and dv must be 16-byte aligned");
-    return DSPH_E_BADARG;
-  }
-  DeviceGuard guard(device);
-  return launch_dense_attention_backward(q, k, v, ld, out, lse, dout, delta, dq, dk, dv, ld_grad, N, M, heads, depth,
-                                         (hipStream_t)hip_stream);
-}
-
-// one smoothing pass (csrc/ell_smooth.hip): every argument is checked here, before any launch
-int dsph_ell_smooth(const int32_t* cols, const float* vals, int64_t M, int32_t W, const float* x, float* y, int64_t N, int32_t C,
-                    const int32_t* reps, int32_t pass, const float* mask, int32_t mask_C, int device, void* hip_stream) {
-  if (!cols || !vals || !x || !y) { set_error("ell_smooth: NULL pointer (cols, vals, x and y are required)"); return DSPH_E_BADARG; }
-  if (N < 0 || M < 0) { set_error("ell_smooth: negative size (N %lld, M %lld)", (long long)N, (long long)M); return DSPH_E_BADARG; }
-  if (M > 0x7fffffffLL) { set_error("ell_smooth: M = %lld exceeds the int32 column indices of the table", (long long)M); return DSPH_E_BADARG; }
-  if (W <= 0) { set_error("ell_smooth: table width W = %d, must be at least 1", (int)W); return DSPH_E_BADARG; }
-  if (C <= 0) { set_error("ell_smooth: C = %d channels, must be at least 1", (int)C); return DSPH_E_BADARG; }
-  if (pass < 0) { set_error("ell_smooth: pass %d is negative", (int)pass); return DSPH_E_BADARG; }
-  if (mask && mask_C != 1 && mask_C != C) {
-    set_error("ell_smooth: mask_C = %d, the mask has 1 or C = %d columns", (int)mask_C, (int)C);
-    return DSPH_E_BADARG;
-  }
-  const double elems = (double)N * (double)M * (double)C;
-  if (elems >= 9.0e18 / 4) { set_error("ell_smooth: N * M * C = %.3g elements do not fit 64-bit byte offsets", elems); return DSPH_E_UNSUPPORTED; }
-  const uintptr_t bytes = (uintptr_t)(N * M * (int64_t)C) * sizeof(float), xa = reinterpret_cast<uintptr_t>(x), ya = reinterpret_cast<uintptr_t>(y);
-  if (xa < ya + bytes && ya < xa + bytes && (bytes > 0 || xa == ya)) {
-    set_error("ell_smooth: x and y overlap; a pass reads neighbours of every row and cannot run in place");
-    return DSPH_E_BADARG;
-  }
-  DeviceGuard guard(device);
-  return launch_ell_smooth(cols, vals, M, W, x, y, N, C, reps, pass, mask, mask_C, (hipStream_t)hip_stream);
 }
 
 }  // extern "C"

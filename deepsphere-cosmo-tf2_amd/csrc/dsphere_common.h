@@ -275,31 +275,6 @@ bool qwgrad_shape_ok(int32_t Fin, int32_t Fout, int32_t K);
 size_t qwgrad_slab_bytes(int num_cu);
 int launch_cheb_qwgrad(const QWgradLaunch& s, hipStream_t stream);
 
-// NEST pooling (healpix_pool.hip)
-int launch_healpix_pool(const float* x, float* y, int64_t rows_out, int32_t F, int32_t group, bool maxp, hipStream_t stream);
-int launch_healpix_pool_backward(const float* x, const float* dy, float* dx, int64_t rows_out, int32_t F, int32_t group, bool maxp,
-                                 hipStream_t stream);
-
-// attention over the neighbour table of the pixel graph (nbr_attention.hip)
-int launch_nbr_attention_forward(const float* q, const float* k, const float* v, int64_t ld, float* out, float* lse, const int32_t* nbr,
-                                 int32_t width, int64_t N, int64_t M, int32_t heads, int32_t depth, hipStream_t stream);
-int launch_nbr_attention_backward(const float* q, const float* k, const float* v, int64_t ld, const float* out, const float* lse,
-                                  const float* dout, const int32_t* nbr, int32_t width, const int32_t* nbrT, int32_t widthT,
-                                  float* delta, float* dq, float* dk, float* dv, int64_t ld_grad, int64_t N, int64_t M, int32_t heads,
-                                  int32_t depth, hipStream_t stream);
-
-// dense attention over all rows of a map, flash style on the fp32 MFMA (dense_attention.hip)
-int launch_dense_attention_forward(const float* q, const float* k, const float* v, int64_t ld, float* out, float* lse, int64_t N, int64_t M,
-                                   int32_t heads, int32_t depth, hipStream_t stream);
-int launch_dense_attention_backward(const float* q, const float* k, const float* v, int64_t ld, const float* out, const float* lse,
-                                    const float* dout, float* delta, float* dq, float* dk, float* dv, int64_t ld_grad, int64_t N,
-                                    int64_t M, int32_t heads, int32_t depth, hipStream_t stream);
-
-// one pass of a wide-row ELL matrix over a map of few channels: Gaussian smoothing (ell_smooth.hip)
-int ell_smooth_group(int32_t W);  // lanes that share one row of a table of width W
-int launch_ell_smooth(const int32_t* cols, const float* vals, int64_t M, int32_t W, const float* x, float* y, int64_t N, int32_t C,
-                      const int32_t* reps, int32_t pass, const float* mask, int32_t mask_C, hipStream_t stream);
-
 // input-side strip kernel (cheb_istrip.hip): layers with at most 16 input channels, one wave per strip
 struct IStripLaunch : LaunchBase {
   unsigned char* wimg;       // workspace: istrip_wimg_bytes() per 32-column block

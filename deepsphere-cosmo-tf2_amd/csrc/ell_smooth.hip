@@ -19,24 +19,11 @@
 //   * rows are dealt to workgroups through xcd_remap: neighbouring NEST rows gather each other's pixels from one XCD's L2.
 // Every pixel and element offset is 64-bit (N M C passes 2^31 at real sizes).  A table entry outside [0, M) counts as an empty
 // slot (weight 0, the row's own pixel is read), so no table can make the kernel read out of bounds.
-#include "dsphere_common.h"
+#include "dsphere_mapops.h"
 
 namespace dsph {
 
 namespace {
-
-__device__ __forceinline__ void ldv(const float* p, float (&r)[1]) { r[0] = *p; }
-__device__ __forceinline__ void ldv(const float* p, float (&r)[2]) {
-  const float2 t = *reinterpret_cast<const float2*>(p);
-  r[0] = t.x; r[1] = t.y;
-}
-__device__ __forceinline__ void ldv(const float* p, float (&r)[4]) {
-  const float4 t = *reinterpret_cast<const float4*>(p);
-  r[0] = t.x; r[1] = t.y; r[2] = t.z; r[3] = t.w;
-}
-__device__ __forceinline__ void stv(float* p, const float (&r)[1]) { *p = r[0]; }
-__device__ __forceinline__ void stv(float* p, const float (&r)[2]) { *reinterpret_cast<float2*>(p) = make_float2(r[0], r[1]); }
-__device__ __forceinline__ void stv(float* p, const float (&r)[4]) { *reinterpret_cast<float4*>(p) = make_float4(r[0], r[1], r[2], r[3]); }
 
 // v + (v of the lane the DPP control names); every lane of the wave is active where this is called
 template <int CTRL>
@@ -139,15 +126,37 @@ __global__ __launch_bounds__(256) void ell_smooth_kernel(const int32_t* __restri
 
 }  // namespace
 
-int ell_smooth_group(int32_t W) { return W <= 128 ? 16 : 64; }
+}  // namespace dsph
 
-int launch_ell_smooth(const int32_t* cols, const float* vals, int64_t M, int32_t W, const float* x, float* y, int64_t N, int32_t C,
-                      const int32_t* reps, int32_t pass, const float* mask, int32_t mask_C, hipStream_t stream) {
+extern "C" {
+
+// one smoothing pass: every argument is checked here, before any launch
+int dsph_ell_smooth(const int32_t* cols, const float* vals, int64_t M, int32_t W, const float* x, float* y, int64_t N, int32_t C,
+                    const int32_t* reps, int32_t pass, const float* mask, int32_t mask_C, int device, void* hip_stream) {
+  using namespace dsph;
+  if (!cols || !vals || !x || !y) { set_error("ell_smooth: NULL pointer (cols, vals, x and y are required)"); return DSPH_E_BADARG; }
+  if (N < 0 || M < 0) { set_error("ell_smooth: negative size (N %lld, M %lld)", (long long)N, (long long)M); return DSPH_E_BADARG; }
+  if (M > 0x7fffffffLL) { set_error("ell_smooth: M = %lld exceeds the int32 column indices of the table", (long long)M); return DSPH_E_BADARG; }
+  if (W <= 0) { set_error("ell_smooth: table width W = %d, must be at least 1", (int)W); return DSPH_E_BADARG; }
+  if (C <= 0) { set_error("ell_smooth: C = %d channels, must be at least 1", (int)C); return DSPH_E_BADARG; }
+  if (pass < 0) { set_error("ell_smooth: pass %d is negative", (int)pass); return DSPH_E_BADARG; }
+  if (mask && mask_C != 1 && mask_C != C) {
+    set_error("ell_smooth: mask_C = %d, the mask has 1 or C = %d columns", (int)mask_C, (int)C);
+    return DSPH_E_BADARG;
+  }
+  const double elems = (double)N * (double)M * (double)C;
+  if (elems >= 9.0e18 / 4) { set_error("ell_smooth: N * M * C = %.3g elements do not fit 64-bit byte offsets", elems); return DSPH_E_UNSUPPORTED; }
+  const size_t bytes = (size_t)(N * M * (int64_t)C) * sizeof(float);
+  if (ranges_overlap(x, bytes, y, bytes)) {  // (maps of no bytes overlap nothing)
+    set_error("ell_smooth: x and y overlap; a pass reads neighbours of every row and cannot run in place");
+    return DSPH_E_BADARG;
+  }
+  DeviceGuard guard(device);
   if (N <= 0 || M <= 0) return DSPH_OK;
-  const int G = ell_smooth_group(W);
+  hipStream_t stream = (hipStream_t)hip_stream;
+  const int G = W <= 128 ? 16 : 64;  // lanes that share one row of a table of width W
   const int E = (W + G - 1) / G < 8 ? (W + G - 1) / G : 8;
-  const uintptr_t al = reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y);
-  const int VEC = (C % 4 == 0 && (al & 15) == 0) ? 4 : (C % 2 == 0 && (al & 7) == 0) ? 2 : 1;
+  const int VEC = vec_width(C, ptr_bits({x, y}), true);
   const int64_t nblk64 = (M + 256 / G - 1) / (256 / G);
   if (nblk64 > 0x7fffffffLL) { set_error("ell_smooth: grid too large (%lld workgroups)", (long long)nblk64); return DSPH_E_UNSUPPORTED; }
   const unsigned nblk = (unsigned)nblk64;
@@ -183,4 +192,4 @@ int launch_ell_smooth(const int32_t* cols, const float* vals, int64_t M, int32_t
   return DSPH_OK;
 }
 
-}  // namespace dsph
+}  // extern "C"

@@ -13,7 +13,7 @@
 // the stand-alone kernels only; the pooled epilogues of dsph_poly_forward_pool reduce behind a ReLU that already floors NaN.
 #include <algorithm>
 
-#include "dsphere_common.h"
+#include "dsphere_mapops.h"
 
 namespace dsph {
 
@@ -78,29 +78,56 @@ __global__ __launch_bounds__(256) void healpix_pool_backward_kernel(const float*
 
 static unsigned pool_grid(int64_t total) { return (unsigned)std::min<int64_t>((total + 255) / 256, 1 << 20); }
 
-int launch_healpix_pool(const float* x, float* y, int64_t rows_out, int32_t F, int32_t group, bool maxp, hipStream_t stream) {
-  if (rows_out <= 0) return DSPH_OK;
-  const bool vec = F % 4 == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0;
-  const unsigned grid = pool_grid(rows_out * (vec ? F / 4 : F));
-  if (vec) {
-    if (maxp) hipLaunchKernelGGL((healpix_pool_kernel<true, 4>), dim3(grid), dim3(256), 0, stream, x, y, rows_out, (int)F, (int)group);
-    else hipLaunchKernelGGL((healpix_pool_kernel<false, 4>), dim3(grid), dim3(256), 0, stream, x, y, rows_out, (int)F, (int)group);
+static int pool_args_ok(const void* a, const void* b, int64_t N, int64_t rows_out, int32_t F, int32_t group, int32_t type) {
+  if (!a || !b || N < 0 || rows_out < 0 || F <= 0 || group <= 0 || (type != DSPH_POOL_MAX && type != DSPH_POOL_AVG)) {
+    set_error("healpix_pool: bad arguments (NULL pointer, negative size or unknown pooling type %d)", (int)type);
+    return DSPH_E_BADARG;
+  }
+  if (group > (1 << 20)) { set_error("healpix_pool: group %d too large", (int)group); return DSPH_E_UNSUPPORTED; }
+  return DSPH_OK;
+}
+
+}  // namespace dsph
+
+extern "C" {
+
+int dsph_healpix_pool(const float* x, float* y, int64_t N, int64_t rows_out, int32_t F, int32_t group, int32_t type, int device,
+                      void* hip_stream) {
+  using namespace dsph;
+  const int rc = pool_args_ok(x, y, N, rows_out, F, group, type);
+  if (rc != DSPH_OK) return rc;
+  DeviceGuard guard(device);
+  const int64_t rows = N * rows_out;
+  if (rows <= 0) return DSPH_OK;
+  const int vec = vec_width(F, ptr_bits({x, y}), false);
+  const unsigned grid = pool_grid(rows * (F / vec));
+  hipStream_t stream = (hipStream_t)hip_stream;
+  if (vec == 4) {
+    if (type == DSPH_POOL_MAX) hipLaunchKernelGGL((healpix_pool_kernel<true, 4>), dim3(grid), dim3(256), 0, stream, x, y, rows, (int)F, (int)group);
+    else hipLaunchKernelGGL((healpix_pool_kernel<false, 4>), dim3(grid), dim3(256), 0, stream, x, y, rows, (int)F, (int)group);
   } else {
-    if (maxp) hipLaunchKernelGGL((healpix_pool_kernel<true, 1>), dim3(grid), dim3(256), 0, stream, x, y, rows_out, (int)F, (int)group);
-    else hipLaunchKernelGGL((healpix_pool_kernel<false, 1>), dim3(grid), dim3(256), 0, stream, x, y, rows_out, (int)F, (int)group);
+    if (type == DSPH_POOL_MAX) hipLaunchKernelGGL((healpix_pool_kernel<true, 1>), dim3(grid), dim3(256), 0, stream, x, y, rows, (int)F, (int)group);
+    else hipLaunchKernelGGL((healpix_pool_kernel<false, 1>), dim3(grid), dim3(256), 0, stream, x, y, rows, (int)F, (int)group);
   }
   DSPH_HIP(hipGetLastError());
   return DSPH_OK;
 }
 
-int launch_healpix_pool_backward(const float* x, const float* dy, float* dx, int64_t rows_out, int32_t F, int32_t group, bool maxp,
-                                 hipStream_t stream) {
-  if (rows_out <= 0) return DSPH_OK;
-  const unsigned grid = pool_grid(rows_out * F);
-  if (maxp) hipLaunchKernelGGL(healpix_pool_backward_kernel<true>, dim3(grid), dim3(256), 0, stream, x, dy, dx, rows_out, (int)F, (int)group);
-  else hipLaunchKernelGGL(healpix_pool_backward_kernel<false>, dim3(grid), dim3(256), 0, stream, x, dy, dx, rows_out, (int)F, (int)group);
+int dsph_healpix_pool_backward(const float* x, const float* dy, float* dx, int64_t N, int64_t rows_out, int32_t F, int32_t group,
+                               int32_t type, int device, void* hip_stream) {
+  using namespace dsph;
+  const int rc = pool_args_ok(dy, dx, N, rows_out, F, group, type);
+  if (rc != DSPH_OK) return rc;
+  if (type == DSPH_POOL_MAX && !x) { set_error("healpix_pool_backward: max pooling needs the forward input"); return DSPH_E_BADARG; }
+  DeviceGuard guard(device);
+  const int64_t rows = N * rows_out;
+  if (rows <= 0) return DSPH_OK;
+  const unsigned grid = pool_grid(rows * F);
+  hipStream_t stream = (hipStream_t)hip_stream;
+  if (type == DSPH_POOL_MAX) hipLaunchKernelGGL(healpix_pool_backward_kernel<true>, dim3(grid), dim3(256), 0, stream, x, dy, dx, rows, (int)F, (int)group);
+  else hipLaunchKernelGGL(healpix_pool_backward_kernel<false>, dim3(grid), dim3(256), 0, stream, x, dy, dx, rows, (int)F, (int)group);
   DSPH_HIP(hipGetLastError());
   return DSPH_OK;
 }
 
-}  // namespace dsph
+}  // extern "C"

@@ -26,7 +26,7 @@
 //     the same input give the same bits.
 //
 // Nothing here allocates, synchronises or reads the host: every launch goes on the caller's stream and is legal under capture.
-#include "dsphere_common.h"
+#include "dsphere_mapops.h"
 
 namespace dsph {
 
@@ -69,18 +69,6 @@ struct LnGeo {
   int32_t rpw, rpb;       // rows per wave (64 / L) and per workgroup step
   double inv_d;
 };
-
-template <int VEC> __device__ __forceinline__ void ldv(const float* p, float (&r)[VEC]);
-template <> __device__ __forceinline__ void ldv<1>(const float* p, float (&r)[1]) { r[0] = *p; }
-template <> __device__ __forceinline__ void ldv<4>(const float* p, float (&r)[4]) {
-  const float4 t = *reinterpret_cast<const float4*>(p);
-  r[0] = t.x; r[1] = t.y; r[2] = t.z; r[3] = t.w;
-}
-template <int VEC> __device__ __forceinline__ void stv(float* p, const float (&r)[VEC]);
-template <> __device__ __forceinline__ void stv<1>(float* p, const float (&r)[1]) { *p = r[0]; }
-template <> __device__ __forceinline__ void stv<4>(float* p, const float (&r)[4]) {
-  *reinterpret_cast<float4*>(p) = make_float4(r[0], r[1], r[2], r[3]);
-}
 
 // sum over the L lanes that share a row; every one of them gets the same bits.  Called by all 64 lanes of the wave.
 __device__ __forceinline__ double row_sum(double v, int L) {
@@ -355,17 +343,10 @@ int ln_npl(const LnGeo& g) {
   return p;
 }
 
-struct Span {
-  uintptr_t lo, hi;
-};
-inline Span span_of(const void* p, int64_t rows, int32_t d) {
-  const uintptr_t lo = reinterpret_cast<uintptr_t>(p);
-  return Span{lo, lo + (uintptr_t)rows * (uintptr_t)d * sizeof(float)};
-}
+// do two maps of the call share a byte (an optional map that is not given shares none)
 inline bool overlap(const void* p, const void* q, int64_t rows, int32_t d) {
-  if (!p || !q) return false;
-  const Span a = span_of(p, rows, d), b = span_of(q, rows, d);
-  return a.lo < b.hi && b.lo < a.hi;
+  const size_t bytes = (size_t)rows * (size_t)d * sizeof(float);
+  return p && q && ranges_overlap(p, bytes, q, bytes);
 }
 
 // rows >= 0 (0: nothing to do), 1 <= d <= 1024
@@ -438,14 +419,12 @@ int dsph_ln_forward(const float* x, const float* res, float* sum, float* z, int6
     return DSPH_E_BADARG;
   }
   if (rows == 0) return DSPH_OK;
-  const uintptr_t bits = reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(z) | reinterpret_cast<uintptr_t>(res) |
-                         reinterpret_cast<uintptr_t>(sum);
-  const int vec = (d % 4 == 0 && (bits & 15) == 0) ? 4 : 1;
+  const int vec = vec_width(d, ptr_bits({x, z, res, sum}), false);
   const LnGeo g = ln_geo(rows, d, vec);
   const int npl = ln_npl(g);
   const dim3 grid((unsigned)ln_fwd_grid(rows, d));
   DeviceGuard guard(device);
-  if (!guard.ok) { set_error("ln_forward: cannot select device %d", device); return DSPH_E_BADARG; }
+  if (!select_device("ln_forward", device, guard)) return DSPH_E_BADARG;
   hipStream_t stream = (hipStream_t)hip_stream;
   LN_DISPATCH(ln_fwd_kernel, vec, npl, grid, stream, x, res, sum, z, gamma, beta, (double)eps, g);
   DSPH_HIP(hipGetLastError());
@@ -467,23 +446,17 @@ int dsph_ln_backward(const float* a, const float* dz, const float* dsum, const f
   const bool want_part = dgamma || dbeta;
   if (want_part && rows > 0) {
     if (!workspace) { set_error("ln_backward: workspace is NULL (dgamma and dbeta are reduced through it)"); return DSPH_E_BADARG; }
-    if (workspace_bytes < ln_workspace_bytes(rows, d)) {
-      set_error("ln_backward: workspace of %zu bytes, %zu needed", workspace_bytes, ln_workspace_bytes(rows, d));
-      return DSPH_E_WORKSPACE;
-    }
-    if (reinterpret_cast<uintptr_t>(workspace) & 7) { set_error("ln_backward: workspace is not 8-byte aligned"); return DSPH_E_BADARG; }
+    if (!workspace_ok("ln_backward", workspace, workspace_bytes, ln_workspace_bytes(rows, d), &rc)) return rc;
   }
   if (rows == 0) return DSPH_OK;
-  const uintptr_t bits = reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(dz) | reinterpret_cast<uintptr_t>(da) |
-                         reinterpret_cast<uintptr_t>(dsum);
-  const int vec = (d % 4 == 0 && (bits & 15) == 0) ? 4 : 1;
+  const int vec = vec_width(d, ptr_bits({a, dz, da, dsum}), false);
   const LnGeo g = ln_geo(rows, d, vec);
   const int npl = ln_npl(g);
   const int64_t P = ln_partials(rows, d);
   const dim3 grid((unsigned)P);
   double* part = static_cast<double*>(workspace);
   DeviceGuard guard(device);
-  if (!guard.ok) { set_error("ln_backward: cannot select device %d", device); return DSPH_E_BADARG; }
+  if (!select_device("ln_backward", device, guard)) return DSPH_E_BADARG;
   hipStream_t stream = (hipStream_t)hip_stream;
   LN_DISPATCH(ln_bwd_kernel, vec, npl, grid, stream, a, dz, dsum, gamma, (double)eps, da, part, want_part ? 1 : 0, g);
   DSPH_HIP(hipGetLastError());

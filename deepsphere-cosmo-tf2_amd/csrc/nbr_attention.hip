@@ -23,7 +23,7 @@
 // Two launches on the caller's stream; every output element has one writer and a fixed order of summation.
 #include <cmath>
 
-#include "dsphere_common.h"
+#include "dsphere_mapops.h"
 
 namespace dsph {
 
@@ -233,12 +233,33 @@ static int nbr_grid(NbrGrid& g, const char* who, int64_t N, int64_t M, int32_t h
     default: CALL(64); break;     \
   }
 
-int launch_nbr_attention_forward(const float* q, const float* k, const float* v, int64_t ld, float* out, float* lse, const int32_t* nbr,
-                                 int32_t width, int64_t N, int64_t M, int32_t heads, int32_t depth, hipStream_t stream) {
+// the shape limits of the kernels above, each named in its message
+static int nbr_attention_args_ok(const char* who, int64_t ld, int32_t width, int64_t N, int64_t M, int32_t heads, int32_t depth) {
+  if (N < 0 || M < 0) { set_error("%s: negative size (N %lld, M %lld)", who, (long long)N, (long long)M); return DSPH_E_BADARG; }
+  if (M > 0x7fffffffLL) { set_error("%s: M = %lld exceeds the int32 row indices of the neighbour table", who, (long long)M); return DSPH_E_BADARG; }
+  const int rc = attention_shape_ok(who, heads, depth, " (one wave holds a row)");
+  if (rc != DSPH_OK) return rc;
+  if (width < 1) { set_error("%s: neighbour table width %d, must be at least 1", who, (int)width); return DSPH_E_BADARG; }
+  return attention_stride_ok(who, ld, heads, depth);
+}
+
+}  // namespace dsph
+
+extern "C" {
+
+int dsph_nbr_attention_forward(const float* q, const float* k, const float* v, int64_t ld, float* out, float* lse, const int32_t* nbr,
+                               int32_t width, int64_t N, int64_t M, int32_t heads, int32_t depth, int device, void* hip_stream) {
+  using namespace dsph;
+  if (!q || !k || !v || !out || !nbr) { set_error("nbr_attention_forward: NULL pointer"); return DSPH_E_BADARG; }
+  int rc = nbr_attention_args_ok("nbr_attention_forward", ld, width, N, M, heads, depth);
+  if (rc != DSPH_OK) return rc;
+  if (!aligned16({q, k, v, out})) { set_error("nbr_attention_forward: q, k, v and out must be 16-byte aligned"); return DSPH_E_BADARG; }
+  DeviceGuard guard(device);
   if (N <= 0 || M <= 0) return DSPH_OK;
   NbrGrid g;
-  const int rc = nbr_grid(g, "nbr_attention_forward", N, M, heads, depth);
+  rc = nbr_grid(g, "nbr_attention_forward", N, M, heads, depth);
   if (rc != DSPH_OK) return rc;
+  hipStream_t stream = (hipStream_t)hip_stream;
 #define NBR_FWD(DD)                                                                                                              \
   hipLaunchKernelGGL(nbr_attention_forward_kernel<DD>, dim3(g.nblk), dim3(256), 0, stream, q, k, v, ld, out, lse, nbr, (int)width, M, \
                      (int)heads, g.lpr, g.rpw, g.groups, g.waves, g.nblk, g.scale)
@@ -248,14 +269,28 @@ int launch_nbr_attention_forward(const float* q, const float* k, const float* v,
   return DSPH_OK;
 }
 
-int launch_nbr_attention_backward(const float* q, const float* k, const float* v, int64_t ld, const float* out, const float* lse,
-                                  const float* dout, const int32_t* nbr, int32_t width, const int32_t* nbrT, int32_t widthT,
-                                  float* delta, float* dq, float* dk, float* dv, int64_t ld_grad, int64_t N, int64_t M, int32_t heads,
-                                  int32_t depth, hipStream_t stream) {
+int dsph_nbr_attention_backward(const float* q, const float* k, const float* v, int64_t ld, const float* out, const float* lse,
+                                const float* dout, const int32_t* nbr, int32_t width, const int32_t* nbrT, int32_t widthT, float* delta,
+                                float* dq, float* dk, float* dv, int64_t ld_grad, int64_t N, int64_t M, int32_t heads, int32_t depth,
+                                int device, void* hip_stream) {
+  using namespace dsph;
+  if (!q || !k || !v || !out || !lse || !dout || !nbr || !nbrT || !delta || !dq || !dk || !dv) {
+    set_error("nbr_attention_backward: NULL pointer");
+    return DSPH_E_BADARG;
+  }
+  int rc = nbr_attention_args_ok("nbr_attention_backward", ld, width, N, M, heads, depth);
+  if (rc == DSPH_OK) rc = nbr_attention_args_ok("nbr_attention_backward (gradients, transposed table)", ld_grad, widthT, N, M, heads, depth);
+  if (rc != DSPH_OK) return rc;
+  if (!aligned16({q, k, v, out, dout, dq, dk, dv})) {
+    set_error("nbr_attention_backward: q, k, v, out, dout, dq, dk and dv must be 16-byte aligned");
+    return DSPH_E_BADARG;
+  }
+  DeviceGuard guard(device);
   if (N <= 0 || M <= 0) return DSPH_OK;
   NbrGrid g;
-  const int rc = nbr_grid(g, "nbr_attention_backward", N, M, heads, depth);
+  rc = nbr_grid(g, "nbr_attention_backward", N, M, heads, depth);
   if (rc != DSPH_OK) return rc;
+  hipStream_t stream = (hipStream_t)hip_stream;
 #define NBR_BWD(DD)                                                                                                                  \
   hipLaunchKernelGGL(nbr_attention_dq_kernel<DD>, dim3(g.nblk), dim3(256), 0, stream, q, k, v, ld, out, lse, dout, nbr, (int)width, delta, \
                      dq, ld_grad, M, (int)heads, g.lpr, g.rpw, g.groups, g.waves, g.nblk, g.scale);                                  \
@@ -267,4 +302,4 @@ int launch_nbr_attention_backward(const float* q, const float* k, const float* v
   return DSPH_OK;
 }
 
-}  // namespace dsph
+}  // extern "C"

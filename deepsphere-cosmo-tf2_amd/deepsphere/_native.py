@@ -317,6 +317,20 @@ def _check_dev(t, plan, name):
         raise ValueError(f"{name} must be a contiguous float32 tensor")
 
 
+def _nbytes(t):
+    return t.numel() * t.element_size()
+
+
+def _ensure_workspace(need, device, workspace, floor=0, same_device=False):
+    """The caller's scratch buffer when it holds ``need`` bytes (``same_device``: and lives on ``device``), else a new one of
+    max(need, floor) bytes: -> (buffer, whether it was replaced)."""
+    import torch
+
+    if workspace is not None and _nbytes(workspace) >= need and (not same_device or workspace.device == device):
+        return workspace, False
+    return torch.empty(max(need, floor), dtype=torch.uint8, device=device), True
+
+
 def cheb_forward(plan, x, w, bias, K, act=ACT_NONE, precision=PREC_FP32, algo=ALGO_AUTO, workspace=None, out=None,
                  basis=BASIS_CHEBYSHEV, part=PART_ALL, keep_weights=False):
     """y = dsph_poly_forward_ex(...) on torch CUDA tensors; x (N, n_cols, Fin), w (Fin*K, Fout).
@@ -339,9 +353,9 @@ def cheb_forward(plan, x, w, bias, K, act=ACT_NONE, precision=PREC_FP32, algo=AL
         if bias.numel() != Fout:
             raise ValueError("bias must have Fout elements")
     need = plan.workspace_bytes(N, Fin, Fout, K, precision, algo)
-    if need > 0 and (workspace is None or workspace.numel() * workspace.element_size() < need):
-        workspace = torch.empty(need, dtype=torch.uint8, device=x.device)
-        keep_weights = False
+    if need > 0:
+        workspace, replaced = _ensure_workspace(need, x.device, workspace)
+        keep_weights = keep_weights and not replaced
     orows = plan.out_rows
     if out is None:
         out = torch.empty((N, orows, Fout), dtype=torch.float32, device=x.device)
@@ -353,7 +367,7 @@ def cheb_forward(plan, x, w, bias, K, act=ACT_NONE, precision=PREC_FP32, algo=AL
         plan.handle, _ptr(x), _ptr(w), _ptr(bias), _ptr(out), int(N), int(Fin), Fout, int(K), int(basis), int(act),
         int(precision), int(algo), int(part), FWD_KEEP_WEIGHTS if (keep_weights and need > 0) else 0,
         _ptr(workspace) if need > 0 else _c_vp(),
-        (workspace.numel() * workspace.element_size()) if need > 0 else 0, _stream_ptr(x.device),
+        _nbytes(workspace) if need > 0 else 0, _stream_ptr(x.device),
     )
     check(rc, "dsph_poly_forward_ex")
     return out, workspace
@@ -375,15 +389,14 @@ def cheb_forward_pool(plan, x, w, bias, K, pool_type=POOL_MAX, act=ACT_NONE, pre
     N, rows, Fin = x.shape
     Fout = int(w.shape[1])
     need = plan.workspace_bytes(N, Fin, Fout, K, precision, ALGO_FUSED)
-    if need > 0 and (workspace is None or workspace.numel() * workspace.element_size() < need):
-        workspace = torch.empty(need, dtype=torch.uint8, device=x.device)
-        keep_weights = False
+    if need > 0:
+        workspace, replaced = _ensure_workspace(need, x.device, workspace)
+        keep_weights = keep_weights and not replaced
     out = torch.empty((N, rows // 4, Fout), dtype=torch.float32, device=x.device)
     rc = lib().dsph_poly_forward_pool(
         plan.handle, _ptr(x), _ptr(w), _ptr(bias), _c_vp(), _ptr(out), int(N), int(Fin), Fout, int(K), int(basis), int(act),
         int(precision), int(pool_type), FWD_KEEP_WEIGHTS if (keep_weights and need > 0) else 0,
-        _ptr(workspace) if need > 0 else _c_vp(), (workspace.numel() * workspace.element_size()) if need > 0 else 0,
-        _stream_ptr(x.device))
+        _ptr(workspace) if need > 0 else _c_vp(), _nbytes(workspace) if need > 0 else 0, _stream_ptr(x.device))
     check(rc, "dsph_poly_forward_pool")
     return out, workspace
 
@@ -454,12 +467,11 @@ def cheb_backward_weights(plan, x, dy, K, basis=BASIS_CHEBYSHEV, algo=ALGO_AUTO,
         raise ValueError(f"x must be (N, {plan.n_cols}, Fin) and dy (N, {plan.out_rows}, Fout)")
     Fout = int(dy.shape[2])
     need = int(lib().dsph_backward_weights_workspace_bytes(plan.handle, int(N), int(Fin), Fout, int(K), int(algo)))
-    if workspace is None or workspace.numel() * workspace.element_size() < need or workspace.device != x.device:
-        workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=x.device)
+    workspace, _ = _ensure_workspace(need, x.device, workspace, floor=16, same_device=True)
     dw = torch.empty((Fin * K, Fout), dtype=torch.float32, device=x.device)
     rc = lib().dsph_cheb_backward_weights(plan.handle, _ptr(x), _ptr(dy), _ptr(dw), int(N), int(Fin), Fout, int(K),
                                           int(basis), int(precision), int(algo), _ptr(workspace),
-                                          workspace.numel() * workspace.element_size(), _stream_ptr(x.device))
+                                          _nbytes(workspace), _stream_ptr(x.device))
     check(rc, "dsph_cheb_backward_weights")
     return dw, workspace
 
@@ -474,12 +486,11 @@ def cheb_wgrad(planes, dy, rows=None, workspace=None):
     rows = int(dy.shape[1]) if rows is None else int(rows)
     Fout = int(dy.shape[2])
     need = int(lib().dsph_wgrad_workspace_bytes(int(N), rows, int(Fin), Fout, K))
-    if workspace is None or workspace.numel() * workspace.element_size() < need:
-        workspace = torch.empty(need, dtype=torch.uint8, device=p0.device)
+    workspace, _ = _ensure_workspace(need, p0.device, workspace)
     dw = torch.empty((Fin * K, Fout), dtype=torch.float32, device=p0.device)
     arr = (_c_vp * K)(*[p.data_ptr() for p in planes])
     rc = lib().dsph_cheb_wgrad(ctypes.cast(arr, _c_vp), int(plane_rows), _ptr(dy), _ptr(dw), int(N), rows, int(Fin),
-                               Fout, K, _ptr(workspace), workspace.numel() * workspace.element_size(),
+                               Fout, K, _ptr(workspace), _nbytes(workspace),
                                p0.device.index, _stream_ptr(p0.device))
     check(rc, "dsph_cheb_wgrad")
     return dw, workspace
@@ -580,22 +591,46 @@ def _check_tables(nbr, M, device, name):
         raise ValueError(f"{name} has {nbr.shape[0]} rows, the maps have {M}")
 
 
-def nbr_attention(q, k, v, nbr, num_heads, need_lse=True):
-    """Attention over the neighbour table ``nbr`` (int32 [M, W], -1 padded) on (N, M, d) maps (``dsph_nbr_attention_forward``):
-    -> (out (N, M, d), lse (N, M, heads) or None).  q, k, v may be channel slices of one wider buffer (``rows_layout``)."""
-    import torch
-
-    require_gpu()
+def _qkv_layout(q, k, v, num_heads):
+    """-> (common row stride, N, M, d) of the three (N, M, d) maps of an attention call."""
     lds = [rows_layout(t) for t in (q, k, v)]
     if None in lds or len(set(lds)) != 1 or not (q.shape == k.shape == v.shape) or not (q.device == k.device == v.device):
         raise ValueError("q, k, v must be float32 HIP tensors of one shape (N, M, d) on one device, rows one common stride apart")
     N, M, d = q.shape
     if num_heads < 1 or d % num_heads != 0:
         raise ValueError(f"d = {d} is not a multiple of num_heads = {num_heads}")
+    return lds[0], N, M, d
+
+
+def _attention_grad_buffers(q, out, lse, dout, grads, num_heads):
+    """What both attention backwards take besides q, k, v: -> (out, lse, dout) contiguous and of the forward's shapes, the three
+    gradient tensors (allocated when ``grads`` is None), their common row stride and the (N, M, heads) scratch ``delta``."""
+    import torch
+
+    N, M, d = q.shape
+    out, dout = out.contiguous(), dout.contiguous()
+    if tuple(out.shape) != (N, M, d) or tuple(dout.shape) != (N, M, d) or tuple(lse.shape) != (N, M, num_heads):
+        raise ValueError("out / dout / lse do not have the forward's shapes")
+    if grads is None:
+        grads = tuple(torch.empty((N, M, d), dtype=torch.float32, device=q.device) for _ in range(3))
+    glds = [rows_layout(t) for t in grads]
+    if None in glds or len(set(glds)) != 1 or any(tuple(g.shape) != (N, M, d) for g in grads):
+        raise ValueError("dq, dk, dv must be float32 HIP tensors (N, M, d), rows one common stride apart")
+    delta = torch.empty((N, M, num_heads), dtype=torch.float32, device=q.device)
+    return out, lse.contiguous(), dout, grads, glds[0], delta
+
+
+def nbr_attention(q, k, v, nbr, num_heads, need_lse=True):
+    """Attention over the neighbour table ``nbr`` (int32 [M, W], -1 padded) on (N, M, d) maps (``dsph_nbr_attention_forward``):
+    -> (out (N, M, d), lse (N, M, heads) or None).  q, k, v may be channel slices of one wider buffer (``rows_layout``)."""
+    import torch
+
+    require_gpu()
+    ld, N, M, d = _qkv_layout(q, k, v, num_heads)
     _check_tables(nbr, M, q.device, "nbr")
     out = torch.empty((N, M, d), dtype=torch.float32, device=q.device)
     lse = torch.empty((N, M, num_heads), dtype=torch.float32, device=q.device) if need_lse else None
-    rc = lib().dsph_nbr_attention_forward(_ptr(q), _ptr(k), _ptr(v), lds[0], _ptr(out), _ptr(lse), _ptr(nbr), int(nbr.shape[1]),
+    rc = lib().dsph_nbr_attention_forward(_ptr(q), _ptr(k), _ptr(v), ld, _ptr(out), _ptr(lse), _ptr(nbr), int(nbr.shape[1]),
                                           int(N), int(M), int(num_heads), int(d // num_heads), q.device.index,
                                           _stream_ptr(q.device))
     check(rc, "dsph_nbr_attention_forward")
@@ -606,27 +641,14 @@ def nbr_attention_backward(q, k, v, out, lse, dout, nbr, nbrT, num_heads, grads=
     """dq, dk, dv of ``nbr_attention`` (``dsph_nbr_attention_backward``; deterministic).  ``nbrT``: the table of the transposed
     graph.  ``grads``: three tensors to write into (channel slices of one buffer: the gradient of a fused q/k/v projection comes
     out as one tensor); allocated when None."""
-    import torch
-
     require_gpu()
-    lds = [rows_layout(t) for t in (q, k, v)]
-    if None in lds or len(set(lds)) != 1:
-        raise ValueError("q, k, v must be float32 HIP tensors (N, M, d), rows one common stride apart")
-    N, M, d = q.shape
+    ld, N, M, d = _qkv_layout(q, k, v, num_heads)
     _check_tables(nbr, M, q.device, "nbr")
     _check_tables(nbrT, M, q.device, "nbrT")
-    out, dout = out.contiguous(), dout.contiguous()
-    if tuple(out.shape) != (N, M, d) or tuple(dout.shape) != (N, M, d) or tuple(lse.shape) != (N, M, num_heads):
-        raise ValueError("out / dout / lse do not have the forward's shapes")
-    if grads is None:
-        grads = tuple(torch.empty((N, M, d), dtype=torch.float32, device=q.device) for _ in range(3))
-    glds = [rows_layout(t) for t in grads]
-    if None in glds or len(set(glds)) != 1 or any(tuple(g.shape) != (N, M, d) for g in grads):
-        raise ValueError("dq, dk, dv must be float32 HIP tensors (N, M, d), rows one common stride apart")
-    delta = torch.empty((N, M, num_heads), dtype=torch.float32, device=q.device)
-    rc = lib().dsph_nbr_attention_backward(_ptr(q), _ptr(k), _ptr(v), lds[0], _ptr(out), _ptr(lse.contiguous()), _ptr(dout), _ptr(nbr),
+    out, lse, dout, grads, gld, delta = _attention_grad_buffers(q, out, lse, dout, grads, num_heads)
+    rc = lib().dsph_nbr_attention_backward(_ptr(q), _ptr(k), _ptr(v), ld, _ptr(out), _ptr(lse), _ptr(dout), _ptr(nbr),
                                            int(nbr.shape[1]), _ptr(nbrT), int(nbrT.shape[1]), _ptr(delta), _ptr(grads[0]),
-                                           _ptr(grads[1]), _ptr(grads[2]), glds[0], int(N), int(M), int(num_heads),
+                                           _ptr(grads[1]), _ptr(grads[2]), gld, int(N), int(M), int(num_heads),
                                            int(d // num_heads), q.device.index, _stream_ptr(q.device))
     check(rc, "dsph_nbr_attention_backward")
     return grads
@@ -639,15 +661,10 @@ def dense_attention(q, k, v, num_heads, need_lse=True):
     import torch
 
     require_gpu()
-    lds = [rows_layout(t) for t in (q, k, v)]
-    if None in lds or len(set(lds)) != 1 or not (q.shape == k.shape == v.shape) or not (q.device == k.device == v.device):
-        raise ValueError("q, k, v must be float32 HIP tensors of one shape (N, M, d) on one device, rows one common stride apart")
-    N, M, d = q.shape
-    if num_heads < 1 or d % num_heads != 0:
-        raise ValueError(f"d = {d} is not a multiple of num_heads = {num_heads}")
+    ld, N, M, d = _qkv_layout(q, k, v, num_heads)
     out = torch.empty((N, M, d), dtype=torch.float32, device=q.device)
     lse = torch.empty((N, M, num_heads), dtype=torch.float32, device=q.device) if need_lse else None
-    rc = lib().dsph_dense_attention_forward(_ptr(q), _ptr(k), _ptr(v), lds[0], _ptr(out), _ptr(lse), int(N), int(M), int(num_heads),
+    rc = lib().dsph_dense_attention_forward(_ptr(q), _ptr(k), _ptr(v), ld, _ptr(out), _ptr(lse), int(N), int(M), int(num_heads),
                                             int(d // num_heads), q.device.index, _stream_ptr(q.device))
     check(rc, "dsph_dense_attention_forward")
     return out, lse
@@ -657,24 +674,11 @@ def dense_attention_backward(q, k, v, out, lse, dout, num_heads, grads=None):
     """dq, dk, dv of ``dense_attention`` (``dsph_dense_attention_backward``; deterministic, nothing of size M^2 is allocated).
     ``grads``: three tensors to write into (channel slices of one buffer: the gradient of a fused q/k/v projection comes out as
     one tensor); allocated when None."""
-    import torch
-
     require_gpu()
-    lds = [rows_layout(t) for t in (q, k, v)]
-    if None in lds or len(set(lds)) != 1 or not (q.shape == k.shape == v.shape):
-        raise ValueError("q, k, v must be float32 HIP tensors of one shape (N, M, d), rows one common stride apart")
-    N, M, d = q.shape
-    out, dout = out.contiguous(), dout.contiguous()
-    if tuple(out.shape) != (N, M, d) or tuple(dout.shape) != (N, M, d) or tuple(lse.shape) != (N, M, num_heads):
-        raise ValueError("out / dout / lse do not have the forward's shapes")
-    if grads is None:
-        grads = tuple(torch.empty((N, M, d), dtype=torch.float32, device=q.device) for _ in range(3))
-    glds = [rows_layout(t) for t in grads]
-    if None in glds or len(set(glds)) != 1 or any(tuple(g.shape) != (N, M, d) for g in grads):
-        raise ValueError("dq, dk, dv must be float32 HIP tensors (N, M, d), rows one common stride apart")
-    delta = torch.empty((N, M, num_heads), dtype=torch.float32, device=q.device)
-    rc = lib().dsph_dense_attention_backward(_ptr(q), _ptr(k), _ptr(v), lds[0], _ptr(out), _ptr(lse.contiguous()), _ptr(dout),
-                                             _ptr(delta), _ptr(grads[0]), _ptr(grads[1]), _ptr(grads[2]), glds[0], int(N), int(M),
+    ld, N, M, d = _qkv_layout(q, k, v, num_heads)
+    out, lse, dout, grads, gld, delta = _attention_grad_buffers(q, out, lse, dout, grads, num_heads)
+    rc = lib().dsph_dense_attention_backward(_ptr(q), _ptr(k), _ptr(v), ld, _ptr(out), _ptr(lse), _ptr(dout),
+                                             _ptr(delta), _ptr(grads[0]), _ptr(grads[1]), _ptr(grads[2]), gld, int(N), int(M),
                                              int(num_heads), int(d // num_heads), q.device.index, _stream_ptr(q.device))
     check(rc, "dsph_dense_attention_backward")
     return grads
@@ -744,31 +748,25 @@ def bn_workspace_bytes(rows, F):
     return int(lib().dsph_bn_workspace_bytes(int(rows), int(F)))
 
 
-def _bn_map(t, name):
+def _map_rows(t, name, like=None, min_dim=2):
+    """-> (rows, channels) of the channels-last map ``t`` (..., C); ``like``: the map whose shape and device it must have."""
     import torch
 
-    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() >= 2 and t.is_contiguous()):
-        raise ValueError(f"{name} must be a contiguous float32 (..., F) HIP tensor")
-    F = int(t.shape[-1])
-    return t.numel() // max(F, 1), F
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() >= min_dim and t.is_contiguous()):
+        raise ValueError(f"{name} must be a contiguous float32 (..., channels) HIP tensor of at least {min_dim} dimensions")
+    if like is not None and (t.shape != like.shape or t.device != like.device):
+        raise ValueError(f"{name} must have x's shape and device")
+    C = int(t.shape[-1])
+    return t.numel() // max(C, 1), C
 
 
-def _bn_vec(t, F, device, name):
+def _channel_vec(t, F, device, name):
     import torch
 
     if t is None:
         return
     if not (isinstance(t, torch.Tensor) and t.device == device and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == F):
         raise ValueError(f"{name} must be a contiguous float32 tensor of F = {F} elements on the map's device")
-
-
-def _bn_workspace(rows, F, device, workspace):
-    import torch
-
-    need = bn_workspace_bytes(rows, F)
-    if workspace is None or workspace.device != device or workspace.numel() * workspace.element_size() < need:
-        workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=device)
-    return workspace
 
 
 def bn_stats(y, eps, running_mean=None, running_var=None, momentum=0.0, workspace=None):
@@ -780,13 +778,13 @@ def bn_stats(y, eps, running_mean=None, running_var=None, momentum=0.0, workspac
     import torch
 
     require_gpu()
-    rows, F = _bn_map(y, "y")
-    _bn_vec(running_mean, F, y.device, "running_mean")
-    _bn_vec(running_var, F, y.device, "running_var")
-    workspace = _bn_workspace(rows, F, y.device, workspace)
+    rows, F = _map_rows(y, "y")
+    _channel_vec(running_mean, F, y.device, "running_mean")
+    _channel_vec(running_var, F, y.device, "running_var")
+    workspace, _ = _ensure_workspace(bn_workspace_bytes(rows, F), y.device, workspace, floor=16, same_device=True)
     stats = torch.empty((5, F), dtype=torch.float32, device=y.device)
     rc = lib().dsph_bn_stats(_ptr(y), rows, F, float(eps), _ptr(stats[0]), _ptr(stats[1]), _ptr(stats[2]), _ptr(stats[3]), _ptr(stats[4]), _ptr(running_mean),
-                             _ptr(running_var), float(momentum), _ptr(workspace), workspace.numel() * workspace.element_size(),
+                             _ptr(running_var), float(momentum), _ptr(workspace), _nbytes(workspace),
                              y.device.index, _stream_ptr(y.device))
     check(rc, "dsph_bn_stats")
     return stats, workspace
@@ -798,14 +796,14 @@ def bn_apply(y, mean, rstd, gamma=None, shift=None, act=ACT_NONE, out=None):
     import torch
 
     require_gpu()
-    rows, F = _bn_map(y, "y")
+    rows, F = _map_rows(y, "y")
     for t, name in ((mean, "mean"), (rstd, "rstd"), (gamma, "gamma"), (shift, "shift")):
-        _bn_vec(t, F, y.device, name)
+        _channel_vec(t, F, y.device, name)
     if mean is None or rstd is None:
         raise ValueError("mean and rstd are required")
     if out is None:
         out = torch.empty_like(y)
-    elif out is not y and (_bn_map(out, "out") != (rows, F) or out.device != y.device):
+    elif out is not y and (_map_rows(out, "out") != (rows, F) or out.device != y.device):
         raise ValueError("out must have y's shape and device")
     rc = lib().dsph_bn_apply(_ptr(y), _ptr(out), rows, F, _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(shift), int(act), y.device.index,
                              _stream_ptr(y.device))
@@ -821,20 +819,20 @@ def bn_backward(y, z, dz, mean, rstd, gamma=None, act=ACT_NONE, want_dgamma=True
     import torch
 
     require_gpu()
-    rows, F = _bn_map(y, "y")
-    if _bn_map(dz, "dz") != (rows, F) or dz.device != y.device:
+    rows, F = _map_rows(y, "y")
+    if _map_rows(dz, "dz") != (rows, F) or dz.device != y.device:
         raise ValueError("dz must have y's shape and device")
-    if act != ACT_NONE and (z is None or _bn_map(z, "z") != (rows, F) or z.device != y.device):
+    if act != ACT_NONE and (z is None or _map_rows(z, "z") != (rows, F) or z.device != y.device):
         raise ValueError("z (the forward's output, y's shape) is needed for the activation's derivative")
     for t, name in ((mean, "mean"), (rstd, "rstd"), (gamma, "gamma"), (mean_lo, "mean_lo"), (rstd_lo, "rstd_lo")):
-        _bn_vec(t, F, y.device, name)
-    workspace = _bn_workspace(rows, F, y.device, workspace)
+        _channel_vec(t, F, y.device, name)
+    workspace, _ = _ensure_workspace(bn_workspace_bytes(rows, F), y.device, workspace, floor=16, same_device=True)
     dy = torch.empty_like(y)
     dgamma = torch.empty(F, dtype=torch.float32, device=y.device) if want_dgamma else None
     dshift = torch.empty(F, dtype=torch.float32, device=y.device) if want_dshift else None
     rc = lib().dsph_bn_backward(_ptr(y), _ptr(z if act != ACT_NONE else None), _ptr(dz), _ptr(mean), _ptr(rstd), _ptr(mean_lo), _ptr(rstd_lo), _ptr(gamma), _ptr(dy),
                                 _ptr(dgamma), _ptr(dshift), rows, F, int(act), _ptr(workspace),
-                                workspace.numel() * workspace.element_size(), y.device.index, _stream_ptr(y.device))
+                                _nbytes(workspace), y.device.index, _stream_ptr(y.device))
     check(rc, "dsph_bn_backward")
     return dy, dgamma, dshift, workspace
 
@@ -848,17 +846,6 @@ def ln_workspace_bytes(rows, d):
     return int(lib().dsph_ln_workspace_bytes(int(rows), int(d)))
 
 
-def _ln_map(t, name, like=None):
-    import torch
-
-    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() >= 1 and t.is_contiguous()):
-        raise ValueError(f"{name} must be a contiguous float32 (..., d) HIP tensor")
-    if like is not None and (t.shape != like.shape or t.device != like.device):
-        raise ValueError(f"{name} must have x's shape and device")
-    d = int(t.shape[-1])
-    return t.numel() // max(d, 1), d
-
-
 def ln_forward(x, gamma, beta, eps, res=None, out=None, sum_out=None):
     """Layer norm over the trailing axis of ``x`` (..., d), the residual add in front fused (``dsph_ln_forward``): without ``res``
     -> z = LN(x) * gamma + beta; with ``res`` (x's shape) -> (z, sum) with sum = x + res and z = LN(sum) * gamma + beta.  ``gamma`` /
@@ -867,21 +854,21 @@ def ln_forward(x, gamma, beta, eps, res=None, out=None, sum_out=None):
     import torch
 
     require_gpu()
-    rows, d = _ln_map(x, "x")
-    _bn_vec(gamma, d, x.device, "gamma")
-    _bn_vec(beta, d, x.device, "beta")
+    rows, d = _map_rows(x, "x", min_dim=1)
+    _channel_vec(gamma, d, x.device, "gamma")
+    _channel_vec(beta, d, x.device, "beta")
     if res is not None:
-        _ln_map(res, "res", x)
+        _map_rows(res, "res", x, min_dim=1)
         if sum_out is None:
             sum_out = torch.empty_like(x)
         else:
-            _ln_map(sum_out, "sum_out", x)
+            _map_rows(sum_out, "sum_out", x, min_dim=1)
     elif sum_out is not None:
         raise ValueError("sum_out without res")
     if out is None:
         out = torch.empty_like(x)
     else:
-        _ln_map(out, "out", x)
+        _map_rows(out, "out", x, min_dim=1)
     if rows:  # (a map without rows has no address to pass)
         rc = lib().dsph_ln_forward(_ptr(x), _ptr(res), _ptr(sum_out), _ptr(out), rows, d, float(eps), _ptr(gamma), _ptr(beta), x.device.index,
                                    _stream_ptr(x.device))
@@ -897,22 +884,20 @@ def ln_backward(a, dz, gamma, eps, dsum=None, want_dgamma=True, want_dbeta=True,
     import torch
 
     require_gpu()
-    rows, d = _ln_map(a, "a")
-    _ln_map(dz, "dz", a)
+    rows, d = _map_rows(a, "a", min_dim=1)
+    _map_rows(dz, "dz", a, min_dim=1)
     if dsum is not None:
-        _ln_map(dsum, "dsum", a)
-    _bn_vec(gamma, d, a.device, "gamma")
+        _map_rows(dsum, "dsum", a, min_dim=1)
+    _channel_vec(gamma, d, a.device, "gamma")
     if want_dgamma or want_dbeta:
-        need = ln_workspace_bytes(rows, d)
-        if workspace is None or workspace.device != a.device or workspace.numel() * workspace.element_size() < need:
-            workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=a.device)
+        workspace, _ = _ensure_workspace(ln_workspace_bytes(rows, d), a.device, workspace, floor=16, same_device=True)
     da = torch.empty_like(a)
     new = torch.zeros if rows == 0 else torch.empty  # (the sums over no rows are zero)
     dgamma = new(d, dtype=torch.float32, device=a.device) if want_dgamma else None
     dbeta = new(d, dtype=torch.float32, device=a.device) if want_dbeta else None
     if rows:  # (a map without rows has no address to pass)
         rc = lib().dsph_ln_backward(_ptr(a), _ptr(dz), _ptr(dsum), _ptr(gamma), float(eps), _ptr(da), _ptr(dgamma), _ptr(dbeta), rows, d,
-                                    _ptr(workspace), 0 if workspace is None else workspace.numel() * workspace.element_size(),
+                                    _ptr(workspace), 0 if workspace is None else _nbytes(workspace),
                                     a.device.index, _stream_ptr(a.device))
         check(rc, "dsph_ln_backward")
     return da, dgamma, dbeta, workspace

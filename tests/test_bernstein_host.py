@@ -1,6 +1,7 @@
 """CPU tests of ``Bernstein`` / ``HealpyBernstein``: the coefficient matrix against the restated op sequence
 (tests/bernstein_ref.py), constructor, lazy build, errors and the model builder.  Nothing is convolved without a GPU."""
 
+import ctypes
 import functools
 from math import comb
 
@@ -11,7 +12,7 @@ import torch
 import bernstein_ref as ref
 from deepsphere import Bernstein as PackageBernstein
 from deepsphere import HealpyBernstein as PackageHealpyBernstein
-from deepsphere import healpix
+from deepsphere import _native, healpix
 from deepsphere.gnn_layers import Bernstein, Chebyshev, GCNN_ResidualLayer, bernstein_to_chebyshev
 from deepsphere.healpy_layers import HealpyBernstein, HealpyChebyshev, HealpyPool
 from deepsphere.healpy_networks import HealpyGCNN
@@ -94,6 +95,27 @@ def test_errors():
         bernstein_to_chebyshev(0)
     with pytest.raises(IOError):
         GCNN_ResidualLayer("BERN", {"L": L, "K": 5})
+    # dsph_basis_change refuses before any device call (made-up addresses 8 TiB apart that nothing dereferences): an output over
+    # an input; and, at 2^40 elements, the grid of a call whose pointers allow 2 floats (8-byte aligned) or 1 float (4-byte
+    # aligned) per access -- 2^31 and 2^32 workgroups, where 4 floats per access are 2^30 and would launch
+    lib = _native.lib()
+    W, C, O = 1 << 44, 1 << 43, 1 << 45
+
+    def change(w=W, c=C, o=O, Fin=4, Fout=8, Kp=3):
+        rc = lib.dsph_basis_change(ctypes.c_void_p(w), ctypes.c_void_p(c), ctypes.c_void_p(o), Fin, Fout, Kp, 0, 0, ctypes.c_void_p())
+        return rc, _native.last_error()
+
+    nbytes = 4 * 3 * 8 * 4
+    for kw, text in [(dict(o=W), "w and w_out overlap"), (dict(o=W + 4), "w and w_out overlap"), (dict(o=W + nbytes - 4), "w and w_out overlap"),
+                     (dict(o=W - nbytes + 4), "w and w_out overlap"), (dict(c=O - 32), "coeff and w_out overlap"),
+                     (dict(c=O + nbytes - 4), "coeff and w_out overlap")]:
+        rc, msg = change(**kw)
+        assert rc == -1 and text in msg, (kw, rc, msg)
+    big = dict(Fin=1 << 24, Fout=1 << 10, Kp=64)
+    for kw, text in [(dict(w=W + 8), "2147483648 workgroups"), (dict(o=O + 8), "2147483648 workgroups"), (dict(w=W + 4), "4294967296 workgroups"),
+                     (dict(w=W + 8, o=O + 4), "4294967296 workgroups")]:
+        rc, msg = change(**kw, **big)
+        assert rc == -3 and text in msg, (kw, rc, msg)
 
 
 def test_exports():

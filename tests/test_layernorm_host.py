@@ -84,8 +84,8 @@ def test_workspace_rule():
 
 
 def test_bad_arguments_are_reported_before_any_device_call():
-    """Every case returns its error code with a message that names the entry point; none touches HIP, so this runs without a GPU
-    (the pointers are made-up addresses nothing dereferences)."""
+    """Every case returns its error code with a message that names the entry point (the overlap cases: and the map that
+    overlaps); none touches HIP, so this runs without a GPU (the pointers are made-up addresses nothing dereferences)."""
     lib = _native.lib()
     base, n = 1 << 40, 1 << 30  # made-up addresses a GiB apart: room for every shape below
 
@@ -110,14 +110,14 @@ def test_bad_arguments_are_reported_before_any_device_call():
         ("ln_forward", lambda: fwd(rows=-1)), ("ln_forward", lambda: fwd(d=0)), ("ln_forward", lambda: fwd(d=-3)),
         ("ln_forward", lambda: fwd(d=1025)), ("ln_forward", lambda: fwd(d=1028)),
         ("ln_forward", lambda: fwd(eps=0.0)), ("ln_forward", lambda: fwd(eps=-1e-3)), ("ln_forward", lambda: fwd(eps=float("nan"))),
-        ("ln_forward", lambda: fwd(z=X)), ("ln_forward", lambda: fwd(z=inside)),
-        ("ln_forward", lambda: fwd(res=R, s=S, z=R)), ("ln_forward", lambda: fwd(res=R, s=S, z=S)),
-        ("ln_forward", lambda: fwd(res=R, s=inside)), ("ln_forward", lambda: fwd(res=R, s=X, z=X)),
+        ("ln_forward: z overlaps", lambda: fwd(z=X)), ("ln_forward: z overlaps", lambda: fwd(z=inside)),
+        ("ln_forward: z overlaps", lambda: fwd(res=R, s=S, z=R)), ("ln_forward: z overlaps", lambda: fwd(res=R, s=S, z=S)),
+        ("ln_forward: sum overlaps", lambda: fwd(res=R, s=inside)), ("ln_forward: z overlaps", lambda: fwd(res=R, s=X, z=X)),
         ("ln_backward", lambda: bwd(a=null)), ("ln_backward", lambda: bwd(dz=null)), ("ln_backward", lambda: bwd(da=null)),
         ("ln_backward", lambda: bwd(rows=-2)), ("ln_backward", lambda: bwd(d=0)), ("ln_backward", lambda: bwd(d=1028)),
         ("ln_backward", lambda: bwd(eps=0.0)),
-        ("ln_backward", lambda: bwd(da=X)), ("ln_backward", lambda: bwd(da=R)), ("ln_backward", lambda: bwd(dsum=Z)),
-        ("ln_backward", lambda: bwd(da=inside)),
+        ("ln_backward: da overlaps", lambda: bwd(da=X)), ("ln_backward: da overlaps", lambda: bwd(da=R)),
+        ("ln_backward: da overlaps", lambda: bwd(dsum=Z)), ("ln_backward: da overlaps", lambda: bwd(da=inside)),
         ("ln_backward", lambda: bwd(w=null)), ("ln_backward", lambda: bwd(w=odd)),
     ]
     for i, (who, call) in enumerate(cases):
