@@ -693,16 +693,20 @@ class Chebyshev(torch.nn.Module):
     def invalidate_weights(self):
         """Forget the packed weight images (and a captured graph): the next forward re-packs.  The layer notices weight updates
         by the version counter of ``self.kernel`` -- optimiser steps, ``copy_``, ``load_state_dict`` all move it -- but an
-        in-place write through ``kernel.data`` does not; call this after one."""
+        in-place write through ``kernel.data`` does not; call this after one.  The fold of the moving statistics into the weights
+        (``_folded_bn``) is keyed on the same counter and is rebuilt too."""
         self._wkey = None
         self._graph = None
+        if getattr(self, "_bn_fold", None) is not None:
+            self._bn_fold["key"] = None
 
     def _graph_forward(self, plan, x, bias, act_code, wkey, kernel):
         """The prepared forward as one HIP-graph launch (``graph=True``).  Captured after an ordinary forward has packed the
         weight images and sized the workspace; the captured call keeps them (DSPH_FWD_KEEP_WEIGHTS), so the graph holds the
         compute kernels only -- and under capture the BFS-tile launch always runs beside the structured ones
-        (csrc/cheb_fused.hip).  Re-captured when the input buffer, the shapes, the weights' version or the epilogue change."""
-        key = (x.data_ptr(), tuple(x.shape), wkey, None if bias is None else bias.data_ptr(), act_code)
+        (csrc/cheb_fused.hip).  Re-captured when the input buffer, the shapes, the weights' version or the epilogue change -- or
+        the power of two of ``precision="f16x3"``: the quad strips take it as kernel arguments, which a capture freezes."""
+        key = (x.data_ptr(), tuple(x.shape), wkey, None if bias is None else bias.data_ptr(), act_code, getattr(self, "_f16_xexp", None))
         g = getattr(self, "_graph", None)
         if g is None or g["key"] != key:
             kw = dict(act=act_code, precision=self._prec_code(), algo=_ALGOS[self.algo], basis=self._basis)
@@ -862,9 +866,8 @@ class Bernstein(Chebyshev):
 
     def invalidate_weights(self):
         super().invalidate_weights()
-        for name in ("_basis_image", "_bn_fold"):  # (both are keyed on the version counter a write through .data does not move)
-            if getattr(self, name, None) is not None:
-                getattr(self, name)["key"] = None
+        if getattr(self, "_basis_image", None) is not None:  # (keyed on the version counter a write through .data does not move)
+            self._basis_image["key"] = None
 
 
 class GCNN_ResidualLayer(torch.nn.Module):

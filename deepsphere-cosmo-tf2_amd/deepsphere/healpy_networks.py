@@ -131,7 +131,10 @@ class HealpyGCNN(torch.nn.Sequential):
                 # a graph convolution followed by HealpyPool(p = 1): one pass where the kernels can (inference, a first layer:
                 # the strip kernel stores the pooled map and the full-resolution output is never written), else the two layers
                 nxt = layers[i + 1] if i + 1 < len(layers) else None
-                if (isinstance(layer, gnn.Chebyshev) and isinstance(nxt, hp_nn.HealpyPool) and nxt.p == 1 and not training
+                # (forward_pool folds the moving statistics: not for a layer that would normalise with the batch's --
+                # training=None follows the layer's own mode, as Chebyshev.forward resolves it)
+                batch_stats = (layer.training and getattr(layer, "use_bn", False)) if training is None else bool(training)
+                if (isinstance(layer, gnn.Chebyshev) and isinstance(nxt, hp_nn.HealpyPool) and nxt.p == 1 and not batch_stats
                         and isinstance(x, torch.Tensor)):
                     y = layer.forward_pool(x, nxt.pool_type)
                     if y is not None:
