@@ -133,6 +133,10 @@ SIGNATURES = {
     "dsph_ln_forward": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i32, ctypes.c_float, _c_vp, _c_vp, ctypes.c_int, _c_vp]),
     "dsph_ln_backward": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, _c_vp, ctypes.c_float, _c_vp, _c_vp, _c_vp, _c_i64, _c_i32, _c_vp, ctypes.c_size_t,
                                          ctypes.c_int, _c_vp]),
+    "dsph_patch_gemm": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i32, _c_i32, _c_i32, _c_i32, _c_i32, ctypes.c_int, _c_vp]),
+    "dsph_patch_backward_workspace_bytes": (ctypes.c_size_t, [_c_i64, _c_i32, _c_i32]),
+    "dsph_patch_epilogue_backward": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i32, _c_i32, _c_i32, _c_vp, ctypes.c_size_t, ctypes.c_int,
+                                                    _c_vp]),
 }
 
 
@@ -901,3 +905,83 @@ def ln_backward(a, dz, gamma, eps, dsum=None, want_dgamma=True, want_dbeta=True,
                                     a.device.index, _stream_ptr(a.device))
         check(rc, "dsph_ln_backward")
     return da, dgamma, dbeta, workspace
+
+
+PATCH_MAX_DIM = 4096  # the longest contraction and the widest output row of the patch GEMM (csrc/patch_gemm.hip)
+
+
+def _patch_map(t, name, like=None):
+    """-> (R, C) of the contiguous float32 (R, C) HIP matrix ``t``; ``like``: the matrix whose shape and device it must have."""
+    import torch
+
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.is_contiguous()):
+        raise ValueError(f"{name} must be a contiguous float32 (rows, columns) HIP tensor")
+    if like is not None and (t.shape != like.shape or t.device != like.device):
+        raise ValueError(f"{name} must have {tuple(like.shape)} elements on {like.device}")
+    return int(t.shape[0]), int(t.shape[1])
+
+
+def _patch_period(C, P):
+    if P < 1 or C % P != 0:
+        raise ValueError(f"the bias period P = {P} must be at least 1 and divide the {C} columns")
+
+
+def patch_gemm(x2d, w, bias, P, act=ACT_NONE, precision=PREC_BF16X6, out=None):
+    """out[r, c] = act(sum_j x2d[r, j] w[j, c] + bias[c mod P]) (``dsph_patch_gemm``): the row GEMM of the pseudo-convolutions, bias
+    and activation in its store.  ``x2d`` (R, Kd), ``w`` (Kd, C), ``bias`` [P] or None, ``out`` (R, C), allocated when None.  Kd and
+    C at most PATCH_MAX_DIM.  One launch on the current stream."""
+    import torch
+
+    require_gpu()
+    R, Kd = _patch_map(x2d, "x2d")
+    Kw, C = _patch_map(w, "w")
+    if w.device != x2d.device or Kw != Kd:
+        raise ValueError(f"w must be a ({Kd}, C) matrix on x2d's device")
+    if R < 1 or not (1 <= Kd <= PATCH_MAX_DIM and 1 <= C <= PATCH_MAX_DIM):
+        raise ValueError(f"R = {R}, Kd = {Kd}, C = {C}: at least one row, Kd and C in [1, {PATCH_MAX_DIM}]")
+    _patch_period(C, int(P))
+    _channel_vec(bias, int(P), x2d.device, "bias")
+    if out is None:
+        out = torch.empty((R, C), dtype=torch.float32, device=x2d.device)
+    elif _patch_map(out, "out") != (R, C) or out.device != x2d.device:
+        raise ValueError(f"out must be a ({R}, {C}) matrix on x2d's device")
+    rc = lib().dsph_patch_gemm(_ptr(x2d), _ptr(w), _ptr(bias), _ptr(out), R, Kd, C, int(P), int(act), int(precision), x2d.device.index,
+                               _stream_ptr(x2d.device))
+    check(rc, "dsph_patch_gemm")
+    return out
+
+
+def patch_backward_workspace_bytes(R, C, P):
+    """Bytes of scratch ``patch_epilogue_backward`` needs for the bias gradient of an (R, C) map with bias period P
+    (``dsph_patch_backward_workspace_bytes``): a function of the shape alone, 8 P max(1, min(2048, ceil(R C / 8192)))."""
+    return int(lib().dsph_patch_backward_workspace_bytes(int(R), int(C), int(P)))
+
+
+def patch_epilogue_backward(y, dy, P, act=ACT_NONE, want_dbias=True, out=None, workspace=None):
+    """dz = dy * act'(y), dbias[o] = sum of dz over the rows and the columns = o mod P (``dsph_patch_epilogue_backward``): ->
+    (dz, dbias or None, workspace).  ``y``: the forward's output (None with ACT_NONE); ``out``: where dz goes -- ``dy`` itself for
+    in place, allocated when None.  Deterministic; two launches (one when no bias gradient is wanted)."""
+    import torch
+
+    require_gpu()
+    R, C = _patch_map(dy, "dy")
+    if R < 1 or not 1 <= C <= PATCH_MAX_DIM:
+        raise ValueError(f"R = {R}, C = {C}: at least one row, C in [1, {PATCH_MAX_DIM}]")
+    _patch_period(C, int(P))
+    if act != ACT_NONE:
+        if y is None:
+            raise ValueError("y (the forward's output) is needed for the activation's derivative")
+        _patch_map(y, "y", dy)
+    if out is None:
+        out = torch.empty_like(dy)
+    elif out is not dy:
+        _patch_map(out, "out", dy)
+    dbias = None
+    if want_dbias:
+        workspace, _ = _ensure_workspace(patch_backward_workspace_bytes(R, C, P), dy.device, workspace, floor=16, same_device=True)
+        dbias = torch.empty(int(P), dtype=torch.float32, device=dy.device)
+    rc = lib().dsph_patch_epilogue_backward(_ptr(y if act != ACT_NONE else None), _ptr(dy), _ptr(out), _ptr(dbias), R, C, int(P), int(act),
+                                            _ptr(workspace if want_dbias else None), _nbytes(workspace) if want_dbias else 0,
+                                            dy.device.index, _stream_ptr(dy.device))
+    check(rc, "dsph_patch_epilogue_backward")
+    return out, dbias, workspace

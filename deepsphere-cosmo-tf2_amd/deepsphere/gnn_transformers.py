@@ -391,7 +391,7 @@ class Graph_ViT(torch.nn.Module):
     least 1") and its docstring; p = 1 is a valid patch of four pixels.
 
     Parameter names follow the reference's attributes: ``embed.weight`` (d, Fin, 4^p) and ``embed.bias`` -- a lazily built
-    ``torch.nn.Conv1d``, Glorot-uniform / zero like Keras, evaluated as the single ``addmm`` that ``HealpyPseudoConv`` uses --
+    ``torch.nn.Conv1d``, Glorot-uniform / zero like Keras, evaluated as a single ``addmm`` on the free reshape ``HealpyPseudoConv`` makes --
     ``pos_encoder.pos_embedding`` (1, M / 4^p, d) and ``mha_layers.{i}.wqkv / dense / layer_norm1 / layer_norm2`` as in
     ``Graph_Transformer``.  Runs on a HIP device only."""
 

@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import _native, healpix
-from .gnn_layers import Bernstein, Chebyshev, GCNN_ResidualLayer, Monomial
+from .gnn_layers import Bernstein, Chebyshev, GCNN_ResidualLayer, Monomial, _resolve_activation
 from .gnn_transformers import Graph_Transformer, Graph_ViT
 
 
@@ -77,9 +77,136 @@ class HealpyPool(torch.nn.Module):
     call = forward
 
 
-class HealpyPseudoConv(torch.nn.Module):
+# arithmetic of the pseudo-convolutions' GEMM by name.  "auto" is the fp32-equivalent six-term split wherever the kernel runs: their
+# contractions are short (4^p * Fin down to Fin = 1), where the three-term split measured 1e-5 (gnn_layers.DEFAULT_PRECISION)
+_PATCH_PRECISIONS = {"auto": _native.PREC_BF16X6, "fp32": _native.PREC_FP32, "bf16x6": _native.PREC_BF16X6,
+                     "bf16x3": _native.PREC_BF16X3}
+_PATCH_KWARGS = ("activation", "use_bias", "bias_initializer", "trainable", "name", "precision")
+# THE SHAPE RULE of precision="auto": the kernel runs where the contraction is at most 64 long and the output row at most 256
+# wide; longer contractions and wider rows keep the library GEMM composition (torch.addmm / @ + bias + activation).  Measured on an
+# MI355X against that composition (tools/bench_pseudoconv.py; forward, forward + backward):
+#   Kd 4, C 16: 1.38, 1.10    Kd 1, C 64: 1.15, 1.46    Kd 64, C 32: 1.20, 1.64    Kd 16, C 128: 1.64, 1.52    Kd 64, C 256: 1.29, 1.06
+#   Kd 256, C 64: 0.80, 0.88  Kd 512, C 32: 0.69, 0.78  Kd 32, C 512: 0.94, 0.93   -- the three that lose, and that the rule excludes
+# (at Kd >= 256 the kernel is bound by its split and matrix work, not by the stream).  A precision asked for by name ("fp32",
+# "bf16x6", "bf16x3") names the kernel's arithmetic and runs the kernel at every shape in its range.
+_PATCH_AUTO_MAX_KD, _PATCH_AUTO_MAX_C = 64, 256
+
+
+class _PatchGemmFunction(torch.autograd.Function):
+    """y = act(x2d @ w2 + bias[c mod P]) on ``dsph_patch_gemm``; the backward is the epilogue's gradient
+    (``dsph_patch_epilogue_backward``: dz and dbias), the same GEMM on the transposed weight image for dx and
+    ``dsph_cheb_wgrad`` on the one plane x2d for the weight image's gradient.  ``w2`` is the (Kd, C) image of ``filter.weight``; the
+    permute that made it carries its gradient back to the parameter's layout."""
+
+    @staticmethod
+    def forward(ctx, x2d, w2, bias, P, act, precision, scratch):
+        y = _native.patch_gemm(x2d, w2, bias, P, act=act, precision=precision)
+        ctx.P, ctx.act, ctx.precision, ctx.has_bias, ctx.scratch = P, act, precision, bias is not None, scratch
+        ctx.save_for_backward(x2d, w2, y if act != _native.ACT_NONE else y.new_empty(0))
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x2d, w2, y = ctx.saved_tensors
+        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        need_b = ctx.has_bias and ctx.needs_input_grad[2]
+        dz, db = dy.contiguous(), None
+        linear = ctx.act == _native.ACT_NONE
+        if not linear or need_b:  # (a linear layer without a bias gradient: dz is dy, no launch; with one: dz is dy, a pure reduction)
+            dz, db, _ = _native.patch_epilogue_backward(None if linear else y, dz, ctx.P, act=ctx.act, want_dbias=need_b,
+                                                        out=dz if linear else None)
+        dx = dw = None
+        if need_x:
+            dx = _native.patch_gemm(dz, w2.t().contiguous(), None, 1, act=_native.ACT_NONE, precision=ctx.precision)
+        if need_w:
+            R, Kd = x2d.shape
+            ws = ctx.scratch.get("wgrad")  # the slabs of dsph_cheb_wgrad, kept on the layer between steps
+            dw, ctx.scratch["wgrad"] = _native.cheb_wgrad([x2d.view(1, R, Kd)], dz.view(1, R, dz.shape[1]),
+                                                          workspace=ws if ws is not None and ws.device == x2d.device else None)
+        return dx, dw, db, None, None, None, None
+
+
+class _PseudoConvBase(torch.nn.Module):
+    """What the two pseudo-convolutions share: the Keras arguments the reference hands to its Conv1D / Conv2DTranspose
+    (``activation``, ``use_bias``, ``bias_initializer``, ``trainable``, ``name``), the arithmetic (``precision``: "auto" | "fp32" |
+    "bf16x6" | "bf16x3") and the forward: a float32 tensor on a HIP device runs ``dsph_patch_gemm`` with bias and activation in its
+    store -- under "auto" (the fp32-equivalent "bf16x6") where the contraction is at most 64 long and the output row at most 256
+    wide, the shapes at which it was measured ahead of the library GEMM (``_PATCH_AUTO_MAX_KD``, ``_PATCH_AUTO_MAX_C`` and the
+    figures beside them); under a precision asked for by name at every shape the kernel takes.  Anything else (a CPU tensor,
+    another dtype, "auto" beyond that rule, a contraction or an output row beyond the kernel's 4096) is the same GEMM as a
+    composition of the host framework's operators, bias and activation applied."""
+
+    def _read_kwargs(self, kwargs):
+        for key in kwargs:
+            if key not in _PATCH_KWARGS:
+                raise NotImplementedError(f"{type(self).__name__}: the keyword argument <{key}> is not supported "
+                                          f"(supported: {', '.join(_PATCH_KWARGS)})")
+        self.activation, self._act_code = _resolve_activation(kwargs.get("activation", None))
+        self.use_bias = bool(kwargs.get("use_bias", True))
+        self.bias_initializer = kwargs.get("bias_initializer", None)
+        self.trainable = bool(kwargs.get("trainable", True))
+        self.name = kwargs.get("name", None)
+        self.precision = kwargs.get("precision", "auto")
+        if self.precision not in _PATCH_PRECISIONS:
+            raise ValueError(f"precision must be one of {sorted(_PATCH_PRECISIONS)}")
+        self._image = None  # inference: (key, the (Kd, C) weight image)
+        self._scratch = {}  # training: workspaces kept between steps
+
+    def _init_filter(self):
+        torch.nn.init.xavier_uniform_(self.filter.weight)  # Keras default glorot_uniform, zero bias
+        if self.filter.bias is not None:
+            torch.nn.init.zeros_(self.filter.bias)
+        if self.kernel_initializer is not None:
+            self.kernel_initializer(self.filter.weight)
+        if self.bias_initializer is not None and self.filter.bias is not None:
+            self.bias_initializer(self.filter.bias)
+        for prm in self.filter.parameters():
+            prm.requires_grad_(self.trainable)
+
+    def _weight_image(self, weight):
+        raise NotImplementedError
+
+    def _cached_image(self):
+        """Inference: the contiguous (Kd, C) image of ``filter.weight``, rebuilt when the parameter was replaced or written in place
+        (keyed on ``data_ptr`` and ``_version``, as ``Chebyshev._kernel_image``: a write through ``weight.data``, which bumps no
+        version, is not seen -- update the parameter itself under ``torch.no_grad()``)."""
+        w = self.filter.weight
+        key = (w.data_ptr(), w._version, w.device, w.dtype)
+        if self._image is None or self._image[0] != key:
+            self._image = (key, self._weight_image(w.detach()).contiguous())
+        return self._image[1]
+
+    def _gemm(self, x2d, P):
+        """act(x2d @ image + bias by column mod P) for the (R, Kd) view ``x2d`` of the map."""
+        weight, bias = self.filter.weight, self.filter.bias
+        Kd = int(x2d.shape[1])
+        C = weight.numel() // Kd
+        native = (x2d.is_cuda and x2d.dtype == torch.float32 and weight.dtype == torch.float32 and weight.device == x2d.device
+                  and x2d.shape[0] >= 1 and Kd <= _native.PATCH_MAX_DIM and C <= _native.PATCH_MAX_DIM)
+        if native and self.precision == "auto":  # the shape rule (see _PATCH_AUTO_MAX_KD)
+            native = Kd <= _PATCH_AUTO_MAX_KD and C <= _PATCH_AUTO_MAX_C
+        if not native:
+            w2 = self._weight_image(weight).to(x2d.dtype)
+            if bias is None:
+                y = x2d @ w2
+            elif P == C:
+                y = torch.addmm(bias.to(x2d.dtype), x2d, w2)
+            else:
+                y = ((x2d @ w2).reshape(-1, P) + bias.to(x2d.dtype)).reshape(-1, C)
+            return y if self.activation is None else self.activation(y)
+        act = self._act_code if self._act_code is not None else _native.ACT_NONE
+        prec = _PATCH_PRECISIONS[self.precision]
+        if torch.is_grad_enabled() and (x2d.requires_grad or weight.requires_grad or (bias is not None and bias.requires_grad)):
+            y = _PatchGemmFunction.apply(x2d, self._weight_image(weight).contiguous(), bias, P, act, prec, self._scratch)
+        else:
+            y = _native.patch_gemm(x2d, self._cached_image(), None if bias is None else bias.detach(), P, act=act, precision=prec)
+        return y if self._act_code is not None or self.activation is None else self.activation(y)
+
+
+class HealpyPseudoConv(_PseudoConvBase):
     """Learnable 4^p -> 1 reduction of NEST children (reference ``healpy_layers.py:81-146``: Conv1D with
-    kernel = stride = 4^p, channels last).  Weights: ``filter.weight`` (Fout, Fin, 4^p), ``filter.bias``."""
+    kernel = stride = 4^p, channels last).  Weights: ``filter.weight`` (Fout, Fin, 4^p), ``filter.bias`` (none with
+    ``use_bias=False``).  Keyword arguments: see ``_PseudoConvBase``; any other raises ``NotImplementedError``."""
 
     def __init__(self, p, Fout, kernel_initializer=None, **kwargs):
         super().__init__()
@@ -90,16 +217,17 @@ class HealpyPseudoConv(torch.nn.Module):
         self.Fout = Fout
         self.kernel_initializer = kernel_initializer
         self.kwargs = kwargs
+        self._read_kwargs(kwargs)
         self.filter = None
 
     def build(self, input_shape):
         if int(input_shape[1]) % self.filter_size != 0:
             raise IOError(f"Input shape {tuple(input_shape)} not compatible with the filter size {self.filter_size}")
-        self.filter = torch.nn.Conv1d(int(input_shape[-1]), self.Fout, self.filter_size, stride=self.filter_size)
-        torch.nn.init.xavier_uniform_(self.filter.weight)  # Keras default glorot_uniform, zero bias
-        torch.nn.init.zeros_(self.filter.bias)
-        if self.kernel_initializer is not None:
-            self.kernel_initializer(self.filter.weight)
+        self.filter = torch.nn.Conv1d(int(input_shape[-1]), self.Fout, self.filter_size, stride=self.filter_size, bias=self.use_bias)
+        self._init_filter()
+
+    def _weight_image(self, weight):
+        return weight.permute(2, 1, 0).reshape(-1, self.Fout)  # row (i, f) <- weight[o, f, i]
 
     def forward(self, input_tensor):
         x = _as_tensor(input_tensor)
@@ -107,20 +235,20 @@ class HealpyPseudoConv(torch.nn.Module):
             self.build(x.shape)
             self.filter.to(x.device)
         # kernel = stride = 4^p on NEST-ordered rows: the 4^p children of an output pixel are consecutive rows, so the input
-        # is, without any copy, a (N * M / 4^p) x (4^p * Fin) matrix and the layer one plain library GEMM against the
-        # [4^p * Fin, Fout] view of the Conv1D weights (no transposes of the map, which Conv1d on channels-last data needs)
+        # is, without any copy, a (N * M / 4^p) x (4^p * Fin) matrix and the layer one row GEMM against the
+        # [4^p * Fin, Fout] image of the Conv1D weights (no transposes of the map, which Conv1d on channels-last data needs)
         N, M, Fin = x.shape
         g = self.filter_size
-        w2 = self.filter.weight.permute(2, 1, 0).reshape(g * Fin, self.Fout)  # row (i, f) <- weight[o, f, i]
-        y = torch.addmm(self.filter.bias, x.reshape(N * (M // g), g * Fin), w2.to(x.dtype))
+        y = self._gemm(x.contiguous().reshape(N * (M // g), g * Fin), self.Fout)
         return y.reshape(N, M // g, self.Fout)
 
     call = forward
 
 
-class HealpyPseudoConv_Transpose(torch.nn.Module):
+class HealpyPseudoConv_Transpose(_PseudoConvBase):
     """Learnable 1 -> 4^p expansion into NEST children (reference ``healpy_layers.py:149-216``: a
-    Conv2DTranspose with kernel = stride = (1, 4^p))."""
+    Conv2DTranspose with kernel = stride = (1, 4^p)).  Weights: ``filter.weight`` (Fin, Fout, 4^p), ``filter.bias`` (none with
+    ``use_bias=False``).  Keyword arguments: see ``_PseudoConvBase``; any other raises ``NotImplementedError``."""
 
     def __init__(self, p, Fout, kernel_initializer=None, **kwargs):
         super().__init__()
@@ -131,30 +259,30 @@ class HealpyPseudoConv_Transpose(torch.nn.Module):
         self.Fout = Fout
         self.kernel_initializer = kernel_initializer
         self.kwargs = kwargs
+        self._read_kwargs(kwargs)
         self.filter = None
 
     def build(self, input_shape):
         if int(input_shape[1]) % self.filter_size != 0:  # the reference checks the same thing (:203-204)
             raise IOError(f"Input shape {tuple(input_shape)} not compatible with the filter size {self.filter_size}")
         self.filter = torch.nn.ConvTranspose1d(int(input_shape[-1]), self.Fout, self.filter_size,
-                                               stride=self.filter_size)
-        torch.nn.init.xavier_uniform_(self.filter.weight)
-        torch.nn.init.zeros_(self.filter.bias)
-        if self.kernel_initializer is not None:
-            self.kernel_initializer(self.filter.weight)
+                                               stride=self.filter_size, bias=self.use_bias)
+        self._init_filter()
+
+    def _weight_image(self, weight):
+        return weight.permute(0, 2, 1).reshape(weight.shape[0], -1)  # column (i, o) <- weight[f, o, i]
 
     def forward(self, input_tensor):
         x = _as_tensor(input_tensor)
         if self.filter is None:
             self.build(x.shape)
             self.filter.to(x.device)
-        # the mirror image: every input pixel writes its 4^p NEST children, consecutive rows of the output -- one GEMM of the
-        # (N * M) x Fin map against the [Fin, 4^p * Fout] view of the transposed-convolution weights, reshaped for free
+        # the mirror image: every input pixel writes its 4^p NEST children, consecutive rows of the output -- one row GEMM of the
+        # (N * M) x Fin map against the [Fin, 4^p * Fout] image of the transposed-convolution weights, the bias periodic in Fout,
+        # reshaped for free
         N, M, Fin = x.shape
-        g = self.filter_size
-        w2 = self.filter.weight.permute(0, 2, 1).reshape(Fin, g * self.Fout)  # column (i, o) <- weight[f, o, i]
-        y = x.reshape(N * M, Fin) @ w2.to(x.dtype)
-        return y.reshape(N, M * g, self.Fout) + self.filter.bias
+        y = self._gemm(x.contiguous().reshape(N * M, Fin), self.Fout)
+        return y.reshape(N, M * self.filter_size, self.Fout)
 
     call = forward
 

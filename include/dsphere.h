@@ -576,6 +576,35 @@ size_t dsph_ln_workspace_bytes(int64_t rows, int32_t d);
 int dsph_ln_backward(const float* a, const float* dz, const float* dsum, const float* gamma, float eps, float* da, float* dgamma,
                      float* dbeta, int64_t rows, int32_t d, void* workspace, size_t workspace_bytes, int device, void* hip_stream);
 
+/* The pseudo-convolutions as one row GEMM with the bias and the activation in its store (plan-free; csrc/patch_gemm.hip):
+ *     Y[r, c] = act( sum_j X[r, j] * W[j, c] + bias[c mod P] )
+ * x device (R, Kd) fp32, rows contiguous; w device (Kd, C); y device (R, C); bias device [P] or NULL (none); act a DSPH_ACT_* code.
+ * HealpyPseudoConv (reference healpy_layers.py:81-146, Conv1D with kernel = stride = g = 4^p on a NEST map (N, M, Fin)):
+ *     R = N M / g, Kd = g Fin, C = P = Fout, W[i Fin + f, o] = weight[o, f, i];
+ * HealpyPseudoConv_Transpose (:149-216): R = N M, Kd = Fin, C = g Fout, P = Fout, W[f, i Fout + o] = weight[f, o, i].
+ * Both x views are free reshapes of the map.  ONE launch: every row of x is read once per group of up to 128 output columns,
+ * y is written once.  precision: DSPH_PREC_FP32 (v_mfma_f32_32x32x2_f32), DSPH_PREC_BF16X6 or DSPH_PREC_BF16X3, fp32
+ * accumulation in all three; DSPH_PREC_F16X3 has no scale rule here and runs DSPH_PREC_BF16X6.
+ * Any R in [1, 2^40], Kd and C in [1, 4096] (DSPH_E_UNSUPPORTED beyond); Kd or C not a multiple of four, or x / y off 16-byte
+ * alignment: scalar accesses of the same elements.  Bad arguments (x, w or y NULL; R, Kd, C or P < 1; C % P != 0; an unknown act
+ * or precision; y overlapping x or w): DSPH_E_BADARG with the entry point named in the message, before any HIP call.  The call
+ * only enqueues on `hip_stream`: no allocation, no synchronisation, no copy -- legal under stream capture. */
+int dsph_patch_gemm(const float* x, const float* w, const float* bias, float* y, int64_t R, int32_t Kd, int32_t C, int32_t P, int32_t act,
+                    int32_t precision, int device, void* hip_stream);
+/* The gradient of that epilogue, from the stored output y and the upstream gradient dy (both device (R, C)):
+ *     dZ = dY * act'(Y)   (relu y > 0, elu y > 0 ? 1 : y + 1, sigmoid y (1 - y), tanh 1 - y^2; DSPH_ACT_NONE: dZ = dY, y may be NULL)
+ *     dbias[o] = sum_r sum_{c = o mod P} dZ[r, c]            (device [P], or NULL: not wanted)
+ * dz may be dy itself (in place) and overlaps nothing else.  The P' = max(1, min(2048, ceil(R C / 8192))) workgroups of the
+ * map pass each leave one float64 partial per bias element in the workspace and a second launch merges them in a fixed order: no
+ * atomics, the same call twice gives the same bits.  Workspace: caller-owned, 8-byte aligned,
+ * dsph_patch_backward_workspace_bytes(R, C, P) = 8 P P' bytes, a function of the shape alone (0 for a shape the entry point does
+ * not take); not needed (may be NULL) when dbias is NULL.  Errors as dsph_patch_gemm; a workspace that is too small:
+ * DSPH_E_WORKSPACE.  The rest of the layer's backward reuses what exists: dX = dZ W^T is dsph_patch_gemm on the transposed weight
+ * image without bias and activation, dW = X^T dZ is dsph_cheb_wgrad on the one plane X viewed as (1, R, Kd). */
+size_t dsph_patch_backward_workspace_bytes(int64_t R, int32_t C, int32_t P);
+int dsph_patch_epilogue_backward(const float* y, const float* dy, float* dz, float* dbias, int64_t R, int32_t C, int32_t P, int32_t act,
+                                 void* workspace, size_t workspace_bytes, int device, void* hip_stream);
+
 const char* dsph_last_error(void);
 int dsph_abi_version(void);
 
