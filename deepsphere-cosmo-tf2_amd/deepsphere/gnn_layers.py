@@ -170,15 +170,31 @@ class _ChebConvFunction(torch.autograd.Function):
             kernel_t = kernel.detach().reshape(Fin, K, Fout).permute(2, 1, 0).reshape(Fout * K, Fin).contiguous()
             dx, layer._workspace_t = _native.cheb_forward(
                 plan_t, dy, kernel_t, None, K, act=_native.ACT_NONE,
-                precision=_PRECISIONS[resolve_dx_precision(layer.precision, Fout, K, plan_t.uses_chain(Fout, Fin, K) if K > 9 else None)],
+                precision=_PRECISIONS[resolve_dx_precision(layer.precision, Fout, K, layer._chained(transposed=True))],
                 algo=_ALGOS[layer.algo], workspace=layer._workspace_t, basis=layer._basis)
         if ctx.needs_input_grad[1]:
             plan = layer._get_plan()
             dk, layer._workspace_w = _native.cheb_backward_weights(
-                plan, x, dy, K, basis=layer._basis, algo=_ALGOS[layer.algo], workspace=getattr(layer, "_workspace_w", None),
+                plan, x, dy, K, basis=layer._basis, algo=_ALGOS[layer.algo], workspace=layer._workspace_w,
                 precision=_PRECISIONS[resolve_wgrad_precision(layer.precision, N * M)])
             dk = layer._wgrad_out(dk)
         return dx, dk, None
+
+
+def _batch_stats(module, training):
+    """The one mode rule: does a call with this ``training`` argument normalise with (and update from) the batch's statistics?
+    ``None`` follows ``module.training`` (torch style); anything else is the caller's word, whatever the module's mode."""
+    return module.training if training is None else bool(training)
+
+
+def _torch_batch_norm(bn, y, training):
+    """The host framework's batch norm ``bn`` on a channels-last map (N, M, F), through the two transposes, in the mode
+    ``training``; the module's own mode is restored."""
+    was_training = bn.training
+    bn.train(training)
+    y = bn(y.transpose(1, 2)).transpose(1, 2)
+    bn.train(was_training)
+    return y
 
 
 def _bn_native_ok(bn, y):
@@ -377,11 +393,21 @@ class Chebyshev(torch.nn.Module):
             returned tensor is then the SAME buffer on every call (copy it if it must outlive the next forward).
         """
         super().__init__()
+        # Rescaled Laplacian (host, float64 -> float32), then padded ELL for the kernels.
+        Lt, lmax = utils.prepare_L(L, scale=self._scale)
+        self._setup(L, lmax, *utils.csr_to_ell(Lt), K, Fout=Fout, initializer=initializer, activation=activation, use_bias=use_bias,
+                    use_bn=use_bn, n_matmul_splits=n_matmul_splits, **kwargs)
+
+    def _setup(self, L, lmax, ell_cols, ell_vals, K, /, Fout=None, initializer=None, activation=None, use_bias=False, use_bn=False,
+               n_matmul_splits=1, **kwargs):
+        """The one construction path behind ``__init__`` and ``from_prepared_ell``: every attribute a layer ever holds is
+        assigned here -- what it is built from, then what it remembers between calls."""
         self.L = L
+        self.lmax = lmax
         self.K = int(K)
         if self.K < 1:
             raise ValueError("K must be at least 1")
-        self.Fout = Fout
+        self.Fout = Fout  # as the caller gave it; build() resolves None to Fin in self._Fout
         self.use_bias = use_bias
         self.use_bn = use_bn
         self.bn = None  # created in build() once Fout is known
@@ -389,32 +415,32 @@ class Chebyshev(torch.nn.Module):
         self.activation, self._act_code = _resolve_activation(activation)
         self.n_matmul_splits = n_matmul_splits
         device = kwargs.pop("device", None)
-        precision = kwargs.pop("precision", DEFAULT_PRECISION)
-        algo = kwargs.pop("algo", "auto")
+        self.precision = kwargs.pop("precision", DEFAULT_PRECISION)
+        self.algo = kwargs.pop("algo", "auto")
         self._plan_options = dict(kwargs.pop("plan_options", None) or {})
         self._use_graph = bool(kwargs.pop("graph", False))
         self.x_absmax = kwargs.pop("x_absmax", None)
-        if precision not in _PRECISIONS:
+        if self.precision not in _PRECISIONS:
             raise ValueError(f"precision must be one of {sorted(_PRECISIONS)}")
-        if algo not in _ALGOS:
+        if self.algo not in _ALGOS:
             raise ValueError(f"algo must be one of {sorted(_ALGOS)}")
-        self.precision = precision
-        self.algo = algo
         self.kwargs = kwargs
         self._device = torch.device(device) if device is not None else None
-
-        # Rescaled Laplacian (host, float64 -> float32), then padded ELL for the kernels.
-        Lt, self.lmax = utils.prepare_L(L, scale=self._scale)
-        self._M = Lt.shape[0]
-        self._ell_cols, self._ell_vals = utils.csr_to_ell(Lt)
-        self._nnz = int(Lt.nnz)
-        self._plan = None
-        self._plan_t = None
-        self._workspace = None
-        self._workspace_t = None
+        self._M = ell_cols.shape[0]
+        self._ell_cols, self._ell_vals = ell_cols, ell_vals
+        self._nnz = int(np.count_nonzero(ell_vals))
         self.kernel = None
         self.bias = None
         self._built = False
+        self._Fin = self._Fout = None  # the widths build() resolved
+        # what the layer keeps between calls, and what makes each stale:
+        self._plan = self._plan_t = None  # LaplacianPlan of L~ and of its transpose: for good
+        self._workspace = self._workspace_t = self._workspace_w = None  # of forward, input gradient, weight gradient: grow only
+        self._prepared = None  # (terms, Fin, with backward) the plan's tables were last built for
+        self._wkey = None  # _weights_key() + the workspace pointer of the call that left its weight images in the workspace
+        self._graph = None  # graph=True: {"key", "graph", "out", "hold"} of the captured forward
+        self._bn_fold = {"key": None, "count": 0}  # _folded_bn's image (+ "kernel", "bias"); key None = stale, count = its version
+        self._f16_xexp = None  # the power of two last handed to DSPH_OPT_F16_XEXP
 
     # -- Keras-style lazy build ---------------------------------------------------------------
     def build(self, input_shape):
@@ -439,7 +465,7 @@ class Chebyshev(torch.nn.Module):
         if self.use_bn:
             # Keras momentum 0.9 == torch momentum 0.1; center=False, scale=False
             self.bn = torch.nn.BatchNorm1d(Fout, eps=1e-5, momentum=0.1, affine=False).to(dev)
-        self._Fin = Fin
+        self._Fin, self._Fout = Fin, Fout
         self._built = True
 
     def _resolve_device(self, x):
@@ -460,11 +486,10 @@ class Chebyshev(torch.nn.Module):
                 raise RuntimeError("the Chebyshev forward needs a HIP device; there is no CPU fallback")
             index = dev.index if dev.index is not None else torch.cuda.current_device()
             self._device = torch.device("cuda", index)
-            self._plan = _native.LaplacianPlan(self._ell_cols, self._ell_vals, device=index,
-                                               options=getattr(self, "_plan_options", None))
+            self._plan = _native.LaplacianPlan(self._ell_cols, self._ell_vals, device=index, options=self._plan_options)
         if not transposed:
             return self._plan
-        if getattr(self, "_plan_t", None) is None:
+        if self._plan_t is None:
             # the backward applies T_k(L~)^T; a symmetric L~ (every graph Laplacian) reuses the plan
             M, W = self._ell_cols.shape
             rows = np.repeat(np.arange(M, dtype=np.int64), W)
@@ -477,8 +502,7 @@ class Chebyshev(torch.nn.Module):
                 At = A.T.tocsr()
                 At.sort_indices()
                 tc, tv = utils.csr_to_ell(At)
-                self._plan_t = _native.LaplacianPlan(tc, tv, device=self._device.index,
-                                                     options=getattr(self, "_plan_options", None))
+                self._plan_t = _native.LaplacianPlan(tc, tv, device=self._device.index, options=self._plan_options)
         return self._plan_t
 
     def _prec_code(self):
@@ -488,11 +512,11 @@ class Chebyshev(torch.nn.Module):
     def _chained(self, transposed=False):
         """Does the plan run this layer's forward (``transposed``: its input gradient, Fout -> Fin on the transposed plan) as the
         chain of <= 5-term passes?  None below K = 10 (no plan is asked: resolve_precision's rule needs nothing there)."""
-        if self._n_terms <= 9 or getattr(self, "_plan", None) is None:
+        if self._n_terms <= 9 or self._plan is None:
             return None
         if transposed:
-            return self._get_plan(transposed=True).uses_chain(self.Fout, self._Fin, self._n_terms)
-        return self._plan.uses_chain(self._Fin, self.Fout, self._n_terms)
+            return self._get_plan(transposed=True).uses_chain(self._Fout, self._Fin, self._n_terms)
+        return self._plan.uses_chain(self._Fin, self._Fout, self._n_terms)
 
     # -- forward --------------------------------------------------------------------------------
     def forward(self, input_tensor, training=False):
@@ -519,86 +543,81 @@ class Chebyshev(torch.nn.Module):
         plan = self._get_plan()
         wants_grad = torch.is_grad_enabled() and (
             self.kernel.requires_grad or input_tensor.requires_grad or (self.use_bias and self.bias.requires_grad))
-        prepared = getattr(self, "_prepared", None)
+        prepared = self._prepared
         if prepared is None or prepared[:2] != (self._n_terms, Fin) or (wants_grad and not prepared[2]):
             # tile tables now, not inside the first kernel launch (allocation + synchronisation: dsph_plan_prepare_layer); with
             # autograd on also what the backward needs (DSPH_PREPARE_BACKWARD: the weight-gradient tables and the one-second host
             # pass that decides whether L~ is symmetric) -- otherwise the first training step would stall inside
             # dsph_cheb_backward_weights, mid-capture under a HIP graph
-            plan.prepare(self._n_terms, Fin, Fout=self.Fout, backward=wants_grad)
+            plan.prepare(self._n_terms, Fin, Fout=self._Fout, backward=wants_grad)
             self._prepared = (self._n_terms, Fin, bool(wants_grad) or bool(prepared and prepared[:2] == (self._n_terms, Fin) and prepared[2]))
-        if wants_grad:
-            # differentiable path: the linear part through the autograd function above, the epilogue
-            # (BN -> bias -> activation, gnn_layers.py:152-159) through _BatchNormActFunction when it normalises with batch
-            # statistics on the GPU, as ordinary torch ops otherwise
+        bn_training = self.use_bn and _batch_stats(self, training)
+        if wants_grad:  # the linear part through the autograd function above, the whole epilogue after it
             x = input_tensor.to(device=self._device, dtype=torch.float32).contiguous()
             y = _ChebConvFunction.apply(x, self.kernel, self)
-            if self.use_bn and (self.training if training is None else bool(training)) and _bn_native_ok(self.bn, y):
-                # batch statistics, the bias and the activation in the batch-norm kernels (csrc/batch_norm.hip)
-                return self._bn_act(y, self.bias if self.use_bias else None, inplace=False)
-            if self.use_bn:
-                was_training = self.bn.training
-                self.bn.train(self.training if training is None else bool(training))
-                y = self.bn(y.transpose(1, 2)).transpose(1, 2)
-                self.bn.train(was_training)
-            if self.use_bias:
-                y = y + self.bias
-            if self.activation is not None:
-                y = self.activation(y)
-            return y
-        x = input_tensor.detach().to(device=self._device, dtype=torch.float32).contiguous()
-        bias = self.bias.detach().reshape(-1).contiguous() if self.use_bias else None
-        kernel, kver = self._kernel_image()
-
+            return self._finish(y, bn_training, self.bias if self.use_bias else None, autograd=True)
         # Batch norm with the moving statistics (the reference's default call, training=False) is a per-channel scale and
         # shift between the contraction and the bias (gnn_layers.py:152-159: BN -> bias -> activation; center=False,
         # scale=False): folded into the weights and the bias, the whole epilogue runs inside the kernel -- no transposed
         # copies, no elementwise pass.  With batch statistics (training=True) the batch-norm kernels follow the convolution
         # (csrc/batch_norm.hip: statistics, then normalisation + bias + activation in one pass, in place).
-        bn_training = self.use_bn and (self.training if training is None else bool(training))
-        if self.use_bn and not bn_training:
-            kernel, bias, kver = self._folded_bn()
-        fuse_epilogue = not bn_training
-        act_code = self._act_code if (fuse_epilogue and self._act_code is not None) else _native.ACT_NONE
+        x = input_tensor.detach().to(device=self._device, dtype=torch.float32).contiguous()
+        kernel, bias, version = self._inference_weights(bn_training)
+        fused_bias = None if bn_training else bias
+        act_code = self._act_code if (not bn_training and self._act_code is not None) else _native.ACT_NONE
         self._set_f16_scale(plan, x)
-        # Inference steady state: the packed weight images of the previous forward are still in the workspace -- same kernel
-        # tensor at the same version (torch bumps it on every in-place write: optimiser step, copy_, load_state_dict), same
-        # arithmetic, same workspace -- so the call launches no weight-preparation kernel (DSPH_FWD_KEEP_WEIGHTS).
-        # (and same batch class: the tile kernels pack four maps of a narrow layer into one item when there is more than one map)
-        wkey = (kernel.data_ptr(), kver, self._prec_code(), (self.algo, N > 1),
-                None if self._workspace is None else self._workspace.data_ptr())
-        if getattr(self, "_use_graph", False):
-            y = self._graph_forward(plan, x, bias if fuse_epilogue else None, act_code, wkey[:4], kernel)
+        key = self._weights_key(kernel, version, N)
+        if self._use_graph:
+            y = self._graph_forward(plan, x, fused_bias, act_code, key, kernel)
         else:
             y, self._workspace = _native.cheb_forward(
-                plan, x, kernel, bias if fuse_epilogue else None, self._n_terms, act=act_code,
-                precision=self._prec_code(), algo=_ALGOS[self.algo], workspace=self._workspace,
-                basis=self._basis, keep_weights=getattr(self, "_wkey", None) == wkey,
-            )
-            self._wkey = wkey[:4] + (self._workspace.data_ptr() if self._workspace is not None else None,)
-        if bn_training and _bn_native_ok(self.bn, y):  # the same three in one pass over the fresh y, in place
-            y = self._bn_act(y, bias, inplace=True)
-        elif bn_training:  # BN -> bias -> activation, the reference's order (gnn_layers.py:152-159)
-            was_training = self.bn.training
-            self.bn.train(True)
-            y = self.bn(y.transpose(1, 2)).transpose(1, 2).contiguous()
-            self.bn.train(was_training)
-            if bias is not None:
-                y = y + self.bias.detach()
-            if self.activation is not None:
-                y = self.activation(y)
-        elif self.activation is not None and self._act_code is None:
-            y = self.activation(y)
-        return y
+                plan, x, kernel, fused_bias, self._n_terms, act=act_code, precision=key[2], algo=_ALGOS[self.algo],
+                workspace=self._workspace, basis=self._basis, keep_weights=self._weights_kept(key))
+            self._record_weights(key)
+        return self._finish(y, bn_training, bias, autograd=False)
 
-    def _bn_act(self, y, shift, inplace):
-        """Training batch norm -> bias -> activation (gnn_layers.py:152-159) on the convolution's output through
-        ``_BatchNormActFunction``: the activation inside the kernel when it has a code, after it in the host framework otherwise."""
-        act = self._act_code if (self.activation is not None and self._act_code is not None) else _native.ACT_NONE
-        y = _BatchNormActFunction.apply(y, None, shift, self.bn, act, inplace)
-        if self.activation is not None and self._act_code is None:
-            y = self.activation(y)
-        return y
+    def _finish(self, y, bn_training, shift, autograd):
+        """BN -> bias -> activation (gnn_layers.py:152-159) on the convolution's output, the one place for the three situations:
+        autograd on (``shift``: ``self.bias`` or None; nothing in place); autograd off with batch statistics (``shift``: the
+        detached flat bias; the batch-norm kernels write over y, the convolution's fresh output); autograd off otherwise -- the
+        kernel has run the epilogue, moving statistics folded in, and only an activation without a code is left."""
+        host_act = self.activation is not None and self._act_code is None
+        if autograd or bn_training:
+            if bn_training and _bn_native_ok(self.bn, y):
+                # batch statistics, the bias and the activation in the batch-norm kernels (csrc/batch_norm.hip)
+                y = _BatchNormActFunction.apply(y, None, shift, self.bn, _native.ACT_NONE if host_act else self._act_code, not autograd)
+            else:  # as ordinary torch ops
+                if self.use_bn:
+                    y = _torch_batch_norm(self.bn, y, bn_training)
+                    y = y if autograd else y.contiguous()
+                if shift is not None:
+                    y = y + shift
+                host_act = self.activation is not None
+        return self.activation(y) if host_act else y
+
+    def _inference_weights(self, bn_training):
+        """``(kernel, bias, version)`` as the kernels of a call without autograd see them: ``_kernel_image()`` and the detached
+        flat bias, or -- batch norm on its moving statistics -- the fold of those into both.  ``version`` keys the kept weight images."""
+        if self.use_bn and not bn_training:
+            return self._folded_bn()
+        kernel, version = self._kernel_image()
+        return kernel, self.bias.detach().reshape(-1).contiguous() if self.use_bias else None, version
+
+    # Inference steady state: the packed weight images of the previous forward are still in the workspace -- same kernel tensor at
+    # the same version (torch bumps it on every in-place write: optimiser step, copy_, load_state_dict), same arithmetic, same
+    # batch class (the tile kernels pack four maps of a narrow layer into one item when there is more than one map), same
+    # workspace -- so the call launches no weight-preparation kernel (DSPH_FWD_KEEP_WEIGHTS).  The key is built, asked and
+    # recorded here and nowhere else; self._wkey = None forgets.
+    def _weights_key(self, kernel, version, N):
+        return (kernel.data_ptr(), version, self._prec_code(), (self.algo, N > 1))
+
+    def _weights_kept(self, key):
+        """Before the call: does the workspace hold the images of ``key``?"""
+        return self._wkey == key + (None if self._workspace is None else self._workspace.data_ptr(),)
+
+    def _record_weights(self, key):
+        """After the call: it does, in the workspace the call returned."""
+        self._wkey = key + (None if self._workspace is None else self._workspace.data_ptr(),)
 
     def _folded_bn(self):
         """Inference batch norm folded into the layer's parameters: ``(kernel * s, bias - mean * s, version)`` with
@@ -609,26 +628,27 @@ class Chebyshev(torch.nn.Module):
         kept weight images of the steady state are keyed on a stable pointer and a fold counter."""
         bn = self.bn
         # (a training-mode call updates the moving statistics inside the framework's native batch norm WITHOUT moving their
-        # version counters; it does bump num_batches_tracked, in Python)
-        key = (self.kernel.data_ptr(), self.kernel._version, bn.running_mean._version, bn.running_var._version,
+        # version counters; it does bump num_batches_tracked, in Python.  eps and the buffers' pointers: a module whose eps was
+        # changed, or whose buffers were rebound to other tensors at the same version, is not the module that was folded)
+        key = (self.kernel.data_ptr(), self.kernel._version, bn.eps, bn.running_mean.data_ptr(), bn.running_mean._version,
+               bn.running_var.data_ptr(), bn.running_var._version,
                bn.num_batches_tracked._version if bn.num_batches_tracked is not None else None,
                None if not self.use_bias else (self.bias.data_ptr(), self.bias._version))
-        fold = getattr(self, "_bn_fold", None)
-        if fold is None or fold["key"] != key:
+        fold = self._bn_fold
+        if fold["key"] != key:
             with torch.no_grad():
                 s = torch.rsqrt(bn.running_var.to(torch.float32) + bn.eps)
                 kf = self._kernel_image()[0] * s
                 bf = -bn.running_mean.to(torch.float32) * s
                 if self.use_bias:
                     bf = bf + self.bias.detach().reshape(-1)
-                if fold is None:
-                    fold = {"kernel": kf.contiguous(), "bias": bf.contiguous(), "count": 0}
-                else:
+                if "kernel" in fold:
                     fold["kernel"].copy_(kf)
                     fold["bias"].copy_(bf)
-                fold["key"] = key
-                fold["count"] += 1
-            self._bn_fold = fold
+                else:
+                    fold["kernel"], fold["bias"] = kf.contiguous(), bf.contiguous()
+            fold["key"] = key
+            fold["count"] += 1
         return fold["kernel"], fold["bias"], ("bn-fold", fold["count"])
 
     def _set_f16_scale(self, plan, x):
@@ -637,13 +657,13 @@ class Chebyshev(torch.nn.Module):
         named none, from a reduction over x on the device and ONE host synchronisation per forward."""
         if self.precision != "f16x3":
             return
-        amax = getattr(self, "x_absmax", None)
+        amax = self.x_absmax
         if amax is None:
             amax = float(x.abs().amax())
         e = 0
         if np.isfinite(amax) and amax > 0.0:
             e = int(np.clip(14 - np.frexp(amax)[1], -100, 100))
-        if getattr(self, "_f16_xexp", None) != e:
+        if self._f16_xexp != e:
             plan.set_option(_native.OPT_F16_XEXP, e)
             self._f16_xexp = e
 
@@ -657,7 +677,7 @@ class Chebyshev(torch.nn.Module):
         (``HealpyGCNN.forward`` does).  Same values as the two layers (bit for bit for "MAX")."""
         if pool_type not in ("MAX", "AVG") or not isinstance(input_tensor, torch.Tensor) or input_tensor.dim() != 3:
             return None
-        if self._act_code not in (_native.ACT_NONE, _native.ACT_RELU) or getattr(self, "_use_graph", False):
+        if self._act_code not in (_native.ACT_NONE, _native.ACT_RELU) or self._use_graph:
             return None
         if torch.is_grad_enabled() and (input_tensor.requires_grad or (self._built and (self.kernel.requires_grad or (
                 self.use_bias and self.bias.requires_grad)))):
@@ -673,21 +693,15 @@ class Chebyshev(torch.nn.Module):
         if Fin != self._Fin:
             return None
         plan = self._get_plan()
-        Fout = int(self.kernel.shape[1])
-        if not _native.pool_fusable(plan, N, Fin, Fout, self._n_terms, self._act_code):
+        if not _native.pool_fusable(plan, N, Fin, self._Fout, self._n_terms, self._act_code):
             return None
         x = input_tensor.detach().to(device=self._device, dtype=torch.float32).contiguous()
-        bias = self.bias.detach().reshape(-1).contiguous() if self.use_bias else None
-        kernel, kver = self._kernel_image()
-        if self.use_bn:  # (inference: the moving statistics folded into weights and bias, as in forward)
-            kernel, bias, kver = self._folded_bn()
-        wkey = (kernel.data_ptr(), kver, self._prec_code(), (self.algo, N > 1),
-                None if self._workspace is None else self._workspace.data_ptr())
+        kernel, bias, version = self._inference_weights(False)  # (the moving statistics folded in, as in forward)
+        key = self._weights_key(kernel, version, N)
         y, self._workspace = _native.cheb_forward_pool(
             plan, x, kernel, bias, self._n_terms, pool_type=_native.POOL_MAX if pool_type == "MAX" else _native.POOL_AVG,
-            act=self._act_code, precision=self._prec_code(), workspace=self._workspace,
-            basis=self._basis, keep_weights=getattr(self, "_wkey", None) == wkey)
-        self._wkey = wkey[:4] + (self._workspace.data_ptr() if self._workspace is not None else None,)
+            act=self._act_code, precision=key[2], workspace=self._workspace, basis=self._basis, keep_weights=self._weights_kept(key))
+        self._record_weights(key)
         return y
 
     def invalidate_weights(self):
@@ -697,8 +711,7 @@ class Chebyshev(torch.nn.Module):
         (``_folded_bn``) is keyed on the same counter and is rebuilt too."""
         self._wkey = None
         self._graph = None
-        if getattr(self, "_bn_fold", None) is not None:
-            self._bn_fold["key"] = None
+        self._bn_fold["key"] = None
 
     def _graph_forward(self, plan, x, bias, act_code, wkey, kernel):
         """The prepared forward as one HIP-graph launch (``graph=True``).  Captured after an ordinary forward has packed the
@@ -706,10 +719,10 @@ class Chebyshev(torch.nn.Module):
         compute kernels only -- and under capture the BFS-tile launch always runs beside the structured ones
         (csrc/cheb_fused.hip).  Re-captured when the input buffer, the shapes, the weights' version or the epilogue change -- or
         the power of two of ``precision="f16x3"``: the quad strips take it as kernel arguments, which a capture freezes."""
-        key = (x.data_ptr(), tuple(x.shape), wkey, None if bias is None else bias.data_ptr(), act_code, getattr(self, "_f16_xexp", None))
-        g = getattr(self, "_graph", None)
+        key = (x.data_ptr(), tuple(x.shape), wkey, None if bias is None else bias.data_ptr(), act_code, self._f16_xexp)
+        g = self._graph
         if g is None or g["key"] != key:
-            kw = dict(act=act_code, precision=self._prec_code(), algo=_ALGOS[self.algo], basis=self._basis)
+            kw = dict(act=act_code, precision=wkey[2], algo=_ALGOS[self.algo], basis=self._basis)
             y, self._workspace = _native.cheb_forward(plan, x, kernel, bias, self._n_terms, workspace=self._workspace, **kw)
             self._wkey = None
             graph = torch.cuda.CUDAGraph()
@@ -733,42 +746,11 @@ class Chebyshev(torch.nn.Module):
         the oracle and the kernels.  Not part of the reference API."""
         self = cls.__new__(cls)
         torch.nn.Module.__init__(self)
-        self.L = None
-        self.K = int(K)
-        if self.K < 1:
-            raise ValueError("K must be at least 1")
-        self.Fout = kwargs.pop("Fout", None)
-        self.use_bias = kwargs.pop("use_bias", False)
-        self.use_bn = kwargs.pop("use_bn", False)
-        self.bn = None
-        self.initializer = kwargs.pop("initializer", None)
-        self.activation, self._act_code = _resolve_activation(kwargs.pop("activation", None))
-        self.n_matmul_splits = kwargs.pop("n_matmul_splits", 1)
-        device = kwargs.pop("device", None)
-        self.precision = kwargs.pop("precision", DEFAULT_PRECISION)
-        self.algo = kwargs.pop("algo", "auto")
-        self._plan_options = dict(kwargs.pop("plan_options", None) or {})
-        self._use_graph = bool(kwargs.pop("graph", False))
-        self.x_absmax = kwargs.pop("x_absmax", None)
-        if self.precision not in _PRECISIONS or self.algo not in _ALGOS:
-            raise ValueError("unknown precision or algo")
-        self.kwargs = kwargs
-        self._device = torch.device(device) if device is not None else None
-        self.lmax = lmax
         cols = np.ascontiguousarray(ell_cols, dtype=np.int32)
         vals = np.ascontiguousarray(ell_vals, dtype=np.float32)
         if cols.ndim != 2 or cols.shape != vals.shape:
             raise ValueError("ELL arrays must have shape [M, W]")
-        self._M = cols.shape[0]
-        self._ell_cols, self._ell_vals = cols, vals
-        self._nnz = int(np.count_nonzero(vals))
-        self._plan = None
-        self._plan_t = None
-        self._workspace = None
-        self._workspace_t = None
-        self.kernel = None
-        self.bias = None
-        self._built = False
+        self._setup(None, lmax, cols, vals, K, **kwargs)
         return self
 
 
@@ -834,9 +816,14 @@ class Bernstein(Chebyshev):
     def _n_terms(self):
         return self.K + 1
 
+    def _setup(self, *args, **kwargs):
+        super()._setup(*args, **kwargs)
+        self._coeff = None  # bernstein_to_chebyshev(K) on the kernel's device
+        self._basis_image = {"key": None, "count": 0}  # _kernel_image's image (+ "kernel"), kept as Chebyshev._bn_fold is
+
     def _coeff_on(self, device):
         """C rounded once to fp32, on ``device``: a plain tensor, neither a parameter nor in ``state_dict``."""
-        c = getattr(self, "_coeff", None)
+        c = self._coeff
         if c is None or c.device != device:
             c = self._coeff = torch.as_tensor(bernstein_to_chebyshev(self.K).astype(np.float32)).to(device)
         return c
@@ -853,21 +840,20 @@ class Bernstein(Chebyshev):
         keeps its fold, which is computed from this image (the two maps commute: one mixes the rows of a channel, the other
         scales columns).  In the steady state nothing is launched and the kept weight images stay valid."""
         kernel = self.kernel.detach()
-        key = (kernel.data_ptr(), self.kernel._version)
-        img = getattr(self, "_basis_image", None)
-        if img is None or img["key"] != key or img["kernel"].device != kernel.device:
-            if img is None or img["kernel"].device != kernel.device or img["kernel"].shape != kernel.shape:
-                img = {"kernel": torch.empty_like(kernel), "count": 0 if img is None else img["count"]}
+        key = (kernel.data_ptr(), self.kernel._version, kernel.device)
+        img = self._basis_image
+        if img["key"] != key:
+            buf = img.get("kernel")
+            if buf is None or buf.device != kernel.device or buf.shape != kernel.shape:
+                img["kernel"] = torch.empty_like(kernel)
             _native.basis_change(kernel, self._coeff_on(kernel.device), out=img["kernel"])
             img["key"] = key
             img["count"] += 1
-            self._basis_image = img
         return img["kernel"], ("basis", img["count"])
 
     def invalidate_weights(self):
         super().invalidate_weights()
-        if getattr(self, "_basis_image", None) is not None:  # (keyed on the version counter a write through .data does not move)
-            self._basis_image["key"] = None
+        self._basis_image["key"] = None  # (keyed on the version counter a write through .data does not move)
 
 
 class GCNN_ResidualLayer(torch.nn.Module):
@@ -924,7 +910,7 @@ class GCNN_ResidualLayer(torch.nn.Module):
         if self.norm_type == "batch_norm" and _bn_native_ok(mod, x):
             # channels last as the map is: batch statistics through the batch-norm kernels with the module's scale and shift
             # (training), the elementwise kernel alone on the moving statistics (inference without autograd)
-            if self.training if training is None else bool(training):
+            if _batch_stats(self, training):
                 return _BatchNormActFunction.apply(x, mod.weight, mod.bias, mod, _native.ACT_NONE, False)
             if mod.running_mean is not None and not (torch.is_grad_enabled() and (
                     x.requires_grad or any(p is not None and p.requires_grad for p in (mod.weight, mod.bias)))):
@@ -932,11 +918,7 @@ class GCNN_ResidualLayer(torch.nn.Module):
                 b = None if mod.bias is None else mod.bias.detach().contiguous()
                 return _native.bn_apply(x.contiguous(), mod.running_mean, torch.rsqrt(mod.running_var + mod.eps), w, b)
         if self.norm_type == "batch_norm":
-            was = mod.training
-            mod.train(self.training if training is None else bool(training))
-            y = mod(x.transpose(1, 2)).transpose(1, 2)
-            mod.train(was)
-            return y
+            return _torch_batch_norm(mod, x, _batch_stats(self, training))
         axes = [a % x.dim() for a in mod._axes]
         if axes == list(range(x.dim() - len(axes), x.dim())):
             # the trailing axis alone (the default): the layer-norm kernels, in training and in inference; the module holds the parameters

@@ -95,6 +95,7 @@ class HealpyGCNN(torch.nn.Sequential):
         self.layers_in, self.layers_use = layers, layers_use
         self.n_neighbors = n_neighbors
         self.reduction_fac = reduction_fac
+        self._warned_training = False  # (forward warns once about train() mode with the default training=False)
 
     @staticmethod
     def _transform_indices(nside_in, nside_out, indices):
@@ -114,7 +115,7 @@ class HealpyGCNN(torch.nn.Sequential):
         no counterpart).  A network in ``model.train()`` mode that holds batch-norm layers and is called without the argument
         would silently normalise with -- and never update -- the moving statistics: that combination warns once; write
         ``model(x, training=True)`` in a training loop (``training=None``: follow ``self.training``)."""
-        if training is False and self.training and not getattr(self, "_warned_training", False):
+        if training is False and self.training and not self._warned_training:
             if any(getattr(layer, "use_bn", False) for layer in self):
                 import warnings
 
@@ -133,7 +134,7 @@ class HealpyGCNN(torch.nn.Sequential):
                 nxt = layers[i + 1] if i + 1 < len(layers) else None
                 # (forward_pool folds the moving statistics: not for a layer that would normalise with the batch's --
                 # training=None follows the layer's own mode, as Chebyshev.forward resolves it)
-                batch_stats = (layer.training and getattr(layer, "use_bn", False)) if training is None else bool(training)
+                batch_stats = gnn._batch_stats(layer, training) and (training is not None or getattr(layer, "use_bn", False))
                 if (isinstance(layer, gnn.Chebyshev) and isinstance(nxt, hp_nn.HealpyPool) and nxt.p == 1 and not batch_stats
                         and isinstance(x, torch.Tensor)):
                     y = layer.forward_pool(x, nxt.pool_type)

@@ -96,12 +96,14 @@ class Run:
     """One long-lived layer, its float64 model, and the steps of a sequence.  ``play`` applies a list of (step, args...)."""
 
     def __init__(self, cls, nside, K, Fin, Fout, seed=0, **kw):
+        """``Fout=None``: the layer is constructed without one and takes its input's width."""
         cols, vals, Lt = grid(nside)
-        self.M, self.Fin, self.Fout, self.kw, self.cls = cols.shape[0], Fin, Fout, kw, cls
+        self.M, self.Fin, self.Fout, self.kw, self.cls = cols.shape[0], Fin, Fin if Fout is None else Fout, kw, cls
         self._make = lambda **over: cls.from_prepared_ell(cols, vals, K, Fout=Fout, device="cuda:0", **{**kw, **over})
-        self.rng = np.random.default_rng(1000 * Fin + 10 * Fout + K + seed)
+        self.rng = np.random.default_rng(1000 * Fin + 10 * self.Fout + K + seed)
         self.layer = self._make()
         self.layer.build((1, self.M, Fin))
+        self.declared = set(vars(self.layer))  # a layer declares all it keeps at construction: play() holds it to that
         W, b = self.new_weights()
         with torch.no_grad():
             self.layer.kernel.copy_(dev(W))
@@ -136,6 +138,7 @@ class Run:
             print(f"step {i}: {step}")
             getattr(self, step[0])(*step[1:])
         torch.cuda.synchronize()
+        assert set(vars(self.layer)) == self.declared, f"attributes that appeared after build(): {sorted(set(vars(self.layer)) - self.declared)}"
         compared, relaxed = (TALLY[k] - self.start[k] for k in ("compared", "relaxed"))
         print(f"{compared} steps compared with a twin, {relaxed} relaxed")
         assert compared > 0 and 5 * relaxed <= compared
@@ -318,6 +321,15 @@ def test_train_and_eval_with_batch_norm(cls, K, Fin, Fout, act):
     run = Run(cls, 16, K, Fin, Fout, use_bias=True, use_bn=True, activation=act, precision="fp32", plan_options=NEVER)
     run.play(TRAIN_EVAL)
     assert run.model.num_batches_tracked == 3
+
+
+def test_more_than_nine_terms_without_Fout():
+    """K = 10, 16 channels, ``Fout`` omitted, nside 16: the smallest shape at which a real plan is asked whether the layer runs as
+    the chain of passes -- with the width ``build()`` resolved, forward and input gradient.  (``self.Fout`` = None went to
+    ``dsph_plan_uses_chain``: ``TypeError`` in the first forward.)"""
+    run = Run(gnn_layers.Chebyshev, 16, 10, 16, None, use_bias=True, activation="relu", plan_options=NEVER)
+    assert run.layer.Fout is None and run.layer._Fout == 16 and tuple(run.layer.kernel.shape) == (160, 16)
+    run.play([("infer", 2), ("sgd", 2)])
 
 
 def test_bernstein_steady_state():

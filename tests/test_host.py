@@ -371,6 +371,28 @@ def test_folded_batch_norm_parameters_and_their_cache():
     _, b4, ver4 = layer._folded_bn()
     s4 = torch.rsqrt(layer.bn.running_var + layer.bn.eps)
     assert ver4 != ver3 and torch.allclose(b4, layer.bias.detach().reshape(-1) - layer.bn.running_mean * s4, rtol=1e-6, atol=1e-7)
+    # eps is part of the fold: a changed eps re-folds
+    layer.bn.eps = 1e-2
+    k5, _, ver5 = layer._folded_bn()
+    s5 = torch.rsqrt(layer.bn.running_var + 1e-2)
+    assert ver5 != ver4 and torch.allclose(k5, layer.kernel.detach() * s5, rtol=1e-6), "a changed eps re-folds"
+    # so is the identity of the moving statistics: a buffer rebound to another tensor at the SAME version counter re-folds
+    var = torch.full((4,), 100.0)
+    with torch.no_grad():
+        while var._version < layer.bn.running_var._version:
+            var.add_(0.0)
+    assert var._version == layer.bn.running_var._version and var.data_ptr() != layer.bn.running_var.data_ptr()
+    layer.bn.running_var = var
+    k6, _, ver6 = layer._folded_bn()
+    assert ver6 != ver5 and torch.allclose(k6, layer.kernel.detach() / np.sqrt(100.0 + 1e-2), rtol=1e-6), "rebound statistics re-fold"
+    mean = torch.full((4,), 3.0)
+    with torch.no_grad():
+        while mean._version < layer.bn.running_mean._version:
+            mean.add_(0.0)
+    assert mean._version == layer.bn.running_mean._version
+    layer.bn.running_mean = mean
+    _, b7, ver7 = layer._folded_bn()
+    assert ver7 != ver6 and torch.allclose(b7, layer.bias.detach().reshape(-1) - 3.0 / np.sqrt(100.0 + 1e-2), rtol=1e-6, atol=1e-7)
 
 
 def test_precision_rules_of_the_backward_and_the_f16_scale():
@@ -409,3 +431,105 @@ def test_precision_rules_of_the_backward_and_the_f16_scale():
     plan = _Plan()
     layer._set_f16_scale(plan, None)
     assert plan.calls == []
+
+
+def _constructor_pair(**kw):
+    """The same layer through ``Chebyshev(L=...)`` and through ``from_prepared_ell`` on the first one's L~."""
+    a = gnn_layers.Chebyshev(L=healpix.healpix_laplacian(2, mode="grid"), **kw)
+    return a, gnn_layers.Chebyshev.from_prepared_ell(a._ell_cols, a._ell_vals, lmax=a.lmax, **kw)
+
+
+def test_the_two_constructors_build_the_same_layer():
+    """``Chebyshev(L=...)`` and ``from_prepared_ell`` with every shared keyword at a non-default value: after ``build()`` the same
+    attributes, equal in everything but ``L`` (``from_prepared_ell`` has none) -- and the same words for a bad argument."""
+    init = lambda t: torch.nn.init.constant_(t, 0.125)  # noqa: E731
+    kw = dict(K=3, Fout=6, initializer=init, activation="elu", use_bias=True, use_bn=True, n_matmul_splits=2, device="cpu",
+              precision="f16x3", algo="fused", plan_options={_native.OPT_STRIPS: _native.STRIPS_NEVER}, graph=True, x_absmax=2.5,
+              regularizer="l1")
+    a, b = _constructor_pair(**kw)
+    for layer in (a, b):
+        layer.build((1, 48, 5))
+    va, vb = vars(a), vars(b)
+    assert set(va) == set(vb)
+    assert a.L is not None and b.L is None and a.lmax == b.lmax
+    for name in sorted(set(va) - {"L", "lmax"}):
+        x, y = va[name], vb[name]
+        if isinstance(x, torch.Tensor):
+            continue
+        if isinstance(x, np.ndarray):
+            assert x.dtype == y.dtype and np.array_equal(x, y), name
+        elif name in ("_parameters", "_modules"):  # (the tensors and modules themselves differ: the same names and shapes)
+            assert list(x) == list(y) and [tuple(t.shape) for t in a.parameters()] == [tuple(t.shape) for t in b.parameters()], name
+        else:
+            assert x == y, name
+    assert (a.precision, a.algo, a._use_graph, a.x_absmax, a.kwargs, a._Fout, a._act_code) == (
+        "f16x3", "fused", True, 2.5, {"regularizer": "l1"}, 6, _native.ACT_ELU)
+    for bad in ({"precision": "fp8"}, {"algo": "magic"}, {"K": 0}):
+        said = []
+        for make in (lambda kw: gnn_layers.Chebyshev(L=np.eye(4), **kw),
+                     lambda kw: gnn_layers.Chebyshev.from_prepared_ell(np.zeros((4, 1), np.int32), np.ones((4, 1), np.float32), **kw)):
+            with pytest.raises(ValueError) as err:
+                make({"K": 2, **bad})
+            said.append(str(err.value))
+        assert said[0] == said[1] and said[0], bad
+    with pytest.raises(ValueError, match="precision must be one of"):
+        gnn_layers.Chebyshev.from_prepared_ell(np.zeros((4, 1), np.int32), np.ones((4, 1), np.float32), 2, precision="fp8")
+    with pytest.raises(ValueError, match="algo must be one of"):
+        gnn_layers.Chebyshev.from_prepared_ell(np.zeros((4, 1), np.int32), np.ones((4, 1), np.float32), 2, algo="magic")
+
+
+class _StandInPlan:
+    """What the layer asks of its plan on the host: ``set_option`` recorded, ``uses_chain`` taking its arguments as the C call
+    does (``int()``: None raises)."""
+
+    def __init__(self):
+        self.calls = []
+
+    def set_option(self, opt, value):
+        self.calls.append((opt, value))
+
+    def uses_chain(self, Fin, Fout, K):
+        self.calls.append(("uses_chain", int(Fin), int(Fout), int(K)))
+        return False
+
+
+@pytest.mark.parametrize("cls", [gnn_layers.Chebyshev, gnn_layers.Monomial, gnn_layers.Bernstein])
+def test_no_attribute_appears_after_build(cls):
+    """A layer declares all it will ever keep at construction: the caches of later calls (the batch-norm fold, the f16 input
+    scale, invalidation) fill attributes that are already there."""
+    layer = cls.from_prepared_ell(np.zeros((4, 1), np.int32), np.ones((4, 1), np.float32), 3, use_bn=True, use_bias=True,
+                                  precision="f16x3", device="cpu")
+    layer.build((1, 4, 5))
+    declared = set(vars(layer))
+    for name in ("_plan", "_plan_t", "_workspace", "_workspace_t", "_workspace_w", "_prepared", "_wkey", "_graph", "_bn_fold", "_f16_xexp",
+                 "_Fin", "_Fout") + (("_coeff", "_basis_image") if cls is gnn_layers.Bernstein else ()):
+        assert name in declared, name
+    if cls is not gnn_layers.Bernstein:  # (its fold reads the basis image: a device kernel)
+        layer._folded_bn()
+    layer.x_absmax = 3.0
+    plan = _StandInPlan()
+    layer._set_f16_scale(plan, None)
+    assert plan.calls == [(_native.OPT_F16_XEXP, 12)] and layer._f16_xexp == 12
+    layer.invalidate_weights()
+    assert set(vars(layer)) == declared
+    assert layer._wkey is None and layer._graph is None
+
+
+@pytest.mark.parametrize("transposed", [False, True], ids=["forward", "input-gradient"])
+def test_more_than_nine_terms_without_Fout(transposed):
+    """K = 10 on 16 channels with ``Fout`` omitted: the chain query gets the width ``build()`` resolved, in both directions.
+    (It got ``self.Fout`` = None: ``TypeError: int() argument must be ... not 'NoneType'`` from ``_prec_code()``.)"""
+    layer = gnn_layers.Chebyshev.from_prepared_ell(np.zeros((4, 1), np.int32), np.ones((4, 1), np.float32), 10, device="cpu")
+    layer.build((1, 4, 16))
+    assert layer.Fout is None and tuple(layer.kernel.shape) == (160, 16)
+    layer._plan = layer._plan_t = plan = _StandInPlan()
+    if transposed:
+        assert layer._chained(transposed=True) is False
+    else:
+        assert layer._prec_code() == _native.PREC_BF16X3, "one pass, 16 channels: the three-term split"
+    assert plan.calls == [("uses_chain", 16, 16, 10)] and layer._Fout == 16
+    wide = gnn_layers.Chebyshev.from_prepared_ell(np.zeros((4, 1), np.int32), np.ones((4, 1), np.float32), 10, Fout=32, device="cpu")
+    wide.build((1, 4, 16))
+    wide._plan = wide._plan_t = plan = _StandInPlan()
+    wide._chained(transposed=transposed)
+    assert plan.calls == [("uses_chain", 32, 16, 10) if transposed else ("uses_chain", 16, 32, 10)]
