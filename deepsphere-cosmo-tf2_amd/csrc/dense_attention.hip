@@ -28,13 +28,11 @@
 // Two launches on the caller's stream; every output element has one writer and a fixed order of summation.
 #include <cmath>
 
-#include "dsphere_mapops.h"
+#include "dense_attention_common.h"
 
 namespace dsph {
 
 typedef float da_f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int DA_TILE = 64;  // rows a workgroup owns (16 per wave) = rows of a streamed tile
 
 template <int D>
 struct DaShape {
@@ -119,35 +117,6 @@ __device__ __forceinline__ void da_stage_store(const float4 (&s)[DaShape<D>::STA
     const int idx = tid + 256 * i, row = idx / (D / 4), c4 = idx % (D / 4);
     if (row < DA_TILE) *reinterpret_cast<float4*>(tile + row * DaShape<D>::STRIDE + 4 * c4) = s[i];
   }
-}
-
-__device__ __forceinline__ float da_group_max(float v) {
-  v = fmaxf(v, __shfl_xor(v, 16));
-  return fmaxf(v, __shfl_xor(v, 32));
-}
-__device__ __forceinline__ float da_group_sum(float v) {
-  v += __shfl_xor(v, 16);
-  return v + __shfl_xor(v, 32);
-}
-
-// which (map, head, block of 64 rows) a workgroup owns, and the lane's row in it
-struct DaBlock {
-  int64_t base;   // first row of the map
-  int64_t row;    // the lane's owned row
-  int64_t ch;     // first channel of the head
-  int h;
-  bool own;       // row < M
-};
-
-__device__ __forceinline__ DaBlock da_block(int64_t M, int heads, int D, int64_t nblk) {
-  DaBlock B;
-  const int64_t b = blockIdx.x, blk = b % nblk, nh = b / nblk;
-  B.h = (int)(nh % heads);
-  B.base = (nh / heads) * M;
-  B.ch = (int64_t)B.h * D;
-  B.row = blk * DA_TILE + (threadIdx.x >> 6) * 16 + (threadIdx.x & 15);
-  B.own = B.row < M;
-  return B;
 }
 
 // the lane's accumulator, times f, to channels [16 b + 4 g, + 4) of its row
@@ -382,17 +351,6 @@ __global__ __launch_bounds__(256) void dense_attention_dkv_kernel(const float* _
   da_store_acc<D>(dk + (B.base + B.row) * ldg + B.ch, ak, scale, g);
 }
 
-// workgroups of a launch: one per (map, head, block of 64 rows)
-static int dense_grid(const char* who, int64_t N, int64_t M, int32_t heads, int64_t* nblk, unsigned* grid) {
-  *nblk = (M + DA_TILE - 1) / DA_TILE;
-  if (N > 0x7fffffffLL / heads || N * heads > 0x7fffffffLL / *nblk) {
-    set_error("%s: grid too large (N %lld, heads %d, %lld row blocks)", who, (long long)N, (int)heads, (long long)*nblk);
-    return DSPH_E_UNSUPPORTED;
-  }
-  *grid = (unsigned)(N * heads * *nblk);
-  return DSPH_OK;
-}
-
 #define DENSE_BY_DEPTH(depth, CALL) \
   switch (depth) {                  \
     case 4: CALL(4); break;         \
@@ -401,14 +359,6 @@ static int dense_grid(const char* who, int64_t N, int64_t M, int32_t heads, int6
     case 32: CALL(32); break;       \
     default: CALL(64); break;       \
   }
-
-// the shape limits of the kernels above, each named in its message
-static int dense_attention_args_ok(const char* who, int64_t ld, int64_t N, int64_t M, int32_t heads, int32_t depth) {
-  if (N < 0) { set_error("%s: negative batch size N = %lld", who, (long long)N); return DSPH_E_BADARG; }
-  if (M < 1) { set_error("%s: M = %lld rows, must be at least 1", who, (long long)M); return DSPH_E_BADARG; }
-  const int rc = attention_shape_ok(who, heads, depth, "");
-  return rc != DSPH_OK ? rc : attention_stride_ok(who, ld, heads, depth);
-}
 
 }  // namespace dsph
 

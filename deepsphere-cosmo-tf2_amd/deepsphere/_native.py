@@ -120,6 +120,10 @@ SIGNATURES = {
                                                      _c_vp]),
     "dsph_dense_attention_backward": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, _c_i64, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64,
                                                       _c_i64, _c_i64, _c_i32, _c_i32, ctypes.c_int, _c_vp]),
+    "dsph_dense_attention_forward_prec": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, _c_i64, _c_vp, _c_vp, _c_i64, _c_i64, _c_i32, _c_i32,
+                                                          _c_i32, ctypes.c_int, _c_vp]),
+    "dsph_dense_attention_backward_prec": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, _c_i64, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp,
+                                                           _c_i64, _c_i64, _c_i64, _c_i32, _c_i32, _c_i32, ctypes.c_int, _c_vp]),
     "dsph_ell_smooth": (ctypes.c_int, [_c_vp, _c_vp, _c_i64, _c_i32, _c_vp, _c_vp, _c_i64, _c_i32, _c_vp, _c_i32, _c_vp, _c_i32,
                                         ctypes.c_int, _c_vp]),
     "dsph_basis_change": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, _c_i32, _c_i32, _c_i32, _c_i32, ctypes.c_int, _c_vp]),
@@ -658,33 +662,36 @@ def nbr_attention_backward(q, k, v, out, lse, dout, nbr, nbrT, num_heads, grads=
     return grads
 
 
-def dense_attention(q, k, v, num_heads, need_lse=True):
-    """Attention of every row over ALL rows of its map on (N, M, d) maps (``dsph_dense_attention_forward``; flash style, no logit
-    reaches memory): -> (out (N, M, d), lse (N, M, heads) or None).  q, k, v may be channel slices of one wider buffer
-    (``rows_layout``)."""
+def dense_attention(q, k, v, num_heads, need_lse=True, precision=PREC_FP32):
+    """Attention of every row over ALL rows of its map on (N, M, d) maps (``dsph_dense_attention_forward_prec``; flash style, no
+    logit reaches memory): -> (out (N, M, d), lse (N, M, heads) or None).  q, k, v may be channel slices of one wider buffer
+    (``rows_layout``).  ``precision``: PREC_FP32 (exact-fp32 MFMA, every depth), PREC_BF16X6 or PREC_BF16X3 (the bf16 split
+    arithmetics, depth 32 and 64; any other depth raises)."""
     import torch
 
     require_gpu()
     ld, N, M, d = _qkv_layout(q, k, v, num_heads)
     out = torch.empty((N, M, d), dtype=torch.float32, device=q.device)
     lse = torch.empty((N, M, num_heads), dtype=torch.float32, device=q.device) if need_lse else None
-    rc = lib().dsph_dense_attention_forward(_ptr(q), _ptr(k), _ptr(v), ld, _ptr(out), _ptr(lse), int(N), int(M), int(num_heads),
-                                            int(d // num_heads), q.device.index, _stream_ptr(q.device))
-    check(rc, "dsph_dense_attention_forward")
+    rc = lib().dsph_dense_attention_forward_prec(_ptr(q), _ptr(k), _ptr(v), ld, _ptr(out), _ptr(lse), int(N), int(M),
+                                                 int(num_heads), int(d // num_heads), int(precision), q.device.index,
+                                                 _stream_ptr(q.device))
+    check(rc, "dsph_dense_attention_forward_prec")
     return out, lse
 
 
-def dense_attention_backward(q, k, v, out, lse, dout, num_heads, grads=None):
-    """dq, dk, dv of ``dense_attention`` (``dsph_dense_attention_backward``; deterministic, nothing of size M^2 is allocated).
-    ``grads``: three tensors to write into (channel slices of one buffer: the gradient of a fused q/k/v projection comes out as
-    one tensor); allocated when None."""
+def dense_attention_backward(q, k, v, out, lse, dout, num_heads, grads=None, precision=PREC_FP32):
+    """dq, dk, dv of ``dense_attention`` (``dsph_dense_attention_backward_prec``; deterministic, nothing of size M^2 is
+    allocated).  ``grads``: three tensors to write into (channel slices of one buffer: the gradient of a fused q/k/v projection
+    comes out as one tensor); allocated when None.  ``precision``: as in ``dense_attention``."""
     require_gpu()
     ld, N, M, d = _qkv_layout(q, k, v, num_heads)
     out, lse, dout, grads, gld, delta = _attention_grad_buffers(q, out, lse, dout, grads, num_heads)
-    rc = lib().dsph_dense_attention_backward(_ptr(q), _ptr(k), _ptr(v), ld, _ptr(out), _ptr(lse), _ptr(dout),
-                                             _ptr(delta), _ptr(grads[0]), _ptr(grads[1]), _ptr(grads[2]), gld, int(N), int(M),
-                                             int(num_heads), int(d // num_heads), q.device.index, _stream_ptr(q.device))
-    check(rc, "dsph_dense_attention_backward")
+    rc = lib().dsph_dense_attention_backward_prec(_ptr(q), _ptr(k), _ptr(v), ld, _ptr(out), _ptr(lse), _ptr(dout),
+                                                  _ptr(delta), _ptr(grads[0]), _ptr(grads[1]), _ptr(grads[2]), gld, int(N),
+                                                  int(M), int(num_heads), int(d // num_heads), int(precision), q.device.index,
+                                                  _stream_ptr(q.device))
+    check(rc, "dsph_dense_attention_backward_prec")
     return grads
 
 

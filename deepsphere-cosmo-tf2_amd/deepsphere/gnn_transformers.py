@@ -6,7 +6,8 @@ embedding lookups that materialise q, k and v per edge, ``exp`` and two segment 
 and two backward (``csrc/nbr_attention.hip``) working on channels-last (N, M, d) maps and a padded neighbour table.  The dense
 attention of ``Graph_ViT`` -- in the reference two ``matmul``s around a softmax over a materialised (N, heads, M, M) tensor
 (``:14-51``) -- is a flash-style kernel on the exact-fp32 MFMA (``csrc/dense_attention.hip``: key tiles through LDS, online
-softmax, no logit in memory; two deterministic backward launches) on the same layout.  The layer norms around both, with the add
+softmax, no logit in memory; two deterministic backward launches) on the same layout, or, by ``precision=``, on the bf16 MFMA
+through a six- or three-term split of its fp32 operands (``csrc/dense_attention_split.hip``, depth 32 and 64 per head).  The layer norms around both, with the add
 between them, run on the layer-norm kernels (``csrc/layer_norm.hip``); the dense layers are the host framework's, like the GEMM of
 ``HealpyPseudoConv``.
 """
@@ -112,23 +113,39 @@ class _SparseAttentionPacked(torch.autograd.Function):
         return dqkv, None, None, None
 
 
+# The arithmetic of the dense-attention products, by name.  "fp32": the exact-fp32 MFMA, every depth.  "bf16x6" (fp32-equivalent)
+# and "bf16x3": the bf16 split kernels, depth 32 and 64 per head only.  There is no "auto" and nothing falls back.
+_DENSE_PRECISIONS = {"fp32": _native.PREC_FP32, "bf16x6": _native.PREC_BF16X6, "bf16x3": _native.PREC_BF16X3}
+_SPLIT_DEPTHS = (32, 64)
+
+
+def _dense_precision(precision, depth=None):
+    """The name of a dense-attention arithmetic, checked (and, with ``depth``, checked against the depths it runs)."""
+    if precision not in _DENSE_PRECISIONS:
+        raise ValueError(f"precision = {precision!r} is not one of 'fp32', 'bf16x6', 'bf16x3'")
+    if precision != "fp32" and depth is not None and depth not in _SPLIT_DEPTHS:
+        raise ValueError(f"precision = {precision!r} runs key_dim (channels per head) 32 or 64, not {depth}: the bf16 split "
+                         "kernels contract 32 channels per instruction; use precision='fp32'")
+    return precision
+
+
 class _DenseAttention(torch.autograd.Function):
     """out = softmax over ALL rows of (q k^T / sqrt(depth)) v; saves q, k, v, out and the log-sum-exp, gradients from
     ``dsph_dense_attention_backward``."""
 
     @staticmethod
-    def forward(ctx, q, k, v, num_heads):
+    def forward(ctx, q, k, v, num_heads, precision=_native.PREC_FP32):
         q, k, v = _kernel_layout(q, k, v)
-        out, lse = _native.dense_attention(q, k, v, num_heads)
+        out, lse = _native.dense_attention(q, k, v, num_heads, precision=precision)
         ctx.save_for_backward(q, k, v, out, lse)
-        ctx.num_heads = num_heads
+        ctx.num_heads, ctx.precision = num_heads, precision
         return out
 
     @staticmethod
     def backward(ctx, dout):
         q, k, v, out, lse = ctx.saved_tensors
-        dq, dk, dv = _native.dense_attention_backward(q, k, v, out, lse, dout, ctx.num_heads)
-        return dq, dk, dv, None
+        dq, dk, dv = _native.dense_attention_backward(q, k, v, out, lse, dout, ctx.num_heads, precision=ctx.precision)
+        return dq, dk, dv, None, None
 
 
 class _DenseAttentionPacked(torch.autograd.Function):
@@ -136,15 +153,15 @@ class _DenseAttentionPacked(torch.autograd.Function):
     slices read in place, dq, dk, dv written into the slices of ONE gradient tensor."""
 
     @staticmethod
-    def forward(ctx, qkv, num_heads):
+    def forward(ctx, qkv, num_heads, precision=_native.PREC_FP32):
         qkv = qkv.contiguous()
         d = qkv.shape[2] // 3
         q, k, v = qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:]
         if d % 4 != 0:  # (slices that are not 16-byte aligned: copies; the kernels then name their limit)
             q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
-        out, lse = _native.dense_attention(q, k, v, num_heads)
+        out, lse = _native.dense_attention(q, k, v, num_heads, precision=precision)
         ctx.save_for_backward(qkv, out, lse)
-        ctx.num_heads = num_heads
+        ctx.num_heads, ctx.precision = num_heads, precision
         return out
 
     @staticmethod
@@ -153,11 +170,11 @@ class _DenseAttentionPacked(torch.autograd.Function):
         d = qkv.shape[2] // 3
         dqkv = torch.empty_like(qkv)
         _native.dense_attention_backward(qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:], out, lse, dout, ctx.num_heads,
-                                         grads=(dqkv[..., :d], dqkv[..., d:2 * d], dqkv[..., 2 * d:]))
-        return dqkv, None
+                                         grads=(dqkv[..., :d], dqkv[..., d:2 * d], dqkv[..., 2 * d:]), precision=ctx.precision)
+        return dqkv, None, None
 
 
-def scaled_dot_product_attention(q, k, v, num_heads):
+def scaled_dot_product_attention(q, k, v, num_heads, precision="fp32"):
     """Attention of every row over all rows of its map (reference ``gnn_transformers.py:14-51`` with ``mask=None``),
     differentiable.
 
@@ -165,12 +182,16 @@ def scaled_dot_product_attention(q, k, v, num_heads):
         -- the reference's ``split_heads`` without its transposes.  Strided views are read in place when their rows share one
         stride (three slices of one projection buffer).
     :param num_heads: number of heads; d / num_heads one of 4, 8, 16, 32, 64 and d <= 256
+    :param precision: not a reference argument -- the arithmetic of the products: "fp32" (exact-fp32 MFMA), "bf16x6" (bf16 MFMA
+        on a three-term split of both operands, fp32-equivalent) or "bf16x3" (two terms, operands to 16 bits); the split ones
+        run d / num_heads 32 and 64 only and raise elsewhere
     :return: (N, M, d)
 
     The reference also returns the attention weights, an (N, heads, M, M) tensor that nothing in it reads; they are never formed
     here (that is the point of the kernel), and its ``mask`` argument, which ``Graph_ViT`` never passes, is not rebuilt."""
     _require_hip(q, k, v)
-    return _DenseAttention.apply(q, k, v, int(num_heads))
+    code = _DENSE_PRECISIONS[_dense_precision(precision)]
+    return _DenseAttention.apply(q, k, v, int(num_heads), code)
 
 
 def scaled_dot_product_sparse_attention(q, k, v, nbr, nbrT, num_heads):
@@ -233,7 +254,7 @@ class MultiHeadAttention(torch.nn.Module):
     (eps = 1e-3, Keras' default).  ``use_norm=False`` makes both norms the identity (the reference crashes there: it calls
     norms it did not create)."""
 
-    def __init__(self, d_model, num_heads, use_norm=True, activation="relu", sparse_A_indices=None, dense=False):
+    def __init__(self, d_model, num_heads, use_norm=True, activation="relu", sparse_A_indices=None, dense=False, precision="fp32"):
         """
         :param d_model: channels of q, k and v (all heads together)
         :param num_heads: number of heads; must divide ``d_model``
@@ -245,6 +266,9 @@ class MultiHeadAttention(torch.nn.Module):
         :param dense: not a reference argument -- attention over ALL rows on the dense kernel (what the reference does when it has
             no ``sparse_A_indices``; ``Graph_ViT`` builds its blocks this way).  No tables are needed or read.  The reference's
             ``mask`` argument of that path is not rebuilt (``Graph_ViT`` never passes one).
+        :param precision: not a reference argument -- the arithmetic of the dense attention's products, "fp32" (default),
+            "bf16x6" or "bf16x3" (``scaled_dot_product_attention``).  A split one needs ``dense=True`` and 32 or 64 channels per
+            head; the attention over graph neighbours is a memory-bound gather and has no split.
         """
         super().__init__()
         if num_heads < 1 or d_model % num_heads != 0:
@@ -252,6 +276,10 @@ class MultiHeadAttention(torch.nn.Module):
         self.d_model, self.num_heads, self.use_norm = int(d_model), int(num_heads), bool(use_norm)
         self.depth = self.d_model // self.num_heads
         self.dense_attention = bool(dense)
+        self.precision = _dense_precision(precision, self.depth)
+        if self.precision != "fp32" and not self.dense_attention:
+            raise ValueError(f"precision = {precision!r} needs dense=True: the attention over graph neighbours has no split "
+                             "arithmetic")
         self.activation, self._act_code = _resolve_activation(activation)
         if sparse_A_indices is not None:
             nbr, nbrT = _tables_from_indices(sparse_A_indices)
@@ -290,7 +318,7 @@ class MultiHeadAttention(torch.nn.Module):
         x = _layer_norm(self.layer_norm1, inputs) if self.use_norm else inputs
         qkv = self.wqkv(x)  # (N, M, 3 d): q | k | v
         if self.dense_attention:
-            att = _DenseAttentionPacked.apply(qkv, self.num_heads)
+            att = _DenseAttentionPacked.apply(qkv, self.num_heads, _DENSE_PRECISIONS[self.precision])
         else:
             att = _SparseAttentionPacked.apply(qkv, nbr, nbrT, self.num_heads)
         if self.use_norm:
@@ -395,7 +423,8 @@ class Graph_ViT(torch.nn.Module):
     ``pos_encoder.pos_embedding`` (1, M / 4^p, d) and ``mha_layers.{i}.wqkv / dense / layer_norm1 / layer_norm2`` as in
     ``Graph_Transformer``.  Runs on a HIP device only."""
 
-    def __init__(self, p, key_dim, num_heads, positional_encoding=True, n_layers=1, activation="relu", layer_norm=True):
+    def __init__(self, p, key_dim, num_heads, positional_encoding=True, n_layers=1, activation="relu", layer_norm=True,
+                 precision="fp32"):
         super().__init__()
         if not p >= 1:
             raise IOError("The super pixel size factor p has to be at least 1!")
@@ -410,12 +439,13 @@ class Graph_ViT(torch.nn.Module):
         self.n_layers = n_layers
         self.activation = activation
         self.layer_norm = layer_norm
+        self.precision = _dense_precision(precision, int(key_dim))  # (of the blocks' attention; see MultiHeadAttention)
         self.embed = None
         if self.positional_encoding:
             self.pos_encoder = AddPositionEmbs()
         self.mha_layers = torch.nn.ModuleList(
             MultiHeadAttention(d_model=self.embedding_size, num_heads=self.num_heads, use_norm=self.layer_norm,
-                               activation=self.activation, dense=True) for _ in range(n_layers))
+                               activation=self.activation, dense=True, precision=self.precision) for _ in range(n_layers))
 
     def build(self, input_shape, device=None):
         n_nodes, g = int(input_shape[1]), self.embed_filter_size

@@ -402,7 +402,8 @@ class Healpy_ViT(Graph_ViT):
     """``Graph_ViT`` under its HEALPix name (reference ``healpy_layers.py:381-414``, a subclass that adds nothing): a layer, not
     a deferred spec -- it needs no graph.  The model builder counts it as a reduction by 2^p in nside, like ``HealpyPool``."""
 
-    def __init__(self, p, key_dim, num_heads, positional_encoding=True, n_layers=1, activation="relu", layer_norm=True):
+    def __init__(self, p, key_dim, num_heads, positional_encoding=True, n_layers=1, activation="relu", layer_norm=True,
+                 precision="fp32"):
         """
         :param p: the super-pixels are the 4^p NEST children of a pixel at nside / 2^p; p >= 1
         :param key_dim: channels of key, query and value per head; the embedding has ``key_dim * num_heads`` channels
@@ -411,9 +412,11 @@ class Healpy_ViT(Graph_ViT):
         :param n_layers: number of attention blocks
         :param activation: activation of the blocks
         :param layer_norm: layer norms in the blocks
+        :param precision: arithmetic of the attention's products: "fp32" (default), "bf16x6" or "bf16x3" -- the bf16 split
+            kernels, ``key_dim`` 32 or 64 only (``gnn_transformers.MultiHeadAttention``)
         """
         super().__init__(p=p, key_dim=key_dim, num_heads=num_heads, positional_encoding=positional_encoding, n_layers=n_layers,
-                         activation=activation, layer_norm=layer_norm)
+                         activation=activation, layer_norm=layer_norm, precision=precision)
 
 
 class _SmoothFunction(torch.autograd.Function):

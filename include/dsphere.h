@@ -458,6 +458,24 @@ int dsph_dense_attention_backward(const float* q, const float* k, const float* v
                                   const float* dout, float* delta, float* dq, float* dk, float* dv, int64_t ld_grad, int64_t N,
                                   int64_t M, int32_t heads, int32_t depth, int device, void* hip_stream);
 
+/* The same two calls with a choice of arithmetic for their matrix products (csrc/dense_attention_split.hip); everything above
+ * holds, argument checks and messages included.  `precision`:
+ *   DSPH_PREC_FP32    the two entry points above, bit for bit (every depth)
+ *   DSPH_PREC_BF16X6  every product (q k^T, p v, dout v^T, ds k, ds^T q, p^T dout) on v_mfma_f32_16x16x32_bf16 with both operands
+ *                     split into three bf16 terms, six partial products, fp32 accumulation: fp32-equivalent
+ *   DSPH_PREC_BF16X3  two terms, three partial products: operands carry 16 significant bits
+ * Each term is the round-to-nearest bf16 of the running remainder; bf16 has fp32's exponent range, so there is no scale rule and
+ * no range condition.  The softmax statistics, exp, lse, delta and the rescalings stay fp32.  Same blocking, layouts, tails and
+ * determinism (one writer per element, no atomics) as the fp32 kernels.
+ * The split arithmetics run depth 32 and 64 (the contraction fills the instruction's K = 32); at depth 4, 8 or 16 they return
+ * DSPH_E_UNSUPPORTED naming the depths 32, 64, before any launch -- there is no fallback to fp32.  Any other precision code
+ * (DSPH_PREC_F16X3 included): DSPH_E_BADARG. */
+int dsph_dense_attention_forward_prec(const float* q, const float* k, const float* v, int64_t ld, float* out, float* lse, int64_t N,
+                                      int64_t M, int32_t heads, int32_t depth, int32_t precision, int device, void* hip_stream);
+int dsph_dense_attention_backward_prec(const float* q, const float* k, const float* v, int64_t ld, const float* out, const float* lse,
+                                       const float* dout, float* delta, float* dq, float* dk, float* dv, int64_t ld_grad, int64_t N,
+                                       int64_t M, int32_t heads, int32_t depth, int32_t precision, int device, void* hip_stream);
+
 /* One pass of Gaussian smoothing: a wide-row ELL matrix over a map of few channels (plan-free; csrc/ell_smooth.hip).
  * Replaces: one utils.split_sparse_dense_matmul per channel and repetition of healpy_layers.HealpySmoothing.call (reference
  * healpy_layers.py:725-764) with the transposes, the unstack / stack and the mask multiply around them.

@@ -10,11 +10,14 @@ this process, alternating, after a warm-up; times are medians of device-event ti
 products of 2 N heads M^2 depth each forward (4 N heads M^2 depth), and 2.5 times that backward (five products); the kernels'
 backward recomputes the logits in both passes (seven products).  The rate is the algorithmic FLOPs over the time, against the
 157 TFLOP/s of the fp32 MFMA (64 FLOP / clk / SIMD x 4 SIMDs x 256 CUs x 2.4 GHz).  Peak memory: torch.cuda.max_memory_allocated
-over one call of each side, above what q, k, v and the upstream gradient occupy.  Prints the figures and one JSON line.  Needs a
-GPU: there is no CPU fallback and no figure without one.
+over one call of each side, above what q, k, v and the upstream gradient occupy.  The two bf16 split arithmetics of the kernels
+(``precision`` PREC_BF16X6, PREC_BF16X3; depth 32 and 64) are further cases of the same alternating loop, ``bf16x6_*`` and
+``bf16x3_*``, with their own agreement figures and their time against the fp32 kernels' (``kernel_*``, the baseline).  Prints
+the figures and one JSON line.  Needs a GPU: there is no CPU fallback and no figure without one.
 """
 
 import argparse
+import functools
 import json
 import os
 import statistics
@@ -82,12 +85,12 @@ def main():
     g = torch.randn((N, M, d), generator=gen, device=dev)
     q, k, v = qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:]
 
-    def kernel_fwd():
-        return _native.dense_attention(q, k, v, heads)
+    def kernel_fwd(precision=_native.PREC_FP32):
+        return _native.dense_attention(q, k, v, heads, precision=precision)
 
-    def kernel_fwd_bwd():
-        out, lse = _native.dense_attention(q, k, v, heads)
-        return _native.dense_attention_backward(q, k, v, out, lse, g, heads)
+    def kernel_fwd_bwd(precision=_native.PREC_FP32):
+        out, lse = _native.dense_attention(q, k, v, heads, precision=precision)
+        return _native.dense_attention_backward(q, k, v, out, lse, g, heads, precision=precision)
 
     def torch_fwd():
         with torch.no_grad():
@@ -99,15 +102,20 @@ def main():
         return [a.grad for a in t]
 
     cases = {"kernel_fwd": kernel_fwd, "kernel_fwd_bwd": kernel_fwd_bwd}
+    splits = {"bf16x6": _native.PREC_BF16X6, "bf16x3": _native.PREC_BF16X3} if args.depth in (32, 64) else {}
+    for name, code in splits.items():
+        cases[name + "_fwd"] = functools.partial(kernel_fwd, code)
+        cases[name + "_fwd_bwd"] = functools.partial(kernel_fwd_bwd, code)
     agree = {}
     if not args.skip_baseline:
         cases.update({"torch_fwd": torch_fwd, "torch_fwd_bwd": torch_fwd_bwd})
         # same numbers first (faster and different is not faster)
-        out_k, out_t = kernel_fwd()[0], torch_fwd()
-        gk, gt = kernel_fwd_bwd(), torch_fwd_bwd()
-        agree["out"] = float((out_k - out_t).abs().max() / out_t.abs().max())
-        for name, a, b in zip(("dq", "dk", "dv"), gk, gt):
-            agree[name] = float((a - b).abs().max() / b.abs().max())
+        out_t, gt = torch_fwd(), torch_fwd_bwd()
+        for prefix, code in [("", _native.PREC_FP32)] + [(n + "_", c) for n, c in splits.items()]:
+            out_k, gk = kernel_fwd(code)[0], kernel_fwd_bwd(code)
+            agree[prefix + "out"] = float((out_k - out_t).abs().max() / out_t.abs().max())
+            for name, a, b in zip(("dq", "dk", "dv"), gk, gt):
+                agree[prefix + name] = float((a - b).abs().max() / b.abs().max())
         del out_k, out_t, gk, gt
     for _ in range(args.warmup):
         for fn in cases.values():
@@ -121,7 +129,7 @@ def main():
     spread = {name: (min(t), max(t)) for name, t in times.items()}
     peaks = {name: peak_bytes(fn) for name, fn in cases.items()}
     flops_fwd = 4.0 * N * heads * M * M * args.depth
-    flops = {"kernel_fwd": flops_fwd, "torch_fwd": flops_fwd, "kernel_fwd_bwd": 3.5 * flops_fwd, "torch_fwd_bwd": 3.5 * flops_fwd}
+    flops = {name: 3.5 * flops_fwd if name.endswith("_fwd_bwd") else flops_fwd for name in cases}
     print(f"{M} tokens, batch {N}, {heads} heads x {args.depth}; logits of one call: {N * heads * M * M * 4 / 2**20:.0f} MiB; "
           f"q: {N * M * d * 4 / 2**20:.1f} MiB; device: {torch.cuda.get_device_name(0)}")
     if agree:
@@ -131,8 +139,13 @@ def main():
         print(f"{name:16s} {ms[name]:9.3f} ms   (min {spread[name][0]:.3f}, max {spread[name][1]:.3f}, {args.reps} calls)   "
               f"{rate / 1e12:6.1f} TFLOP/s algorithmic = {rate / FP32_MFMA_PEAK:.2f} of the fp32 MFMA peak   "
               f"peak memory {peaks[name] / 2**20:9.1f} MiB")
-    result = {"tokens": M, "batch": N, "heads": heads, "depth": args.depth, "ms": ms, "peak_bytes": peaks,
+    result = {"tokens": M, "batch": N, "heads": heads, "depth": args.depth, "ms": ms, "min_max_ms": spread, "peak_bytes": peaks,
               "flops_fwd": flops_fwd, "agreement": agree}
+    for name in splits:
+        result[f"fp32_over_{name}_fwd"] = ms["kernel_fwd"] / ms[name + "_fwd"]
+        result[f"fp32_over_{name}_fwd_bwd"] = ms["kernel_fwd_bwd"] / ms[name + "_fwd_bwd"]
+        print(f"fp32 kernels / {name}: forward {result[f'fp32_over_{name}_fwd']:.2f} x, "
+              f"forward + backward {result[f'fp32_over_{name}_fwd_bwd']:.2f} x")
     if not args.skip_baseline:
         result["ratio_fwd"] = ms["torch_fwd"] / ms["kernel_fwd"]
         result["ratio_fwd_bwd"] = ms["torch_fwd_bwd"] / ms["kernel_fwd_bwd"]
