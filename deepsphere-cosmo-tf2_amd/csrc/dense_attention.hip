@@ -127,11 +127,13 @@ __device__ __forceinline__ void da_store_acc(float* rowp, const da_f32x4 (&acc)[
     if (16 * b + 4 * g < D) *reinterpret_cast<float4*>(rowp + 16 * b + 4 * g) = make_float4(acc[b][0] * f, acc[b][1] * f, acc[b][2] * f, acc[b][3] * f);
 }
 
-template <int D>
+// MASKED: the logits take the mask's addend (dense_attention_common.h) and `lse` is the pair buffer (N, M, heads, 2) = (m, log l):
+// with every key of a row masked m = -1e9 and m + log l rounds back to m, so the backward needs the two apart.
+template <int D, bool MASKED = false, typename... MK>
 __global__ __launch_bounds__(256) void dense_attention_forward_kernel(const float* __restrict__ q, const float* __restrict__ k,
                                                                        const float* __restrict__ v, int64_t ld, float* __restrict__ out,
                                                                        float* __restrict__ lse, int64_t M, int heads, int64_t nblk,
-                                                                       float scale) {
+                                                                       float scale, MK... mk) {
   using S = DaShape<D>;
   __shared__ __attribute__((aligned(16))) float sk[DA_TILE * S::STRIDE];
   __shared__ __attribute__((aligned(16))) float sv[DA_TILE * S::STRIDE];
@@ -143,6 +145,8 @@ __global__ __launch_bounds__(256) void dense_attention_forward_kernel(const floa
 #pragma unroll
   for (int b = 0; b < S::CB; ++b) acc[b] = da_f32x4{0.f, 0.f, 0.f, 0.f};
   float m = -__builtin_huge_valf(), l = 0.f;
+  const float* mrow = nullptr;
+  if constexpr (MASKED) mrow = da_mask_row(da_mask_of(mk...), B, M);
   const int64_t ntiles = (M + DA_TILE - 1) / DA_TILE;
   float4 pk[S::STAGE], pv[S::STAGE];
   {
@@ -165,10 +169,16 @@ __global__ __launch_bounds__(256) void dense_attention_forward_kernel(const floa
     float mx = -__builtin_huge_valf();
 #pragma unroll
     for (int sub = 0; sub < 4; ++sub) {
+      float mb[4];
+      if constexpr (MASKED) da_mask_addend4(mb, mrow, j0 + 16 * sub + 4 * g, M);
       s[sub] = da_tile_dot<D>(sk, sub, qf, lane);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        s[sub][r] = j0 + 16 * sub + 4 * g + r < M ? s[sub][r] * scale : -__builtin_huge_valf();
+        if constexpr (MASKED) {
+          s[sub][r] = j0 + 16 * sub + 4 * g + r < M ? da_masked_logit(s[sub][r], scale, mb[r]) : -__builtin_huge_valf();
+        } else {
+          s[sub][r] = j0 + 16 * sub + 4 * g + r < M ? s[sub][r] * scale : -__builtin_huge_valf();
+        }
         mx = fmaxf(mx, s[sub][r]);
       }
     }
@@ -197,16 +207,23 @@ __global__ __launch_bounds__(256) void dense_attention_forward_kernel(const floa
   }
   if (!B.own) return;
   da_store_acc<D>(out + (B.base + B.row) * ((int64_t)heads * D) + B.ch, acc, 1.f / l, g);
-  if (lse != nullptr && g == 0) lse[(B.base + B.row) * heads + B.h] = m + logf(l);
+  if (lse != nullptr && g == 0) {
+    if constexpr (MASKED) {
+      *reinterpret_cast<float2*>(lse + 2 * ((B.base + B.row) * heads + B.h)) = make_float2(m, logf(l));
+    } else {
+      lse[(B.base + B.row) * heads + B.h] = m + logf(l);
+    }
+  }
 }
 
 // pass 1 of the backward: delta and dq of the owned query rows, over the key tiles
-template <int D>
+template <int D, bool MASKED = false, typename... MK>
 __global__ __launch_bounds__(256) void dense_attention_dq_kernel(const float* __restrict__ q, const float* __restrict__ k,
                                                                   const float* __restrict__ v, int64_t ld, const float* __restrict__ out,
                                                                   const float* __restrict__ lse, const float* __restrict__ dout,
                                                                   float* __restrict__ delta, float* __restrict__ dq, int64_t ldg, int64_t M,
-                                                                  int heads, int64_t nblk, float scale) {
+                                                                  int heads, int64_t nblk, float scale,
+                                                                  MK... mk) {
   using S = DaShape<D>;
   __shared__ __attribute__((aligned(16))) float sk[DA_TILE * S::STRIDE];
   __shared__ __attribute__((aligned(16))) float sv[DA_TILE * S::STRIDE];
@@ -215,6 +232,9 @@ __global__ __launch_bounds__(256) void dense_attention_dq_kernel(const float* __
   const int64_t d = (int64_t)heads * D;
   float qf[S::NF], gf[S::NF];
   float dl = 0.f, ls = 0.f;
+  float ll = 0.f;            // MASKED: (ls, ll) = (m, log l) of the owned row
+  const float* mrow = nullptr;
+  if constexpr (MASKED) mrow = da_mask_row(da_mask_of(mk...), B, M);
   if (B.own) {
     float of[S::NF];
     da_load_frag<D>(qf, q + (B.base + B.row) * ld + B.ch, g);
@@ -222,7 +242,12 @@ __global__ __launch_bounds__(256) void dense_attention_dq_kernel(const float* __
     da_load_frag<D>(of, out + (B.base + B.row) * d + B.ch, g);
 #pragma unroll
     for (int e = 0; e < S::NF; ++e) dl = fmaf(gf[e], of[e], dl);
-    ls = lse[(B.base + B.row) * heads + B.h];
+    if constexpr (MASKED) {
+      const float2 st = *reinterpret_cast<const float2*>(lse + 2 * ((B.base + B.row) * heads + B.h));
+      ls = st.x; ll = st.y;
+    } else {
+      ls = lse[(B.base + B.row) * heads + B.h];
+    }
   } else {
     da_zero_frag<D>(qf);
     da_zero_frag<D>(gf);
@@ -251,12 +276,19 @@ __global__ __launch_bounds__(256) void dense_attention_dq_kernel(const float* __
     }
 #pragma unroll
     for (int sub = 0; sub < 4; ++sub) {
+      float mb[4];
+      if constexpr (MASKED) da_mask_addend4(mb, mrow, j0 + 16 * sub + 4 * g, M);
       const da_f32x4 s = da_tile_dot<D>(sk, sub, qf, lane);
       const da_f32x4 dp = da_tile_dot<D>(sv, sub, gf, lane);
       da_f32x4 ds;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const float p = j0 + 16 * sub + 4 * g + r < M ? __expf(fmaf(s[r], scale, -ls)) : 0.f;
+        float p;
+        if constexpr (MASKED) {
+          p = j0 + 16 * sub + 4 * g + r < M ? __expf((da_masked_logit(s[r], scale, mb[r]) - ls) - ll) : 0.f;
+        } else {
+          p = j0 + 16 * sub + 4 * g + r < M ? __expf(fmaf(s[r], scale, -ls)) : 0.f;
+        }
         ds[r] = p * (dp[r] - dl);
       }
       da_tile_acc<D>(acc, sk, sub, ds, lane);
@@ -274,16 +306,18 @@ __global__ __launch_bounds__(256) void dense_attention_dq_kernel(const float* __
 }
 
 // pass 2: dk and dv of the owned key rows, over the query tiles (q and dout rows in LDS, their lse and delta beside them)
-template <int D>
+template <int D, bool MASKED = false, typename... MK>
 __global__ __launch_bounds__(256) void dense_attention_dkv_kernel(const float* __restrict__ q, const float* __restrict__ k,
                                                                    const float* __restrict__ v, int64_t ld, const float* __restrict__ lse,
                                                                    const float* __restrict__ dout, const float* __restrict__ delta,
                                                                    float* __restrict__ dk, float* __restrict__ dv, int64_t ldg, int64_t M,
-                                                                   int heads, int64_t nblk, float scale) {
+                                                                   int heads, int64_t nblk, float scale,
+                                                                   MK... mk) {
   using S = DaShape<D>;
+  constexpr int ST = MASKED ? 2 : 1;  // floats of a row's statistic: lse, or m and, DA_TILE further on, log l
   __shared__ __attribute__((aligned(16))) float sq[DA_TILE * S::STRIDE];
   __shared__ __attribute__((aligned(16))) float sg[DA_TILE * S::STRIDE];
-  __shared__ __attribute__((aligned(16))) float sl[DA_TILE];
+  __shared__ __attribute__((aligned(16))) float sl[ST * DA_TILE];
   __shared__ __attribute__((aligned(16))) float sd[DA_TILE];
   const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4;
   const DaBlock B = da_block(M, heads, D, nblk);
@@ -302,14 +336,28 @@ __global__ __launch_bounds__(256) void dense_attention_dkv_kernel(const float* _
   const int64_t ntiles = (M + DA_TILE - 1) / DA_TILE;
   float4 pq[S::STAGE], pg[S::STAGE];
   float pl = 0.f, pd = 0.f;  // threads 0..63: lse and delta of tile row tid
+  float pl2 = 0.f;           // MASKED: (pl, pl2) = (m, log l)
+  DaKeyMask km;
+  if constexpr (MASKED) km = da_key_mask(da_mask_of(mk...), B, M);
   {
     const int valid = (int)(M < DA_TILE ? M : DA_TILE);
     da_stage_load<D>(pq, q + B.base * ld + B.ch, ld, valid, tid);
     da_stage_load<D>(pg, dout + B.base * d + B.ch, d, valid, tid);
-    if (tid < valid) { pl = lse[(B.base + tid) * heads + B.h]; pd = delta[(B.base + tid) * heads + B.h]; }
+    if (tid < valid) {
+      if constexpr (MASKED) {
+        const float2 st = *reinterpret_cast<const float2*>(lse + 2 * ((B.base + tid) * heads + B.h));
+        pl = st.x; pl2 = st.y;
+      } else {
+        pl = lse[(B.base + tid) * heads + B.h];
+      }
+      pd = delta[(B.base + tid) * heads + B.h];
+    }
     da_stage_store<D>(pq, sq, tid);
     da_stage_store<D>(pg, sg, tid);
-    if (tid < DA_TILE) { sl[tid] = pl; sd[tid] = pd; }
+    if (tid < DA_TILE) {
+      sl[tid] = pl; sd[tid] = pd;
+      if constexpr (MASKED) sl[DA_TILE + tid] = pl2;
+    }
   }
   __syncthreads();
   for (int64_t t = 0; t < ntiles; ++t) {
@@ -319,8 +367,16 @@ __global__ __launch_bounds__(256) void dense_attention_dkv_kernel(const float* _
       const int valid = (int)(left < DA_TILE ? left : DA_TILE);
       da_stage_load<D>(pq, q + (B.base + i0 + DA_TILE) * ld + B.ch, ld, valid, tid);
       da_stage_load<D>(pg, dout + (B.base + i0 + DA_TILE) * d + B.ch, d, valid, tid);
-      pl = pd = 0.f;
-      if (tid < valid) { pl = lse[(B.base + i0 + DA_TILE + tid) * heads + B.h]; pd = delta[(B.base + i0 + DA_TILE + tid) * heads + B.h]; }
+      pl = pd = pl2 = 0.f;
+      if (tid < valid) {
+        if constexpr (MASKED) {
+          const float2 st = *reinterpret_cast<const float2*>(lse + 2 * ((B.base + i0 + DA_TILE + tid) * heads + B.h));
+          pl = st.x; pl2 = st.y;
+        } else {
+          pl = lse[(B.base + i0 + DA_TILE + tid) * heads + B.h];
+        }
+        pd = delta[(B.base + i0 + DA_TILE + tid) * heads + B.h];
+      }
     }
 #pragma unroll
     for (int sub = 0; sub < 4; ++sub) {
@@ -329,10 +385,20 @@ __global__ __launch_bounds__(256) void dense_attention_dkv_kernel(const float* _
       const float4 l4 = *reinterpret_cast<const float4*>(sl + 16 * sub + 4 * g);
       const float4 d4 = *reinterpret_cast<const float4*>(sd + 16 * sub + 4 * g);
       const float lq[4] = {l4.x, l4.y, l4.z, l4.w}, dq4[4] = {d4.x, d4.y, d4.z, d4.w};
+      float mb[4], lq2[4];
+      if constexpr (MASKED) {
+        da_key_mask_addend4(mb, km, i0 + 16 * sub + 4 * g, M);
+        const float4 t = *reinterpret_cast<const float4*>(sl + DA_TILE + 16 * sub + 4 * g);
+        lq2[0] = t.x; lq2[1] = t.y; lq2[2] = t.z; lq2[3] = t.w;
+      }
       da_f32x4 p, ds;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        p[r] = i0 + 16 * sub + 4 * g + r < M ? __expf(fmaf(s[r], scale, -lq[r])) : 0.f;
+        if constexpr (MASKED) {
+          p[r] = i0 + 16 * sub + 4 * g + r < M ? __expf((da_masked_logit(s[r], scale, mb[r]) - lq[r]) - lq2[r]) : 0.f;
+        } else {
+          p[r] = i0 + 16 * sub + 4 * g + r < M ? __expf(fmaf(s[r], scale, -lq[r])) : 0.f;
+        }
         ds[r] = p[r] * (dp[r] - dq4[r]);
       }
       da_tile_acc<D>(av, sg, sub, p, lane);
@@ -342,7 +408,10 @@ __global__ __launch_bounds__(256) void dense_attention_dkv_kernel(const float* _
     if (t + 1 < ntiles) {
       da_stage_store<D>(pq, sq, tid);
       da_stage_store<D>(pg, sg, tid);
-      if (tid < DA_TILE) { sl[tid] = pl; sd[tid] = pd; }
+      if (tid < DA_TILE) {
+        sl[tid] = pl; sd[tid] = pd;
+        if constexpr (MASKED) sl[DA_TILE + tid] = pl2;
+      }
     }
     __syncthreads();
   }
@@ -359,6 +428,42 @@ __global__ __launch_bounds__(256) void dense_attention_dkv_kernel(const float* _
     case 32: CALL(32); break;       \
     default: CALL(64); break;       \
   }
+
+// the masked launches (arguments checked by the entry points in dense_attention_split.hip)
+int dense_attention_forward_masked_fp32(const float* q, const float* k, const float* v, int64_t ld, float* out, float* stat, const DaMask& mk,
+                                        int64_t N, int64_t M, int32_t heads, int32_t depth, hipStream_t stream) {
+  int64_t nblk;
+  unsigned grid;
+  const int rc = dense_grid("dense_attention_forward_masked", N, M, heads, &nblk, &grid);
+  if (rc != DSPH_OK) return rc;
+  const float scale = (float)(1.0 / std::sqrt((double)depth));
+#define DENSE_FWD(DD)                                                                                                                  \
+  hipLaunchKernelGGL((dense_attention_forward_kernel<DD, true, DaMask>), dim3(grid), dim3(256), 0, stream, q, k, v, ld, out, stat, M, (int)heads, \
+                     nblk, scale, mk)
+  DENSE_BY_DEPTH(depth, DENSE_FWD)
+#undef DENSE_FWD
+  DSPH_HIP(hipGetLastError());
+  return DSPH_OK;
+}
+
+int dense_attention_backward_masked_fp32(const float* q, const float* k, const float* v, int64_t ld, const float* out, const float* stat,
+                                         const DaMask& mk, const float* dout, float* delta, float* dq, float* dk, float* dv, int64_t ld_grad,
+                                         int64_t N, int64_t M, int32_t heads, int32_t depth, hipStream_t stream) {
+  int64_t nblk;
+  unsigned grid;
+  const int rc = dense_grid("dense_attention_backward_masked", N, M, heads, &nblk, &grid);
+  if (rc != DSPH_OK) return rc;
+  const float scale = (float)(1.0 / std::sqrt((double)depth));
+#define DENSE_BWD(DD)                                                                                                                     \
+  hipLaunchKernelGGL((dense_attention_dq_kernel<DD, true, DaMask>), dim3(grid), dim3(256), 0, stream, q, k, v, ld, out, stat, dout, delta, dq,    \
+                     ld_grad, M, (int)heads, nblk, scale, mk);                                                                            \
+  hipLaunchKernelGGL((dense_attention_dkv_kernel<DD, true, DaMask>), dim3(grid), dim3(256), 0, stream, q, k, v, ld, stat, dout, delta, dk, dv,    \
+                     ld_grad, M, (int)heads, nblk, scale, mk)
+  DENSE_BY_DEPTH(depth, DENSE_BWD)
+#undef DENSE_BWD
+  DSPH_HIP(hipGetLastError());
+  return DSPH_OK;
+}
 
 }  // namespace dsph
 
@@ -412,7 +517,7 @@ int dsph_dense_attention_backward(const float* q, const float* k, const float* v
   hipStream_t stream = (hipStream_t)hip_stream;
 #define DENSE_BWD(DD)                                                                                                                  \
   hipLaunchKernelGGL(dense_attention_dq_kernel<DD>, dim3(grid), dim3(256), 0, stream, q, k, v, ld, out, lse, dout, delta, dq, ld_grad, M, \
-                     (int)heads, nblk, scale);                                                                                         \
+                     (int)heads, nblk, scale);                                                                             \
   hipLaunchKernelGGL(dense_attention_dkv_kernel<DD>, dim3(grid), dim3(256), 0, stream, q, k, v, ld, lse, dout, delta, dk, dv, ld_grad, M, \
                      (int)heads, nblk, scale)
   DENSE_BY_DEPTH(depth, DENSE_BWD)

@@ -220,11 +220,13 @@ __device__ __forceinline__ void das_store_acc(float* rowp, const das_f32x4 (&acc
     *reinterpret_cast<float4*>(rowp + 16 * b + 4 * g) = make_float4(acc[b][0] * f, acc[b][1] * f, acc[b][2] * f, acc[b][3] * f);
 }
 
-template <int D, int PREC>
+// MASKED, here and below: as in dense_attention.hip -- the mask's addend goes onto the fp32 logit after the product (it is never
+// split) and `lse` is the pair buffer (N, M, heads, 2) = (m, log l).
+template <int D, int PREC, bool MASKED = false, typename... MK>
 __global__ __launch_bounds__(256) void dense_attention_split_forward_kernel(const float* __restrict__ q, const float* __restrict__ k,
                                                                              const float* __restrict__ v, int64_t ld, float* __restrict__ out,
                                                                              float* __restrict__ lse, int64_t M, int heads, int64_t nblk,
-                                                                             float scale) {
+                                                                             float scale, MK... mk) {
   constexpr int NT = das_terms(PREC), TS = das_tile_rows(0, D, NT);
   using S = DasShape<D, TS>;
   __shared__ __attribute__((aligned(16))) __bf16 sk[NT * S::ROWIMG];
@@ -240,6 +242,8 @@ __global__ __launch_bounds__(256) void dense_attention_split_forward_kernel(cons
 #pragma unroll
   for (int b = 0; b < S::CB; ++b) acc[b] = das_f32x4{0.f, 0.f, 0.f, 0.f};
   float m = -__builtin_huge_valf(), l = 0.f;
+  const float* mrow = nullptr;
+  if constexpr (MASKED) mrow = da_mask_row(da_mask_of(mk...), B, M);
   const int64_t ntiles = (M + TS - 1) / TS;
   float4 pk[S::RPT], pv[S::RPT];
   {
@@ -262,10 +266,16 @@ __global__ __launch_bounds__(256) void dense_attention_split_forward_kernel(cons
     float mx = -__builtin_huge_valf();
 #pragma unroll
     for (int sub = 0; sub < S::NSUB; ++sub) {
+      float mb[4];
+      if constexpr (MASKED) da_mask_addend4(mb, mrow, j0 + 16 * sub + 4 * g, M);
       s[sub] = das_tile_dot<D, TS, NT>(sk, sub, qf, lane);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        s[sub][r] = j0 + 16 * sub + 4 * g + r < M ? s[sub][r] * scale : -__builtin_huge_valf();
+        if constexpr (MASKED) {
+          s[sub][r] = j0 + 16 * sub + 4 * g + r < M ? da_masked_logit(s[sub][r], scale, mb[r]) : -__builtin_huge_valf();
+        } else {
+          s[sub][r] = j0 + 16 * sub + 4 * g + r < M ? s[sub][r] * scale : -__builtin_huge_valf();
+        }
         mx = fmaxf(mx, s[sub][r]);
       }
     }
@@ -293,16 +303,23 @@ __global__ __launch_bounds__(256) void dense_attention_split_forward_kernel(cons
   }
   if (!B.own) return;
   das_store_acc<D>(out + (B.base + B.row) * ((int64_t)heads * D) + B.ch, acc, 1.f / l, g);
-  if (lse != nullptr && g == 0) lse[(B.base + B.row) * heads + B.h] = m + logf(l);
+  if (lse != nullptr && g == 0) {
+    if constexpr (MASKED) {
+      *reinterpret_cast<float2*>(lse + 2 * ((B.base + B.row) * heads + B.h)) = make_float2(m, logf(l));
+    } else {
+      lse[(B.base + B.row) * heads + B.h] = m + logf(l);
+    }
+  }
 }
 
 // pass 1 of the backward: delta and dq of the owned query rows, over the key tiles
-template <int D, int PREC>
+template <int D, int PREC, bool MASKED = false, typename... MK>
 __global__ __launch_bounds__(256) void dense_attention_split_dq_kernel(const float* __restrict__ q, const float* __restrict__ k,
                                                                         const float* __restrict__ v, int64_t ld, const float* __restrict__ out,
                                                                         const float* __restrict__ lse, const float* __restrict__ dout,
                                                                         float* __restrict__ delta, float* __restrict__ dq, int64_t ldg, int64_t M,
-                                                                        int heads, int64_t nblk, float scale) {
+                                                                        int heads, int64_t nblk, float scale,
+                                                                        MK... mk) {
   constexpr int NT = das_terms(PREC), TS = das_tile_rows(1, D, NT);
   using S = DasShape<D, TS>;
   __shared__ __attribute__((aligned(16))) __bf16 sk[NT * S::ROWIMG];
@@ -313,6 +330,9 @@ __global__ __launch_bounds__(256) void dense_attention_split_dq_kernel(const flo
   const int64_t d = (int64_t)heads * D;
   DasFrag<NT> qf[S::KS], gf[S::KS];
   float dl = 0.f, ls = 0.f;
+  float ll = 0.f;  // MASKED: (ls, ll) = (m, log l) of the owned row
+  const float* mrow = nullptr;
+  if constexpr (MASKED) mrow = da_mask_row(da_mask_of(mk...), B, M);
   {
     float raw[S::KS][8], graw[S::KS][8];
     das_load_own<D, NT>(qf, raw, B.own ? q + (B.base + B.row) * ld + B.ch : nullptr, g);
@@ -323,7 +343,12 @@ __global__ __launch_bounds__(256) void dense_attention_split_dq_kernel(const flo
       for (int ks = 0; ks < S::KS; ++ks)
 #pragma unroll
         for (int j = 0; j < 8; ++j) dl = fmaf(graw[ks][j], orow[32 * ks + 8 * g + j], dl);
-      ls = lse[(B.base + B.row) * heads + B.h];
+      if constexpr (MASKED) {
+        const float2 st = *reinterpret_cast<const float2*>(lse + 2 * ((B.base + B.row) * heads + B.h));
+        ls = st.x; ll = st.y;
+      } else {
+        ls = lse[(B.base + B.row) * heads + B.h];
+      }
     }
   }
   dl = da_group_sum(dl);  // (the four lane groups of a row hold its D channels once)
@@ -351,11 +376,18 @@ __global__ __launch_bounds__(256) void dense_attention_split_dq_kernel(const flo
     das_f32x4 ds[S::NSUB];
 #pragma unroll
     for (int sub = 0; sub < S::NSUB; ++sub) {
+      float mb[4];
+      if constexpr (MASKED) da_mask_addend4(mb, mrow, j0 + 16 * sub + 4 * g, M);
       const das_f32x4 s = das_tile_dot<D, TS, NT>(sk, sub, qf, lane);
       const das_f32x4 dp = das_tile_dot<D, TS, NT>(sv, sub, gf, lane);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const float p = j0 + 16 * sub + 4 * g + r < M ? __expf(fmaf(s[r], scale, -ls)) : 0.f;
+        float p;
+        if constexpr (MASKED) {
+          p = j0 + 16 * sub + 4 * g + r < M ? __expf((da_masked_logit(s[r], scale, mb[r]) - ls) - ll) : 0.f;
+        } else {
+          p = j0 + 16 * sub + 4 * g + r < M ? __expf(fmaf(s[r], scale, -ls)) : 0.f;
+        }
         ds[sub][r] = p * (dp[r] - dl);
       }
     }
@@ -373,19 +405,22 @@ __global__ __launch_bounds__(256) void dense_attention_split_dq_kernel(const flo
 }
 
 // pass 2: dk and dv of the owned key rows, over the query tiles (q and dout rows in LDS, their lse and delta beside them)
-template <int D, int PREC>
+template <int D, int PREC, bool MASKED = false, typename... MK>
 __global__ __launch_bounds__(256) void dense_attention_split_dkv_kernel(const float* __restrict__ q, const float* __restrict__ k,
                                                                          const float* __restrict__ v, int64_t ld, const float* __restrict__ lse,
                                                                          const float* __restrict__ dout, const float* __restrict__ delta,
                                                                          float* __restrict__ dk, float* __restrict__ dv, int64_t ldg, int64_t M,
-                                                                         int heads, int64_t nblk, float scale) {
+                                                                         int heads, int64_t nblk, float scale,
+                                                                         MK... mk) {
   constexpr int NT = das_terms(PREC), TS = das_tile_rows(2, D, NT);
   using S = DasShape<D, TS>;
+  constexpr int ST = MASKED ? 2 : 1;  // floats of a row's statistic: lse, or m and, TS further on, log l
+  static_assert(das_lds_bytes(2, D, TS, NT) + (ST - 1) * TS * 4 <= 64 * 1024, "the second statistic keeps the tile rows das_tile_rows chose");
   __shared__ __attribute__((aligned(16))) __bf16 sq[NT * S::ROWIMG];
   __shared__ __attribute__((aligned(16))) __bf16 sqt[NT * S::TRIMG];
   __shared__ __attribute__((aligned(16))) __bf16 sg[NT * S::ROWIMG];
   __shared__ __attribute__((aligned(16))) __bf16 sgt[NT * S::TRIMG];
-  __shared__ __attribute__((aligned(16))) float sl[TS];
+  __shared__ __attribute__((aligned(16))) float sl[ST * TS];
   __shared__ __attribute__((aligned(16))) float sd[TS];
   const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4;
   const DaBlock B = da_block(M, heads, D, nblk);
@@ -402,14 +437,28 @@ __global__ __launch_bounds__(256) void dense_attention_split_dkv_kernel(const fl
   const int64_t ntiles = (M + TS - 1) / TS;
   float4 pq[S::RPT], pg[S::RPT];
   float pl = 0.f, pd = 0.f;  // threads 0..TS-1: lse and delta of tile row tid
+  float pl2 = 0.f;           // MASKED: (pl, pl2) = (m, log l)
+  DaKeyMask km;
+  if constexpr (MASKED) km = da_key_mask(da_mask_of(mk...), B, M);
   {
     const int valid = (int)(M < TS ? M : TS);
     das_stage_load<D, TS, S::RPT>(pq, q + B.base * ld + B.ch, ld, valid, tid);
     das_stage_load<D, TS, S::RPT>(pg, dout + B.base * d + B.ch, d, valid, tid);
-    if (tid < valid) { pl = lse[(B.base + tid) * heads + B.h]; pd = delta[(B.base + tid) * heads + B.h]; }
+    if (tid < valid) {
+      if constexpr (MASKED) {
+        const float2 st = *reinterpret_cast<const float2*>(lse + 2 * ((B.base + tid) * heads + B.h));
+        pl = st.x; pl2 = st.y;
+      } else {
+        pl = lse[(B.base + tid) * heads + B.h];
+      }
+      pd = delta[(B.base + tid) * heads + B.h];
+    }
     das_stage_store<D, TS, NT, S::RPT>(pq, sq, sqt, tid);
     das_stage_store<D, TS, NT, S::RPT>(pg, sg, sgt, tid);
-    if (tid < TS) { sl[tid] = pl; sd[tid] = pd; }
+    if (tid < TS) {
+      sl[tid] = pl; sd[tid] = pd;
+      if constexpr (MASKED) sl[TS + tid] = pl2;
+    }
   }
   __syncthreads();
   for (int64_t t = 0; t < ntiles; ++t) {
@@ -419,8 +468,16 @@ __global__ __launch_bounds__(256) void dense_attention_split_dkv_kernel(const fl
       const int valid = (int)(left < TS ? left : TS);
       das_stage_load<D, TS, S::RPT>(pq, q + (B.base + i0 + TS) * ld + B.ch, ld, valid, tid);
       das_stage_load<D, TS, S::RPT>(pg, dout + (B.base + i0 + TS) * d + B.ch, d, valid, tid);
-      pl = pd = 0.f;
-      if (tid < valid) { pl = lse[(B.base + i0 + TS + tid) * heads + B.h]; pd = delta[(B.base + i0 + TS + tid) * heads + B.h]; }
+      pl = pd = pl2 = 0.f;
+      if (tid < valid) {
+        if constexpr (MASKED) {
+          const float2 st = *reinterpret_cast<const float2*>(lse + 2 * ((B.base + i0 + TS + tid) * heads + B.h));
+          pl = st.x; pl2 = st.y;
+        } else {
+          pl = lse[(B.base + i0 + TS + tid) * heads + B.h];
+        }
+        pd = delta[(B.base + i0 + TS + tid) * heads + B.h];
+      }
     }
     das_f32x4 p[S::NSUB], ds[S::NSUB];
 #pragma unroll
@@ -430,9 +487,19 @@ __global__ __launch_bounds__(256) void dense_attention_split_dkv_kernel(const fl
       const float4 l4 = *reinterpret_cast<const float4*>(sl + 16 * sub + 4 * g);
       const float4 d4 = *reinterpret_cast<const float4*>(sd + 16 * sub + 4 * g);
       const float lq[4] = {l4.x, l4.y, l4.z, l4.w}, dq4[4] = {d4.x, d4.y, d4.z, d4.w};
+      float mb[4], lq2[4];
+      if constexpr (MASKED) {
+        da_key_mask_addend4(mb, km, i0 + 16 * sub + 4 * g, M);
+        const float4 t4 = *reinterpret_cast<const float4*>(sl + TS + 16 * sub + 4 * g);
+        lq2[0] = t4.x; lq2[1] = t4.y; lq2[2] = t4.z; lq2[3] = t4.w;
+      }
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        p[sub][r] = i0 + 16 * sub + 4 * g + r < M ? __expf(fmaf(s[r], scale, -lq[r])) : 0.f;
+        if constexpr (MASKED) {
+          p[sub][r] = i0 + 16 * sub + 4 * g + r < M ? __expf((da_masked_logit(s[r], scale, mb[r]) - lq[r]) - lq2[r]) : 0.f;
+        } else {
+          p[sub][r] = i0 + 16 * sub + 4 * g + r < M ? __expf(fmaf(s[r], scale, -lq[r])) : 0.f;
+        }
         ds[sub][r] = p[sub][r] * (dp[r] - dq4[r]);
       }
     }
@@ -442,7 +509,10 @@ __global__ __launch_bounds__(256) void dense_attention_split_dkv_kernel(const fl
     if (t + 1 < ntiles) {
       das_stage_store<D, TS, NT, S::RPT>(pq, sq, sqt, tid);
       das_stage_store<D, TS, NT, S::RPT>(pg, sg, sgt, tid);
-      if (tid < TS) { sl[tid] = pl; sd[tid] = pd; }
+      if (tid < TS) {
+        sl[tid] = pl; sd[tid] = pd;
+        if constexpr (MASKED) sl[TS + tid] = pl2;
+      }
     }
     __syncthreads();
   }
@@ -533,9 +603,80 @@ int dsph_dense_attention_backward_prec(const float* q, const float* k, const flo
   hipStream_t stream = (hipStream_t)hip_stream;
 #define DENSE_BWD(DD, PP)                                                                                                                       \
   hipLaunchKernelGGL((dense_attention_split_dq_kernel<DD, PP>), dim3(grid), dim3(256), 0, stream, q, k, v, ld, out, lse, dout, delta, dq, ld_grad, \
-                     M, (int)heads, nblk, scale);                                                                                               \
+                     M, (int)heads, nblk, scale);                                                                                   \
   hipLaunchKernelGGL((dense_attention_split_dkv_kernel<DD, PP>), dim3(grid), dim3(256), 0, stream, q, k, v, ld, lse, dout, delta, dk, dv, ld_grad, \
                      M, (int)heads, nblk, scale)
+  DENSE_SPLIT_DISPATCH(depth, precision, DENSE_BWD);
+#undef DENSE_BWD
+  DSPH_HIP(hipGetLastError());
+  return DSPH_OK;
+}
+
+int dsph_dense_attention_forward_masked(const float* q, const float* k, const float* v, int64_t ld, float* out, float* stat, const float* mask,
+                                        int64_t mask_stride_batch, int64_t mask_stride_head, int64_t mask_stride_query, int64_t N, int64_t M,
+                                        int32_t heads, int32_t depth, int32_t precision, int device, void* hip_stream) {
+  using namespace dsph;
+  const char* who = "dense_attention_forward_masked";
+  if (!q || !k || !v || !out) { set_error("%s: NULL pointer", who); return DSPH_E_BADARG; }
+  int rc = dense_mask_args_ok(who, mask, mask_stride_batch, mask_stride_head, mask_stride_query);
+  if (rc == DSPH_OK) rc = dense_attention_args_ok(who, ld, N, M, heads, depth);
+  if (rc == DSPH_OK) rc = dense_precision_ok(who, precision, depth);
+  if (rc != DSPH_OK) return rc;
+  if (!aligned16({q, k, v, out}) || (reinterpret_cast<uintptr_t>(stat) & 7) != 0) {
+    set_error("%s: q, k, v and out must be 16-byte aligned, stat 8-byte", who);
+    return DSPH_E_BADARG;
+  }
+  DeviceGuard guard(device);
+  if (N <= 0 || M <= 0) return DSPH_OK;
+  const DaMask mk{mask, mask_stride_batch, mask_stride_head, mask_stride_query};
+  hipStream_t stream = (hipStream_t)hip_stream;
+  if (precision == DSPH_PREC_FP32) return dense_attention_forward_masked_fp32(q, k, v, ld, out, stat, mk, N, M, heads, depth, stream);
+  int64_t nblk;
+  unsigned grid;
+  rc = dense_grid(who, N, M, heads, &nblk, &grid);
+  if (rc != DSPH_OK) return rc;
+  const float scale = (float)(1.0 / std::sqrt((double)depth));
+#define DENSE_FWD(DD, PP)                                                                                                                      \
+  hipLaunchKernelGGL((dense_attention_split_forward_kernel<DD, PP, true, DaMask>), dim3(grid), dim3(256), 0, stream, q, k, v, ld, out, stat, M, (int)heads, \
+                     nblk, scale, mk)
+  DENSE_SPLIT_DISPATCH(depth, precision, DENSE_FWD);
+#undef DENSE_FWD
+  DSPH_HIP(hipGetLastError());
+  return DSPH_OK;
+}
+
+int dsph_dense_attention_backward_masked(const float* q, const float* k, const float* v, int64_t ld, const float* out, const float* stat,
+                                         const float* mask, int64_t mask_stride_batch, int64_t mask_stride_head, int64_t mask_stride_query,
+                                         const float* dout, float* delta, float* dq, float* dk, float* dv, int64_t ld_grad, int64_t N, int64_t M,
+                                         int32_t heads, int32_t depth, int32_t precision, int device, void* hip_stream) {
+  using namespace dsph;
+  const char* who = "dense_attention_backward_masked";
+  if (!q || !k || !v || !out || !stat || !dout || !delta || !dq || !dk || !dv) { set_error("%s: NULL pointer", who); return DSPH_E_BADARG; }
+  int rc = dense_mask_args_ok(who, mask, mask_stride_batch, mask_stride_head, mask_stride_query);
+  if (rc == DSPH_OK) rc = dense_attention_args_ok(who, ld, N, M, heads, depth);
+  if (rc == DSPH_OK) rc = dense_attention_args_ok("dense_attention_backward_masked (gradients)", ld_grad, N, M, heads, depth);
+  if (rc == DSPH_OK) rc = dense_precision_ok(who, precision, depth);
+  if (rc != DSPH_OK) return rc;
+  if (!aligned16({q, k, v, out, dout, dq, dk, dv}) || (reinterpret_cast<uintptr_t>(stat) & 7) != 0) {
+    set_error("%s: q, k, v, out, dout, dq, dk and dv must be 16-byte aligned, stat 8-byte", who);
+    return DSPH_E_BADARG;
+  }
+  DeviceGuard guard(device);
+  if (N <= 0 || M <= 0) return DSPH_OK;
+  const DaMask mk{mask, mask_stride_batch, mask_stride_head, mask_stride_query};
+  hipStream_t stream = (hipStream_t)hip_stream;
+  if (precision == DSPH_PREC_FP32)
+    return dense_attention_backward_masked_fp32(q, k, v, ld, out, stat, mk, dout, delta, dq, dk, dv, ld_grad, N, M, heads, depth, stream);
+  int64_t nblk;
+  unsigned grid;
+  rc = dense_grid(who, N, M, heads, &nblk, &grid);
+  if (rc != DSPH_OK) return rc;
+  const float scale = (float)(1.0 / std::sqrt((double)depth));
+#define DENSE_BWD(DD, PP)                                                                                                                        \
+  hipLaunchKernelGGL((dense_attention_split_dq_kernel<DD, PP, true, DaMask>), dim3(grid), dim3(256), 0, stream, q, k, v, ld, out, stat, dout, delta, dq, \
+                     ld_grad, M, (int)heads, nblk, scale, mk);                                                                                   \
+  hipLaunchKernelGGL((dense_attention_split_dkv_kernel<DD, PP, true, DaMask>), dim3(grid), dim3(256), 0, stream, q, k, v, ld, stat, dout, delta, dk, dv, \
+                     ld_grad, M, (int)heads, nblk, scale, mk)
   DENSE_SPLIT_DISPATCH(depth, precision, DENSE_BWD);
 #undef DENSE_BWD
   DSPH_HIP(hipGetLastError());

@@ -124,6 +124,11 @@ SIGNATURES = {
                                                           _c_i32, ctypes.c_int, _c_vp]),
     "dsph_dense_attention_backward_prec": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, _c_i64, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp,
                                                            _c_i64, _c_i64, _c_i64, _c_i32, _c_i32, _c_i32, ctypes.c_int, _c_vp]),
+    "dsph_dense_attention_forward_masked": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, _c_i64, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i64,
+                                                            _c_i64, _c_i32, _c_i32, _c_i32, ctypes.c_int, _c_vp]),
+    "dsph_dense_attention_backward_masked": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, _c_i64, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_vp,
+                                                             _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i64, _c_i32, _c_i32, _c_i32,
+                                                             ctypes.c_int, _c_vp]),
     "dsph_ell_smooth": (ctypes.c_int, [_c_vp, _c_vp, _c_i64, _c_i32, _c_vp, _c_vp, _c_i64, _c_i32, _c_vp, _c_i32, _c_vp, _c_i32,
                                         ctypes.c_int, _c_vp]),
     "dsph_basis_change": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, _c_i32, _c_i32, _c_i32, _c_i32, ctypes.c_int, _c_vp]),
@@ -610,14 +615,16 @@ def _qkv_layout(q, k, v, num_heads):
     return lds[0], N, M, d
 
 
-def _attention_grad_buffers(q, out, lse, dout, grads, num_heads):
+def _attention_grad_buffers(q, out, lse, dout, grads, num_heads, pair=False):
     """What both attention backwards take besides q, k, v: -> (out, lse, dout) contiguous and of the forward's shapes, the three
-    gradient tensors (allocated when ``grads`` is None), their common row stride and the (N, M, heads) scratch ``delta``."""
+    gradient tensors (allocated when ``grads`` is None), their common row stride and the (N, M, heads) scratch ``delta``.
+    ``pair``: ``lse`` is the masked dense attention's (N, M, heads, 2) statistic."""
     import torch
 
     N, M, d = q.shape
     out, dout = out.contiguous(), dout.contiguous()
-    if tuple(out.shape) != (N, M, d) or tuple(dout.shape) != (N, M, d) or tuple(lse.shape) != (N, M, num_heads):
+    if (tuple(out.shape) != (N, M, d) or tuple(dout.shape) != (N, M, d)
+            or tuple(lse.shape) != ((N, M, num_heads, 2) if pair else (N, M, num_heads))):
         raise ValueError("out / dout / lse do not have the forward's shapes")
     if grads is None:
         grads = tuple(torch.empty((N, M, d), dtype=torch.float32, device=q.device) for _ in range(3))
@@ -662,16 +669,61 @@ def nbr_attention_backward(q, k, v, out, lse, dout, nbr, nbrT, num_heads, grads=
     return grads
 
 
-def dense_attention(q, k, v, num_heads, need_lse=True, precision=PREC_FP32):
+def attention_mask(mask, N, num_heads, M, device=None):
+    """The reference's ``mask`` argument of the dense attention as the kernels' operand: -> (t, (sb, sh, sq)), ``t`` a float32
+    tensor (n', h', q', M) with n' in {1, N}, h' in {1, heads}, q' in {1, M} and the last dimension contiguous (moved to ``device``
+    when given), and the element strides of its batch, head and query dimensions, 0 for a dimension of size 1: the kernels
+    broadcast, nothing of size N heads M M is allocated for a broadcast mask.  Views are kept as views (rows need no alignment).
+    A shape that does not broadcast against (N, heads, M, M) raises ValueError naming both shapes; a last dimension of 1 is
+    expanded to M here.  bool / int masks are converted to float32.  The mask is not differentiable: one that requires grad raises."""
+    import torch
+
+    t = mask if isinstance(mask, torch.Tensor) else torch.as_tensor(np.asarray(mask))
+    if t.requires_grad:
+        raise ValueError("the attention mask is not differentiable (it enters the logits as mask * -1e9): pass mask.detach()")
+    full = (int(N), int(num_heads), int(M), int(M))
+    shape4 = (1,) * (4 - t.dim()) + tuple(t.shape) if t.dim() <= 4 else None
+    if shape4 is None or any(s not in (1, f) for s, f in zip(shape4, full)):
+        raise ValueError(f"mask of shape {tuple(t.shape)} does not broadcast against the logits (N, heads, M, M) = {full}")
+    t = t.to(dtype=torch.float32) if device is None else t.to(device=device, dtype=torch.float32)
+    t = t.reshape(shape4)
+    if shape4[3] != full[3]:
+        t = t.expand(shape4[:3] + (full[3],)).contiguous()
+    elif full[3] > 1 and t.stride(3) != 1:
+        t = t.contiguous()
+    strides = tuple(0 if t.shape[i] == 1 else int(t.stride(i)) for i in range(3))
+    return t, strides
+
+
+def _mask_operand(mask, N, num_heads, M, device):
+    t, strides = attention_mask(mask, N, num_heads, M, device)
+    if t.data_ptr() % 4 != 0:
+        t = t.contiguous()
+    return t, strides
+
+
+def dense_attention(q, k, v, num_heads, need_lse=True, precision=PREC_FP32, mask=None):
     """Attention of every row over ALL rows of its map on (N, M, d) maps (``dsph_dense_attention_forward_prec``; flash style, no
     logit reaches memory): -> (out (N, M, d), lse (N, M, heads) or None).  q, k, v may be channel slices of one wider buffer
     (``rows_layout``).  ``precision``: PREC_FP32 (exact-fp32 MFMA, every depth), PREC_BF16X6 or PREC_BF16X3 (the bf16 split
-    arithmetics, depth 32 and 64; any other depth raises)."""
+    arithmetics, depth 32 and 64; any other depth raises).
+
+    ``mask``: the reference's argument (``attention_mask``), added to the logits as ``mask * -1e9``
+    (``dsph_dense_attention_forward_masked``).  The statistic then comes back as the pair (N, M, heads, 2) = (m, log l), which
+    ``dense_attention_backward`` takes in place of ``lse`` together with the same mask.  ``mask=None`` runs what it always ran."""
     import torch
 
     require_gpu()
     ld, N, M, d = _qkv_layout(q, k, v, num_heads)
     out = torch.empty((N, M, d), dtype=torch.float32, device=q.device)
+    if mask is not None:
+        mk, (sb, sh, sq) = _mask_operand(mask, N, num_heads, M, q.device)
+        stat = torch.empty((N, M, num_heads, 2), dtype=torch.float32, device=q.device) if need_lse else None
+        rc = lib().dsph_dense_attention_forward_masked(_ptr(q), _ptr(k), _ptr(v), ld, _ptr(out), _ptr(stat), _ptr(mk), sb, sh, sq,
+                                                       int(N), int(M), int(num_heads), int(d // num_heads), int(precision),
+                                                       q.device.index, _stream_ptr(q.device))
+        check(rc, "dsph_dense_attention_forward_masked")
+        return out, stat
     lse = torch.empty((N, M, num_heads), dtype=torch.float32, device=q.device) if need_lse else None
     rc = lib().dsph_dense_attention_forward_prec(_ptr(q), _ptr(k), _ptr(v), ld, _ptr(out), _ptr(lse), int(N), int(M),
                                                  int(num_heads), int(d // num_heads), int(precision), q.device.index,
@@ -680,12 +732,22 @@ def dense_attention(q, k, v, num_heads, need_lse=True, precision=PREC_FP32):
     return out, lse
 
 
-def dense_attention_backward(q, k, v, out, lse, dout, num_heads, grads=None, precision=PREC_FP32):
+def dense_attention_backward(q, k, v, out, lse, dout, num_heads, grads=None, precision=PREC_FP32, mask=None):
     """dq, dk, dv of ``dense_attention`` (``dsph_dense_attention_backward_prec``; deterministic, nothing of size M^2 is
     allocated).  ``grads``: three tensors to write into (channel slices of one buffer: the gradient of a fused q/k/v projection
-    comes out as one tensor); allocated when None.  ``precision``: as in ``dense_attention``."""
+    comes out as one tensor); allocated when None.  ``precision``: as in ``dense_attention``.  ``mask``: the forward's, with the
+    forward's pair statistic as ``lse`` (``dsph_dense_attention_backward_masked``)."""
     require_gpu()
     ld, N, M, d = _qkv_layout(q, k, v, num_heads)
+    if mask is not None:
+        mk, (sb, sh, sq) = _mask_operand(mask, N, num_heads, M, q.device)
+        out, stat, dout, grads, gld, delta = _attention_grad_buffers(q, out, lse, dout, grads, num_heads, pair=True)
+        rc = lib().dsph_dense_attention_backward_masked(_ptr(q), _ptr(k), _ptr(v), ld, _ptr(out), _ptr(stat), _ptr(mk), sb, sh, sq,
+                                                        _ptr(dout), _ptr(delta), _ptr(grads[0]), _ptr(grads[1]), _ptr(grads[2]), gld,
+                                                        int(N), int(M), int(num_heads), int(d // num_heads), int(precision),
+                                                        q.device.index, _stream_ptr(q.device))
+        check(rc, "dsph_dense_attention_backward_masked")
+        return grads
     out, lse, dout, grads, gld, delta = _attention_grad_buffers(q, out, lse, dout, grads, num_heads)
     rc = lib().dsph_dense_attention_backward_prec(_ptr(q), _ptr(k), _ptr(v), ld, _ptr(out), _ptr(lse), _ptr(dout),
                                                   _ptr(delta), _ptr(grads[0]), _ptr(grads[1]), _ptr(grads[2]), gld, int(N),

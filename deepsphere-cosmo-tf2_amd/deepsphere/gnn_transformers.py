@@ -129,23 +129,30 @@ def _dense_precision(precision, depth=None):
     return precision
 
 
+def _dense_mask(mask, N, num_heads, M, device):
+    """The mask of a dense-attention call as the kernels read it (``_native.attention_mask``), or None."""
+    return None if mask is None else _native.attention_mask(mask, N, num_heads, M, device)[0]
+
+
 class _DenseAttention(torch.autograd.Function):
-    """out = softmax over ALL rows of (q k^T / sqrt(depth)) v; saves q, k, v, out and the log-sum-exp, gradients from
-    ``dsph_dense_attention_backward``."""
+    """out = softmax over ALL rows of (q k^T / sqrt(depth) + mask * -1e9) v; saves q, k, v, out and the log-sum-exp -- with a mask
+    the mask and the statistic pair (m, log l) -- gradients from ``dsph_dense_attention_backward`` / ``_backward_masked``.  The
+    mask gets no gradient."""
 
     @staticmethod
-    def forward(ctx, q, k, v, num_heads, precision=_native.PREC_FP32):
+    def forward(ctx, q, k, v, num_heads, precision=_native.PREC_FP32, mask=None):
         q, k, v = _kernel_layout(q, k, v)
-        out, lse = _native.dense_attention(q, k, v, num_heads, precision=precision)
-        ctx.save_for_backward(q, k, v, out, lse)
+        mask = _dense_mask(mask, q.shape[0], num_heads, q.shape[1], q.device)
+        out, lse = _native.dense_attention(q, k, v, num_heads, precision=precision, mask=mask)
+        ctx.save_for_backward(q, k, v, out, lse, mask)
         ctx.num_heads, ctx.precision = num_heads, precision
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        q, k, v, out, lse = ctx.saved_tensors
-        dq, dk, dv = _native.dense_attention_backward(q, k, v, out, lse, dout, ctx.num_heads, precision=ctx.precision)
-        return dq, dk, dv, None, None
+        q, k, v, out, lse, mask = ctx.saved_tensors
+        dq, dk, dv = _native.dense_attention_backward(q, k, v, out, lse, dout, ctx.num_heads, precision=ctx.precision, mask=mask)
+        return dq, dk, dv, None, None, None
 
 
 class _DenseAttentionPacked(torch.autograd.Function):
@@ -153,30 +160,31 @@ class _DenseAttentionPacked(torch.autograd.Function):
     slices read in place, dq, dk, dv written into the slices of ONE gradient tensor."""
 
     @staticmethod
-    def forward(ctx, qkv, num_heads, precision=_native.PREC_FP32):
+    def forward(ctx, qkv, num_heads, precision=_native.PREC_FP32, mask=None):
         qkv = qkv.contiguous()
         d = qkv.shape[2] // 3
         q, k, v = qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:]
         if d % 4 != 0:  # (slices that are not 16-byte aligned: copies; the kernels then name their limit)
             q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
-        out, lse = _native.dense_attention(q, k, v, num_heads, precision=precision)
-        ctx.save_for_backward(qkv, out, lse)
+        mask = _dense_mask(mask, qkv.shape[0], num_heads, qkv.shape[1], qkv.device)
+        out, lse = _native.dense_attention(q, k, v, num_heads, precision=precision, mask=mask)
+        ctx.save_for_backward(qkv, out, lse, mask)
         ctx.num_heads, ctx.precision = num_heads, precision
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        qkv, out, lse = ctx.saved_tensors
+        qkv, out, lse, mask = ctx.saved_tensors
         d = qkv.shape[2] // 3
         dqkv = torch.empty_like(qkv)
         _native.dense_attention_backward(qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:], out, lse, dout, ctx.num_heads,
-                                         grads=(dqkv[..., :d], dqkv[..., d:2 * d], dqkv[..., 2 * d:]), precision=ctx.precision)
-        return dqkv, None, None
+                                         grads=(dqkv[..., :d], dqkv[..., d:2 * d], dqkv[..., 2 * d:]), precision=ctx.precision,
+                                         mask=mask)
+        return dqkv, None, None, None
 
 
-def scaled_dot_product_attention(q, k, v, num_heads, precision="fp32"):
-    """Attention of every row over all rows of its map (reference ``gnn_transformers.py:14-51`` with ``mask=None``),
-    differentiable.
+def scaled_dot_product_attention(q, k, v, num_heads, precision="fp32", mask=None):
+    """Attention of every row over all rows of its map (reference ``gnn_transformers.py:14-51``), differentiable in q, k, v.
 
     :param q, k, v: float32 HIP tensors (N, M, d), channels last; head h is channels [h d / num_heads, (h + 1) d / num_heads)
         -- the reference's ``split_heads`` without its transposes.  Strided views are read in place when their rows share one
@@ -185,13 +193,25 @@ def scaled_dot_product_attention(q, k, v, num_heads, precision="fp32"):
     :param precision: not a reference argument -- the arithmetic of the products: "fp32" (exact-fp32 MFMA), "bf16x6" (bf16 MFMA
         on a three-term split of both operands, fp32-equivalent) or "bf16x3" (two terms, operands to 16 bits); the split ones
         run d / num_heads 32 and 64 only and raise elsewhere
+    :param mask: the reference's argument: a float tensor that broadcasts against the (N, heads, M, M) logits and is added to them
+        as ``mask * -1e9`` before the softmax, inside the kernel, in all three arithmetics on the fp32 logit -- 1 "do not attend",
+        0 "attend", a fraction a soft bias (an add, not a select).  Any broadcast form: a key mask (M,), per map (N, 1, 1, M), per
+        head (1, heads, 1, M), a pair mask (M, M), a full one; the kernels broadcast by stride, nothing of size N heads M M is
+        allocated for a broadcast mask, and views are read in place.  bool / int masks are converted to float32.  Not
+        differentiable: a mask that requires grad raises, as does a shape that does not broadcast.  A row whose keys are all
+        masked gives the mean of v, as in the reference (-1e9 absorbs any logit below 32 in fp32).  None (default): the unmasked
+        kernels, unchanged.
     :return: (N, M, d)
 
     The reference also returns the attention weights, an (N, heads, M, M) tensor that nothing in it reads; they are never formed
-    here (that is the point of the kernel), and its ``mask`` argument, which ``Graph_ViT`` never passes, is not rebuilt."""
+    here (that is the point of the kernel)."""
+    if mask is not None and isinstance(mask, torch.Tensor) and mask.requires_grad:
+        raise ValueError("the attention mask is not differentiable (it enters the logits as mask * -1e9): pass mask.detach()")
     _require_hip(q, k, v)
     code = _DENSE_PRECISIONS[_dense_precision(precision)]
-    return _DenseAttention.apply(q, k, v, int(num_heads), code)
+    if mask is None:
+        return _DenseAttention.apply(q, k, v, int(num_heads), code)
+    return _DenseAttention.apply(q, k, v, int(num_heads), code, _dense_mask(mask, q.shape[0], int(num_heads), q.shape[1], q.device))
 
 
 def scaled_dot_product_sparse_attention(q, k, v, nbr, nbrT, num_heads):
@@ -265,7 +285,7 @@ class MultiHeadAttention(torch.nn.Module):
             must be set.
         :param dense: not a reference argument -- attention over ALL rows on the dense kernel (what the reference does when it has
             no ``sparse_A_indices``; ``Graph_ViT`` builds its blocks this way).  No tables are needed or read.  The reference's
-            ``mask`` argument of that path is not rebuilt (``Graph_ViT`` never passes one).
+            ``mask`` argument of that path comes with the call (``forward``).
         :param precision: not a reference argument -- the arithmetic of the dense attention's products, "fp32" (default),
             "bf16x6" or "bf16x3" (``scaled_dot_product_attention``).  A split one needs ``dense=True`` and 32 or 64 channels per
             head; the attention over graph neighbours is a memory-bound gather and has no split.
@@ -308,17 +328,29 @@ class MultiHeadAttention(torch.nn.Module):
     def nbrT(self):
         return getattr(self, "nbrT_", self.nbr)
 
-    def forward(self, inputs, tables=None):
+    def forward(self, inputs, tables=None, mask=None):
+        """``mask``: the reference's ``call(inputs, mask=None)`` argument, for the dense path (``dense=True``): see
+        ``scaled_dot_product_attention``.  Deviation from the reference: on the path over graph neighbours the reference accepts a
+        mask and silently ignores it; here that raises ValueError -- a mask that is dropped is a data bug, and there the
+        neighbour table is the mask."""
         nbr, nbrT = (None, None) if self.dense_attention else tables if tables is not None else (self.nbr, self.nbrT)
         if nbr is None and not self.dense_attention:
             raise NotImplementedError("MultiHeadAttention without neighbour tables is dense attention over all pixels (the "
                                       "reference's Graph_ViT path): construct the block with dense=True to run it")
+        if mask is not None and not self.dense_attention:
+            raise ValueError("mask: the attention over graph neighbours takes no mask (the neighbour table is the mask; the "
+                             "reference ignores the argument there): construct the block with dense=True")
+        if mask is not None and isinstance(mask, torch.Tensor) and mask.requires_grad:
+            raise ValueError("the attention mask is not differentiable (it enters the logits as mask * -1e9): pass mask.detach()")
         _require_hip(inputs)
         # the norms run on the layer-norm kernels (csrc/layer_norm.hip), the add between them inside the second one's launch
         x = _layer_norm(self.layer_norm1, inputs) if self.use_norm else inputs
         qkv = self.wqkv(x)  # (N, M, 3 d): q | k | v
         if self.dense_attention:
-            att = _DenseAttentionPacked.apply(qkv, self.num_heads, _DENSE_PRECISIONS[self.precision])
+            if mask is None:
+                att = _DenseAttentionPacked.apply(qkv, self.num_heads, _DENSE_PRECISIONS[self.precision])
+            else:
+                att = _DenseAttentionPacked.apply(qkv, self.num_heads, _DENSE_PRECISIONS[self.precision], mask)
         else:
             att = _SparseAttentionPacked.apply(qkv, nbr, nbrT, self.num_heads)
         if self.use_norm:
@@ -421,10 +453,17 @@ class Graph_ViT(torch.nn.Module):
     Parameter names follow the reference's attributes: ``embed.weight`` (d, Fin, 4^p) and ``embed.bias`` -- a lazily built
     ``torch.nn.Conv1d``, Glorot-uniform / zero like Keras, evaluated as a single ``addmm`` on the free reshape ``HealpyPseudoConv`` makes --
     ``pos_encoder.pos_embedding`` (1, M / 4^p, d) and ``mha_layers.{i}.wqkv / dense / layer_norm1 / layer_norm2`` as in
-    ``Graph_Transformer``.  Runs on a HIP device only."""
+    ``Graph_Transformer``.  Runs on a HIP device only.
+
+    ``mask``: the reference's blocks take ``call(inputs, mask=None)`` but its ``Graph_ViT`` never passes one; here
+    ``forward(inputs, mask=None)`` hands the mask (over the SUPER-pixels: it broadcasts against (N, heads, M / 4^p, M / 4^p), see
+    ``scaled_dot_product_attention``) to every block.  The constructor argument ``mask`` is not a reference argument: it is kept
+    as a non-persistent buffer (it follows ``.to(device)``, stays out of the ``state_dict``) and used whenever the call passes
+    none, so that a masked layer can sit inside ``HealpyGCNN``, whose ``forward`` hands its layers the maps alone.  For a padded
+    survey footprint ``healpix.superpixel_padding_mask`` builds the key mask."""
 
     def __init__(self, p, key_dim, num_heads, positional_encoding=True, n_layers=1, activation="relu", layer_norm=True,
-                 precision="fp32"):
+                 precision="fp32", mask=None):
         super().__init__()
         if not p >= 1:
             raise IOError("The super pixel size factor p has to be at least 1!")
@@ -440,6 +479,14 @@ class Graph_ViT(torch.nn.Module):
         self.activation = activation
         self.layer_norm = layer_norm
         self.precision = _dense_precision(precision, int(key_dim))  # (of the blocks' attention; see MultiHeadAttention)
+        if mask is not None:
+            mask = mask if isinstance(mask, torch.Tensor) else torch.as_tensor(np.asarray(mask))
+            if mask.requires_grad:
+                raise ValueError("the attention mask is not differentiable (it enters the logits as mask * -1e9): pass mask.detach()")
+            if mask.dim() < 1 or mask.dim() > 4:
+                raise ValueError(f"mask of shape {tuple(mask.shape)} does not broadcast against the logits (N, heads, M, M)")
+            mask = mask.detach().to(torch.float32)
+        self.register_buffer("mask", mask, persistent=False)
         self.embed = None
         if self.positional_encoding:
             self.pos_encoder = AddPositionEmbs()
@@ -458,7 +505,7 @@ class Graph_ViT(torch.nn.Module):
         if self.positional_encoding and self.pos_encoder.pos_embedding is None:
             self.pos_encoder.build((1, n_nodes // g, self.embedding_size), device)
 
-    def forward(self, inputs):
+    def forward(self, inputs, mask=None):
         x = inputs if isinstance(inputs, torch.Tensor) else torch.as_tensor(np.asarray(inputs), dtype=torch.float32)
         g = self.embed_filter_size
         if x.dim() == 3 and x.shape[1] % g != 0:
@@ -476,8 +523,13 @@ class Graph_ViT(torch.nn.Module):
         x = torch.addmm(self.embed.bias, x.reshape(N * (M // g), g * Fin), w2).reshape(N, M // g, self.embedding_size)
         if self.positional_encoding:
             x = self.pos_encoder(x)
+        mask = self.mask if mask is None else mask  # (the call's mask overrides the constructor's)
+        if mask is not None:  # checked and laid out once: the same operand goes to every block
+            if self.mask is not None and mask is self.mask and mask.device != x.device:
+                self.mask = mask = mask.to(x.device)
+            mask = _dense_mask(mask, x.shape[0], self.num_heads, x.shape[1], x.device)
         for mha in self.mha_layers:
-            x = mha(x)
+            x = mha(x, mask=mask)
         return x
 
     call = forward

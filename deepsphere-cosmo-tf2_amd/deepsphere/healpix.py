@@ -30,6 +30,7 @@ __all__ = [
     "grid_laplacian_ell_torch",
     "cap_indices",
     "extend_indices",
+    "superpixel_padding_mask",
 ]
 
 # base-pixel ("face") ring/phi offsets of the HEALPix projection
@@ -336,6 +337,33 @@ def extend_indices(indices, nside_in, nside_out, nest=True):
     per = ratio * ratio
     parents = np.unique(indices // per)
     return (parents[:, None] * per + np.arange(per, dtype=np.int64)[None, :]).reshape(-1)
+
+
+def superpixel_padding_mask(indices, footprint, p):
+    """The key mask of ``Healpy_ViT(p, ..., mask=...)`` for a padded survey footprint: 1.0 for every super-pixel that holds
+    nothing but padding.
+
+    :param indices: the sorted NEST ids the network runs on -- closed under ``p`` coarsenings (every touched parent ``id >> 2 p``
+        has all its 4^p children in the set, what ``extend_indices`` returns); anything else raises ValueError
+    :param footprint: the NEST ids (same nside) that hold data
+    :param p: the super-pixel size factor of the ViT layer: a super-pixel is the 4^p children of a pixel p levels coarser
+    :return: float32 (len(indices) / 4^p,), in the order of the coarsened index set (ascending parent id, the order of the
+        layer's tokens): 1.0 where the super-pixel contains no footprint pixel ("do not attend"), 0.0 elsewhere -- one data pixel
+        keeps a super-pixel attended
+    """
+    indices = np.asarray(indices, dtype=np.int64).reshape(-1)
+    per = 4 ** int(p)
+    if int(p) < 1:
+        raise ValueError("p has to be at least 1")
+    if indices.size % per != 0 or (indices.size > 1 and not np.all(np.diff(indices) > 0)):
+        raise ValueError(f"indices must be sorted NEST ids closed under p = {p} coarsenings ({indices.size} ids, patches of {per})")
+    blocks = indices.reshape(-1, per)
+    parents = blocks[:, 0] // per
+    if not np.array_equal(blocks, parents[:, None] * per + np.arange(per, dtype=np.int64)[None, :]):
+        raise ValueError(f"indices are not closed under p = {p} coarsenings: a parent pixel lacks some of its {per} children "
+                         "(healpix.extend_indices pads a footprint to such a set)")
+    touched = np.unique(np.asarray(footprint, dtype=np.int64).reshape(-1) // per)
+    return (~np.isin(parents, touched)).astype(np.float32)
 
 
 # ----------------------------------------------------------------------------------------------

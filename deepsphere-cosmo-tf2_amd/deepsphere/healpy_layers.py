@@ -403,7 +403,7 @@ class Healpy_ViT(Graph_ViT):
     a deferred spec -- it needs no graph.  The model builder counts it as a reduction by 2^p in nside, like ``HealpyPool``."""
 
     def __init__(self, p, key_dim, num_heads, positional_encoding=True, n_layers=1, activation="relu", layer_norm=True,
-                 precision="fp32"):
+                 precision="fp32", mask=None):
         """
         :param p: the super-pixels are the 4^p NEST children of a pixel at nside / 2^p; p >= 1
         :param key_dim: channels of key, query and value per head; the embedding has ``key_dim * num_heads`` channels
@@ -414,9 +414,13 @@ class Healpy_ViT(Graph_ViT):
         :param layer_norm: layer norms in the blocks
         :param precision: arithmetic of the attention's products: "fp32" (default), "bf16x6" or "bf16x3" -- the bf16 split
             kernels, ``key_dim`` 32 or 64 only (``gnn_transformers.MultiHeadAttention``)
+        :param mask: not a reference argument -- the attention mask over the super-pixels used when the call passes none
+            (``Graph_ViT``): 1 "do not attend", added to the logits as ``mask * -1e9``; for a footprint padded with
+            ``extend_indices``, ``healpix.superpixel_padding_mask(indices, footprint, p)``.  ``forward(inputs, mask=...)``
+            overrides it.
         """
         super().__init__(p=p, key_dim=key_dim, num_heads=num_heads, positional_encoding=positional_encoding, n_layers=n_layers,
-                         activation=activation, layer_norm=layer_norm, precision=precision)
+                         activation=activation, layer_norm=layer_norm, precision=precision, mask=mask)
 
 
 class _SmoothFunction(torch.autograd.Function):

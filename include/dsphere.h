@@ -476,6 +476,35 @@ int dsph_dense_attention_backward_prec(const float* q, const float* k, const flo
                                        const float* dout, float* delta, float* dq, float* dk, float* dv, int64_t ld_grad, int64_t N,
                                        int64_t M, int32_t heads, int32_t depth, int32_t precision, int device, void* hip_stream);
 
+/* The same two calls with the reference's `mask` argument (gnn_transformers.py:14-51: `logits += mask * -1e9` before the softmax):
+ *   x_ij = s_ij + mask_ij * (-1e9),   s_ij = q_i . k_j / sqrt(depth) in fp32 after the scale,
+ * the product mask * -1e9f rounded to fp32, then added in fp32 -- in all three arithmetics on the fp32 logit, after the product;
+ * the mask is never split.  It is an ADD, not a select: 1 is "do not attend", 0 "attend", a fraction a soft bias (2.5e-9 lowers a
+ * logit by 2.5).  A row whose keys are all masked behaves as in the reference: fp32 has an ulp of 64 at 1e9, so -1e9 + s is exactly
+ * -1e9 for |s| < 32, the row's softmax is uniform and its output the mean of v; nothing is NaN.
+ *   mask     device fp32; element (n, h, i, j) -- map, head, query row, key -- is
+ *            mask[n * mask_stride_batch + h * mask_stride_head + i * mask_stride_query + j].  The key stride is 1; each of the
+ *            three strides may be 0 (broadcast), none negative.  So one operand is a shared key mask (M,) [0, 0, 0], a per-map
+ *            key mask (N, 1, 1, M) [M, 0, 0], a per-head one [0, M, 0], a shared pair mask (M, M) [0, 0, M] or a full
+ *            (N, heads, M, M) one.  Rows need no alignment (16-byte loads where the address allows, single loads elsewhere).
+ *            Never read at a key index >= M nor for a query row >= M: the last row may end where the allocation ends.
+ *   stat     device (N, M, heads, 2), 8-byte aligned (forward: or NULL): the row statistic as the PAIR (m, log l), m = max_j x_ij,
+ *            l = sum_j exp(x_ij - m).  Not their sum: on a fully masked row m = -1e9 and m + log l rounds back to m, from which
+ *            the backward would recompute p = 1 instead of 1 / M.  The backward takes p = exp((x - m) - log l).
+ * Everything else -- layouts, shapes, precisions (a split at a depth other than 32, 64: DSPH_E_UNSUPPORTED), tails (keys past M
+ * stay at -inf), determinism (two backward launches, no atomics, one writer per element), messages naming the limit -- is as in
+ * the _prec calls, whose arguments these take besides.  A NULL mask or a negative stride: DSPH_E_BADARG.  The unmasked calls
+ * above run the code they ran before; a mask of zeros gives their `out` bit for bit. */
+int dsph_dense_attention_forward_masked(const float* q, const float* k, const float* v, int64_t ld, float* out, float* stat,
+                                        const float* mask, int64_t mask_stride_batch, int64_t mask_stride_head,
+                                        int64_t mask_stride_query, int64_t N, int64_t M, int32_t heads, int32_t depth,
+                                        int32_t precision, int device, void* hip_stream);
+int dsph_dense_attention_backward_masked(const float* q, const float* k, const float* v, int64_t ld, const float* out,
+                                         const float* stat, const float* mask, int64_t mask_stride_batch, int64_t mask_stride_head,
+                                         int64_t mask_stride_query, const float* dout, float* delta, float* dq, float* dk, float* dv,
+                                         int64_t ld_grad, int64_t N, int64_t M, int32_t heads, int32_t depth, int32_t precision,
+                                         int device, void* hip_stream);
+
 /* One pass of Gaussian smoothing: a wide-row ELL matrix over a map of few channels (plan-free; csrc/ell_smooth.hip).
  * Replaces: one utils.split_sparse_dense_matmul per channel and repetition of healpy_layers.HealpySmoothing.call (reference
  * healpy_layers.py:725-764) with the transposes, the unstack / stack and the mask multiply around them.

@@ -2,6 +2,7 @@
 """Time the dense-attention kernels against the same attention written the reference's way in torch, on one GPU.
 
     python tools/bench_dense_attention.py [--tokens 3072] [--batch 8] [--heads 4] [--depth 32] [--reps 30] [--warmup 5]
+                                          [--mask none|key|pair]
 
 (a) the kernel forward, (b) kernel forward + backward, (c) the reference formulation on the same device: the (N, heads, M, M)
 logits materialised by a matmul, softmax, a second matmul -- forward and forward + backward through autograd.  Both sides run in
@@ -14,6 +15,11 @@ over one call of each side, above what q, k, v and the upstream gradient occupy.
 (``precision`` PREC_BF16X6, PREC_BF16X3; depth 32 and 64) are further cases of the same alternating loop, ``bf16x6_*`` and
 ``bf16x3_*``, with their own agreement figures and their time against the fp32 kernels' (``kernel_*``, the baseline).  Prints
 the figures and one JSON line.  Needs a GPU: there is no CPU fallback and no figure without one.
+
+``--mask key`` (a per-map key mask (N, 1, 1, M)) or ``--mask pair`` (a shared pair mask (M, M)), random 0 / 1 with 30 % ones:
+every kernel case above then runs the masked entry points, the materialised side adds ``mask * -1e9`` to its logits the
+reference's way, and the unmasked kernels join the same alternating loop as ``nomask_*`` (fp32) and ``nomask_bf16x?_*`` -- the
+price of the mask is the ratio against them.  ``--mask none`` (default) is the tool as it was.
 """
 
 import argparse
@@ -36,12 +42,15 @@ from deepsphere import _native  # noqa: E402
 FP32_MFMA_PEAK = 64 * 4 * 256 * 2.4e9  # FLOP / s
 
 
-def materialised_attention(q, k, v, heads):
-    """The reference's algorithm on (N, M, d) tensors: split_heads' transposes, matmul, scale, softmax, matmul, transpose back."""
+def materialised_attention(q, k, v, heads, mask=None):
+    """The reference's algorithm on (N, M, d) tensors: split_heads' transposes, matmul, scale, [+ mask * -1e9,] softmax, matmul,
+    transpose back."""
     N, M, d = q.shape
     D = d // heads
     q4, k4, v4 = (t.reshape(N, M, heads, D).permute(0, 2, 1, 3) for t in (q, k, v))
     logits = torch.matmul(q4, k4.transpose(-1, -2)) / float(np.sqrt(D))
+    if mask is not None:
+        logits = logits + mask * -1e9
     weights = torch.softmax(logits, dim=-1)
     return torch.matmul(weights, v4).permute(0, 2, 1, 3).reshape(N, M, d)
 
@@ -76,6 +85,8 @@ def main():
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--skip-baseline", action="store_true", help="time the kernels only (token counts whose logits do not fit)")
+    ap.add_argument("--mask", choices=("none", "key", "pair"), default="none",
+                    help="run the masked entry points: a per-map key mask (N, 1, 1, M) or a shared pair mask (M, M)")
     args = ap.parse_args()
     _native.require_gpu()
     dev = torch.device("cuda", 0)
@@ -84,35 +95,45 @@ def main():
     qkv = torch.randn((N, M, 3 * d), generator=gen, device=dev)  # the layout the layer hands the kernel: three strided views
     g = torch.randn((N, M, d), generator=gen, device=dev)
     q, k, v = qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:]
+    mask, mkw = None, {}
+    if args.mask != "none":
+        shape = (N, 1, 1, M) if args.mask == "key" else (M, M)
+        mask = (torch.rand(shape, generator=gen, device=dev) < 0.3).to(torch.float32)
+        mask[..., 0] = 0.0  # (every row keeps a key)
+        mkw = {"mask": mask}
 
-    def kernel_fwd(precision=_native.PREC_FP32):
-        return _native.dense_attention(q, k, v, heads, precision=precision)
+    def kernel_fwd(precision=_native.PREC_FP32, **kw):
+        return _native.dense_attention(q, k, v, heads, precision=precision, **kw)
 
-    def kernel_fwd_bwd(precision=_native.PREC_FP32):
-        out, lse = _native.dense_attention(q, k, v, heads, precision=precision)
-        return _native.dense_attention_backward(q, k, v, out, lse, g, heads, precision=precision)
+    def kernel_fwd_bwd(precision=_native.PREC_FP32, **kw):
+        out, lse = _native.dense_attention(q, k, v, heads, precision=precision, **kw)
+        return _native.dense_attention_backward(q, k, v, out, lse, g, heads, precision=precision, **kw)
 
     def torch_fwd():
         with torch.no_grad():
-            return materialised_attention(q, k, v, heads)
+            return materialised_attention(q, k, v, heads, mask)
 
     def torch_fwd_bwd():
         t = [a.detach().requires_grad_(True) for a in (q, k, v)]
-        materialised_attention(t[0], t[1], t[2], heads).backward(g)
+        materialised_attention(t[0], t[1], t[2], heads, mask).backward(g)
         return [a.grad for a in t]
 
-    cases = {"kernel_fwd": kernel_fwd, "kernel_fwd_bwd": kernel_fwd_bwd}
+    cases = {"kernel_fwd": functools.partial(kernel_fwd, **mkw), "kernel_fwd_bwd": functools.partial(kernel_fwd_bwd, **mkw)}
     splits = {"bf16x6": _native.PREC_BF16X6, "bf16x3": _native.PREC_BF16X3} if args.depth in (32, 64) else {}
     for name, code in splits.items():
-        cases[name + "_fwd"] = functools.partial(kernel_fwd, code)
-        cases[name + "_fwd_bwd"] = functools.partial(kernel_fwd_bwd, code)
+        cases[name + "_fwd"] = functools.partial(kernel_fwd, code, **mkw)
+        cases[name + "_fwd_bwd"] = functools.partial(kernel_fwd_bwd, code, **mkw)
+    if mask is not None:  # the unmasked kernels in the same loop: what the mask costs
+        for prefix, code in [("nomask", _native.PREC_FP32)] + [("nomask_" + n, c) for n, c in splits.items()]:
+            cases[prefix + "_fwd"] = functools.partial(kernel_fwd, code)
+            cases[prefix + "_fwd_bwd"] = functools.partial(kernel_fwd_bwd, code)
     agree = {}
     if not args.skip_baseline:
         cases.update({"torch_fwd": torch_fwd, "torch_fwd_bwd": torch_fwd_bwd})
         # same numbers first (faster and different is not faster)
         out_t, gt = torch_fwd(), torch_fwd_bwd()
         for prefix, code in [("", _native.PREC_FP32)] + [(n + "_", c) for n, c in splits.items()]:
-            out_k, gk = kernel_fwd(code)[0], kernel_fwd_bwd(code)
+            out_k, gk = kernel_fwd(code, **mkw)[0], kernel_fwd_bwd(code, **mkw)
             agree[prefix + "out"] = float((out_k - out_t).abs().max() / out_t.abs().max())
             for name, a, b in zip(("dq", "dk", "dv"), gk, gt):
                 agree[prefix + name] = float((a - b).abs().max() / b.abs().max())
@@ -141,6 +162,13 @@ def main():
               f"peak memory {peaks[name] / 2**20:9.1f} MiB")
     result = {"tokens": M, "batch": N, "heads": heads, "depth": args.depth, "ms": ms, "min_max_ms": spread, "peak_bytes": peaks,
               "flops_fwd": flops_fwd, "agreement": agree}
+    if mask is not None:
+        result["mask"] = args.mask
+        for prefix, base in [("kernel", "nomask")] + [(n, "nomask_" + n) for n in splits]:
+            for tail in ("_fwd", "_fwd_bwd"):
+                result[f"masked_over_unmasked_{prefix}{tail}"] = ms[prefix + tail] / ms[base + tail]
+            print(f"{args.mask} mask / no mask, {prefix}: forward {result[f'masked_over_unmasked_{prefix}_fwd']:.2f} x, "
+                  f"forward + backward {result[f'masked_over_unmasked_{prefix}_fwd_bwd']:.2f} x")
     for name in splits:
         result[f"fp32_over_{name}_fwd"] = ms["kernel_fwd"] / ms[name + "_fwd"]
         result[f"fp32_over_{name}_fwd_bwd"] = ms["kernel_fwd_bwd"] / ms[name + "_fwd_bwd"]
