@@ -327,7 +327,9 @@ int dsph_cheb_step(const dsph_plan* plan, const float* in, const float* prev, fl
 /* The dense contraction alone on K planes of shape (N, plane_rows, Fin), plane k at
  * planes[k] (device pointers in a HOST array of K entries):
  *   y[n,m,o] = act( sum_k sum_f planes[k][n,m,f] * w[f*K + k, o] + bias[o] ),  m < rows.
- * Replaces tf.stack/reshape/transpose/matmul (gnn_layers.py:144-150). */
+ * Replaces tf.stack/reshape/transpose/matmul (gnn_layers.py:144-150).
+ * Where the plain contraction kernel runs (the batch is a grid dimension there) N is at most 65535: DSPH_E_UNSUPPORTED beyond,
+ * reported after the device has been selected. */
 int dsph_cheb_contract(const float* const* planes, int64_t plane_rows, const float* w,
                        const float* bias, float* y, int64_t N, int64_t rows, int32_t Fin,
                        int32_t Fout, int32_t K, int32_t act, int32_t precision, int device,
@@ -398,7 +400,9 @@ int dsph_residual_epilogue(float* y, const float* skip, int64_t n, float alpha, 
  *   x  device (N, rows_out * group, F) fp32      y  device (N, rows_out, F) fp32      group = 4^p
  *   y[n, m, f] = max | mean over i < group of x[n, group * m + i, f]
  * The backward (the reference gets it from TensorFlow's autodiff): dx[n, group * m + i, f] = dy[n, m, f] / group for the mean;
- * for the maximum dy[n, m, f] at the first child that holds it and 0 at the others (x: the forward input; may be NULL for the mean). */
+ * for the maximum dy[n, m, f] at the first child that holds it and 0 at the others (x: the forward input; may be NULL for the mean).
+ * group at most 2^20 (DSPH_E_UNSUPPORTED beyond, before any HIP call); every offset is 64-bit, the grid is capped at 2^20
+ * workgroups and walked grid-stride. */
 #define DSPH_POOL_MAX 0
 #define DSPH_POOL_AVG 1
 int dsph_healpix_pool(const float* x, float* y, int64_t N, int64_t rows_out, int32_t F, int32_t group, int32_t type, int device,
@@ -418,7 +422,8 @@ int dsph_healpix_pool_backward(const float* x, const float* dy, float* dx, int64
  * The softmax is the stable form (running maximum); the reference exponentiates the raw logits, which is the same number until
  * it overflows (logits above 88).  A row without neighbours gives out = 0 and lse = 0 (the reference: 0 / 0).
  * Shapes: depth one of 4, 8, 16, 32, 64; heads >= 1 with heads * depth <= 256; width >= 1; ld a multiple of 4; q, k, v, out
- * 16-byte aligned.  Anything else: DSPH_E_BADARG with the limit named in the message; there is no slower path.
+ * 16-byte aligned; M at most 2^31 - 1 (the table's row indices are int32; N * M * d may pass 2^31: every offset is 64-bit).
+ * Anything else: DSPH_E_BADARG with the limit named in the message, before any HIP call; there is no slower path.
  *
  * The backward (the reference: TensorFlow's autodiff), from the forward's out and lse and the upstream gradient dout (contiguous,
  * out's shape): dq, dk, dv with rows ld_grad floats apart.  nbrT [M][widthT] is the table of the transposed graph (row j lists
@@ -518,7 +523,8 @@ int dsph_dense_attention_backward_masked(const float* q, const float* k, const f
  * A group of 16 (W <= 128) or 64 lanes owns a row and keeps its entries in registers over the batch and channel loops, so the table
  * is read from memory once per call; sums are a fused multiply-add chain per lane and a fixed butterfly: no atomics, one writer,
  * bitwise reproducible.  Any W >= 1 and C >= 1 (C = 1, 2 and multiples of 4 with 16-byte aligned maps take vector loads).
- * Bad arguments (NULL, W <= 0, C <= 0, pass < 0, mask_C not 1 or C, x overlapping y): DSPH_E_BADARG before any launch.
+ * M at most 2^31 - 1 (the table's columns are int32; N * M * C may pass 2^31: every offset is 64-bit).
+ * Bad arguments (NULL, M > 2^31 - 1, W <= 0, C <= 0, pass < 0, mask_C not 1 or C, x overlapping y): DSPH_E_BADARG before any launch.
  * Only enqueues on `hip_stream`. */
 int dsph_ell_smooth(const int32_t* cols, const float* vals, int64_t M, int32_t W, const float* x, float* y, int64_t N, int32_t C,
                     const int32_t* reps, int32_t pass, const float* mask, int32_t mask_C, int device, void* hip_stream);
