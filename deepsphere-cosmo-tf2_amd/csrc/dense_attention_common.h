@@ -1,6 +1,7 @@
-// What the two dense-attention translation units share (dense_attention.hip: exact fp32; dense_attention_split.hip: the bf16
-// split arithmetics): which rows a workgroup owns, the statistics of an owned row across its four lane groups, the grid and the
-// argument checks of the entry points.
+// What the dense-attention sources share (dense_attention_kernel.h: the three flash kernels over an arithmetic policy;
+// dense_attention.hip: the exact-fp32 policy and the entry points; dense_attention_split.hip: the bf16 split policy): which rows a
+// workgroup owns, the statistics of an owned row across its four lane groups, the mask operand, the statistic a forward leaves for
+// its backward, the arguments of a call and their checks.
 #pragma once
 
 #include "dsphere_mapops.h"
@@ -101,6 +102,42 @@ __device__ __forceinline__ void da_key_mask_addend4(float (&b)[4], const DaKeyMa
   }
 }
 
+// What the forward leaves per (row, head) for the backward, and how a probability comes back from a logit s.  Unmasked: one float,
+// lse = m + log l, p = exp(s scale - lse).  MASKED: the pair buffer (N, M, heads, 2) = (m, log l), read and written as one float2,
+// p = exp((x - m) - log l) with x the masked logit: with every key of a row masked m = -1e9 and m + log l rounds back to m, so the
+// backward needs the two apart.  (The expressions are the contract: HIP contracts a * b + c, a rewrite can change the last bit.)
+template <bool MASKED>
+struct DaStat {
+  static constexpr int FLOATS = MASKED ? 2 : 1;  // per row, also in the LDS of dk / dv
+  float f[FLOATS];
+  // of element i = row heads + h (an index, not its parts: dk / dv reads delta[i] beside it, and the two share the arithmetic)
+  static __device__ __forceinline__ DaStat load(const float* p, int64_t i) {
+    DaStat st;
+    if constexpr (MASKED) {
+      const float2 t = *reinterpret_cast<const float2*>(p + 2 * i);
+      st.f[0] = t.x; st.f[1] = t.y;
+    } else {
+      st.f[0] = p[i];
+    }
+    return st;
+  }
+  // from the running maximum m and sum l of the online softmax
+  static __device__ __forceinline__ void store(float* p, int64_t row, int heads, int h, float m, float l) {
+    if constexpr (MASKED) {
+      *reinterpret_cast<float2*>(p + 2 * (row * heads + h)) = make_float2(m, logf(l));
+    } else {
+      p[row * heads + h] = m + logf(l);
+    }
+  }
+  // the forward's logit of a key below M
+  static __device__ __forceinline__ float logit(float s, float scale, float addend) {
+    if constexpr (MASKED) return da_masked_logit(s, scale, addend); else return s * scale;
+  }
+  __device__ __forceinline__ float prob(float s, float scale, float addend) const {
+    if constexpr (MASKED) return __expf((da_masked_logit(s, scale, addend) - f[0]) - f[1]); else return __expf(fmaf(s, scale, -f[0]));
+  }
+};
+
 // workgroups of a launch: one per (map, head, block of 64 rows)
 inline int dense_grid(const char* who, int64_t N, int64_t M, int32_t heads, int64_t* nblk, unsigned* grid) {
   *nblk = (M + DA_TILE - 1) / DA_TILE;
@@ -130,12 +167,27 @@ inline int dense_mask_args_ok(const char* who, const float* mask, int64_t sb, in
   return DSPH_OK;
 }
 
-// The fp32 kernels of the _masked entry points (dense_attention.hip); arguments checked by the caller (dense_attention_split.hip,
-// where the entry points live beside the precision dispatch).  `stat` is the pair buffer (N, M, heads, 2) = (m, log l).
-int dense_attention_forward_masked_fp32(const float* q, const float* k, const float* v, int64_t ld, float* out, float* stat, const DaMask& mk,
-                                        int64_t N, int64_t M, int32_t heads, int32_t depth, hipStream_t stream);
-int dense_attention_backward_masked_fp32(const float* q, const float* k, const float* v, int64_t ld, const float* out, const float* stat,
-                                         const DaMask& mk, const float* dout, float* delta, float* dq, float* dk, float* dv, int64_t ld_grad,
-                                         int64_t N, int64_t M, int32_t heads, int32_t depth, hipStream_t stream);
+// A call past its checks, as the launch functions take it.  mk.p == nullptr: no mask, `stat` is lse (N, M, heads); else the pair
+// buffer.  The backward fields stay empty in a forward call.
+struct DenseCall {
+  const float *q, *k, *v;
+  int64_t ld;
+  float* out;        // (the backward reads it)
+  float* stat;
+  DaMask mk;
+  const float* dout;
+  float *delta, *dq, *dk, *dv;
+  int64_t ld_grad;
+  int64_t N, M;
+  int32_t heads, depth, precision;
+  int64_t nblk;
+  unsigned grid;
+  float scale;
+  hipStream_t stream;
+};
+
+// the split unit's launches (dense_attention_split.hip): precision DSPH_PREC_BF16X6 / _BF16X3, depth 32 or 64, checked by the caller
+void dense_split_launch_forward(const DenseCall& c);
+void dense_split_launch_backward(const DenseCall& c);
 
 }  // namespace dsph

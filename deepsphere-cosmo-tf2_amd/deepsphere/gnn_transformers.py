@@ -5,9 +5,9 @@ their ``MultiHeadAttention`` blocks and ``AddPositionEmbs``.  The attention over
 embedding lookups that materialise q, k and v per edge, ``exp`` and two segment sums (``:54-106``) -- is one gather kernel forward
 and two backward (``csrc/nbr_attention.hip``) working on channels-last (N, M, d) maps and a padded neighbour table.  The dense
 attention of ``Graph_ViT`` -- in the reference two ``matmul``s around a softmax over a materialised (N, heads, M, M) tensor
-(``:14-51``) -- is a flash-style kernel on the exact-fp32 MFMA (``csrc/dense_attention.hip``: key tiles through LDS, online
+(``:14-51``) -- is a flash-style kernel on the exact-fp32 MFMA (``csrc/dense_attention_kernel.h``, entry points in ``csrc/dense_attention.hip``: key tiles through LDS, online
 softmax, no logit in memory; two deterministic backward launches) on the same layout, or, by ``precision=``, on the bf16 MFMA
-through a six- or three-term split of its fp32 operands (``csrc/dense_attention_split.hip``, depth 32 and 64 per head).  The layer norms around both, with the add
+through a six- or three-term split of its fp32 operands (the same kernels over the arithmetic of ``csrc/dense_attention_split.hip``, depth 32 and 64 per head).  The layer norms around both, with the add
 between them, run on the layer-norm kernels (``csrc/layer_norm.hip``); the dense layers are the host framework's, like the GEMM of
 ``HealpyPseudoConv``.
 """

@@ -438,7 +438,8 @@ int dsph_nbr_attention_backward(const float* q, const float* k, const float* v, 
                                 float* delta, float* dq, float* dk, float* dv, int64_t ld_grad, int64_t N, int64_t M, int32_t heads,
                                 int32_t depth, int device, void* hip_stream);
 
-/* Dense attention: every row attends to every row of its map (plan-free; csrc/dense_attention.hip).
+/* Dense attention: every row attends to every row of its map (plan-free; csrc/dense_attention.hip, kernels in
+ * csrc/dense_attention_kernel.h).
  * Replaces: gnn_transformers.scaled_dot_product_attention (reference gnn_transformers.py:14-51: matmul, softmax over a materialised
  * (N, heads, M, M) tensor of logits, matmul) with mask = None -- what Graph_ViT (:248-356) and Healpy_ViT (healpy_layers.py:381-414)
  * run on -- and the split_heads transposes around it (:189-196, :225-231).
@@ -463,8 +464,8 @@ int dsph_dense_attention_backward(const float* q, const float* k, const float* v
                                   const float* dout, float* delta, float* dq, float* dk, float* dv, int64_t ld_grad, int64_t N,
                                   int64_t M, int32_t heads, int32_t depth, int device, void* hip_stream);
 
-/* The same two calls with a choice of arithmetic for their matrix products (csrc/dense_attention_split.hip); everything above
- * holds, argument checks and messages included.  `precision`:
+/* The same two calls with a choice of arithmetic for their matrix products (the same kernels over the arithmetic policy of
+ * csrc/dense_attention_split.hip); everything above holds, argument checks and messages included.  `precision`:
  *   DSPH_PREC_FP32    the two entry points above, bit for bit (every depth)
  *   DSPH_PREC_BF16X6  every product (q k^T, p v, dout v^T, ds k, ds^T q, p^T dout) on v_mfma_f32_16x16x32_bf16 with both operands
  *                     split into three bf16 terms, six partial products, fp32 accumulation: fp32-equivalent
