@@ -78,17 +78,6 @@ __device__ __forceinline__ BnLane bn_lane(const BnGeo& g) {
   return l;
 }
 
-// d(act)/d(pre-activation) from the activation's OUTPUT z
-__device__ __forceinline__ float act_grad(float z, int act) {
-  switch (act) {
-    case DSPH_ACT_RELU: return z > 0.f ? 1.f : 0.f;
-    case DSPH_ACT_ELU: return z > 0.f ? 1.f : z + 1.f;
-    case DSPH_ACT_SIGMOID: return z * (1.f - z);
-    case DSPH_ACT_TANH: return 1.f - z * z;
-    default: return 1.f;
-  }
-}
-
 // -- what the two reductions accumulate -------------------------------------------------------------------------------------
 // (count, mean[VEC], M2[VEC]) merged by Chan's formula
 template <int VEC>

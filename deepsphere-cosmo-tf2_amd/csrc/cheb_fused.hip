@@ -414,34 +414,18 @@ __global__ __launch_bounds__(256) void fused_pad_kernel(const float* __restrict_
   }
 }
 
-// Weight fragments in MFMA operand order, one 2 KiB block per (order k, slice c, column block nb):
-//   bf16x3: lane l, element j  <- w[(c*16 + 8*(l>>5) + j)*K + k][32*nb + (l&31)], hi at +0, lo at +1024
-//   fp32  : step t, lane l     <- w[(c*16 + 8*(l>>5) + t)*K + k][32*nb + (l&31)] at t*256 + l*4
-// pack (four maps per item, FusedArgs::pack): one slice, two column blocks, block diagonal -- inner index 4 q + c against columns
-// 16 q + o holds w[c*K + k][o].
+// Weight fragments in MFMA operand order (dsphere_wfrag.h: the 32x32 geometry), one 2 KiB block per (order k, slice c, column
+// block nb): WF_BF16X3 or WF_FP32_STEPS of w[(16 c + inner)*K + k][32 nb + col].
+// pack (four maps per item, FusedArgs::pack): one slice, two column blocks, block diagonal (wf_gather_pack).
 __global__ __launch_bounds__(256) void fused_wprep_kernel(const float* __restrict__ w,
                                                           unsigned char* __restrict__ out, int Fin,
                                                           int Fout, int K, int C, int NB, int prec, int ld, int pack) {
   const int blk = blockIdx.x;  // (k*C + c)*NB + nb
   const int nb = blk % NB, c = (blk / NB) % C, k = blk / (NB * C);
-  for (int e = threadIdx.x; e < 512; e += 256) {
-    const int l = e >> 3, j = e & 7;
-    const int ch = c * FUSED_CH + 8 * (l >> 5) + j, col = 32 * nb + (l & 31);
-    float v;
-    if (pack) {  // pack = P maps: 16 / P inner indices and 64 / P columns each
-      const int ci = 16 / pack, cm = 64 / pack;
-      v = (ch / ci == col / cm && ch % ci < Fin && col % cm < Fout) ? w[((int64_t)(ch % ci) * K + k) * ld + col % cm] : 0.f;
-    }
-    else v = (ch < Fin && col < Fout) ? w[((int64_t)ch * K + k) * ld + col] : 0.f;
-    unsigned char* base = out + (size_t)blk * 2048;
-    if (prec == DSPH_PREC_BF16X3) {
-      const __bf16 hi = (__bf16)v;
-      const __bf16 lo = (__bf16)(v - (float)hi);
-      reinterpret_cast<__bf16*>(base)[l * 8 + j] = hi;
-      reinterpret_cast<__bf16*>(base + 1024)[l * 8 + j] = lo;
-    } else {
-      reinterpret_cast<float*>(base)[j * 64 + l] = v;
-    }
+  for (int e = threadIdx.x; e < WF_ELEMS; e += 256) {
+    const WfElem p = wf_elem32(e);
+    wf_put(out + (size_t)blk * 2 * WF_FRAG, prec == DSPH_PREC_BF16X3 ? WF_BF16X3 : WF_FP32_STEPS, p.l, p.j,
+           wf_gather_pack(w, c * FUSED_CH + p.inner, 32 * nb + p.col, Fin, Fout, K, k, ld, pack));
   }
 }
 

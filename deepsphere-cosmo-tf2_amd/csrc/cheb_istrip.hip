@@ -14,32 +14,17 @@ namespace dsph {
 __global__ __launch_bounds__(256) void istrip_wprep_kernel(const float* __restrict__ w, unsigned char* __restrict__ out, int Fin_w,
                                                            int Fout, int K, int CH, int prec, int ld, int pair) {
   const int k = blockIdx.x;
-  const int terms = is_terms(prec), tb = is_term_bytes(prec);
+  const int terms = wf_terms(prec), tb = wf_term_bytes(prec);
   unsigned char* base = out + (size_t)k * terms * tb;
-  for (int e = threadIdx.x; e < 512; e += 256) {
-    const int l = e >> 3, j = e & 7;
-    const int ch = CH * (l >> 5) + j, col = l & 31;
+  for (int e = threadIdx.x; e < WF_ELEMS; e += 256) {
+    const WfElem p = wf_elem32(e);
+    const int g = p.l >> 5, j = p.j, col = p.col;  // the lane's half; p.inner = 8 g + j only where CH == 8
     float v;
-    if (CH == 1 && pair) v = (j < K && (l >> 5) == (col >> 4) && (col & 15) < Fout) ? w[(int64_t)j * ld + (col & 15)] : 0.f;
-    else if (CH == 1) v = (j < K && (l >> 5) < Fin_w && col < Fout) ? w[((int64_t)(l >> 5) * K + j) * ld + col] : 0.f;
-    else if (pair) v = (j < CH && j < Fin_w && (l >> 5) == (col >> 4) && (col & 15) < Fout) ? w[((int64_t)j * K + k) * ld + (col & 15)] : 0.f;
-    else v = (j < CH && ch < Fin_w && col < Fout) ? w[((int64_t)ch * K + k) * ld + col] : 0.f;
-    if (prec == DSPH_PREC_FP32) {
-      reinterpret_cast<float*>(base)[j * 64 + l] = v;  // step j, lane l
-    } else if (prec == DSPH_PREC_BF16X3) {
-      const __bf16 hi = (__bf16)v;
-      reinterpret_cast<__bf16*>(base)[l * 8 + j] = hi;
-      reinterpret_cast<__bf16*>(base + 1024)[l * 8 + j] = (__bf16)(v - (float)hi);
-    } else {
-      const unsigned au = __builtin_bit_cast(unsigned, v);
-      const float h = __builtin_bit_cast(float, au & 0xffff0000u);
-      const float r = v - h;
-      const unsigned ru = __builtin_bit_cast(unsigned, r);
-      const float m = __builtin_bit_cast(float, ru & 0xffff0000u);
-      reinterpret_cast<unsigned short*>(base)[l * 8 + j] = (unsigned short)(au >> 16);
-      reinterpret_cast<unsigned short*>(base + 1024)[l * 8 + j] = (unsigned short)(ru >> 16);
-      reinterpret_cast<__bf16*>(base + 2048)[l * 8 + j] = (__bf16)(r - m);
-    }
+    if (CH == 1 && pair) v = (j < K && g == (col >> 4)) ? wf_gather(w, 0, col & 15, 1, Fout, 1, j, ld) : 0.f;
+    else if (CH == 1) v = j < K ? wf_gather(w, g, col, Fin_w, Fout, K, j, ld) : 0.f;
+    else if (pair) v = (j < CH && g == (col >> 4)) ? wf_gather(w, j, col & 15, Fin_w, Fout, K, k, ld) : 0.f;
+    else v = j < CH ? wf_gather(w, CH * g + j, col, Fin_w, Fout, K, k, ld) : 0.f;
+    wf_put(base, prec, p.l, j, v);
   }
 }
 
@@ -49,7 +34,7 @@ bool istrip_narrow(int32_t Fin_w) { return Fin_w <= 2; }  // real input channels
 bool istrip_pairs(int32_t Fin_w, int32_t Fout) { return (Fin_w == 1 || (Fin_w >= 3 && Fin_w <= 4)) && Fout <= 16; }
 bool istrip_shape_ok(int32_t Fin, int32_t K) { return K >= 2 && K <= 5 && Fin >= 4 && Fin <= 16 && Fin % 4 == 0; }
 
-size_t istrip_wimg_bytes(int32_t K, int32_t precision) { return (size_t)K * is_terms(precision) * is_term_bytes(precision); }
+size_t istrip_wimg_bytes(int32_t K, int32_t precision) { return (size_t)K * wf_terms(precision) * wf_term_bytes(precision); }
 
 void (*istrip_kernel_k2(int ch, int prec))(IStripArgs);  // cheb_istrip_inst.hip, one translation unit per K
 void (*istrip_kernel_k3(int ch, int prec))(IStripArgs);

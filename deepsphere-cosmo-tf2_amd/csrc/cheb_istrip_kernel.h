@@ -59,10 +59,6 @@ struct IStripArgs {
 
 typedef float is_f32x8 __attribute__((ext_vector_type(8)));
 
-// number of A-operand fragments per level: hi | lo (three-term split), hi | mid | lo (six-term), 8 fp32 steps (exact)
-__host__ __device__ constexpr int is_terms(int prec) { return prec == DSPH_PREC_BF16X3 ? 2 : (prec == DSPH_PREC_BF16X6 ? 3 : 8); }
-__host__ __device__ constexpr int is_term_bytes(int prec) { return prec == DSPH_PREC_FP32 ? 256 : 1024; }
-
 // acc += cw * src[x-1] + cc * src[x] + ce * src[x+1] for the lane's CH channels (see sp_row)
 template <int CH>
 __device__ __forceinline__ void is_row(float (&acc)[CH], const float (&src)[CH], float cw, float cc, float ce) {
@@ -84,86 +80,12 @@ template <int CH> __device__ __forceinline__ void is_fence(float (&v)[CH]) {
     asm volatile("s_nop 1" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]));
 }
 
-// the B operand(s) of a plane row: 8 inner-index slots per lane, slot j <- channel j of the lane's CH (zero beyond CH)
-struct IsFrag {
-  sp_bf16x8 t[3];  // hi, lo (three-term) / hi, mid, lo (six-term)
-};
-template <int CH, int PREC>
-__device__ __forceinline__ IsFrag is_split(const float (&v)[CH]) {
-  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-  typedef float f32x2 __attribute__((ext_vector_type(2)));
-  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-  u32x4 w[3] = {{0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}};
-#pragma unroll
-  for (int j = 0; j < CH / 2; ++j) {
-    const float a0 = v[2 * j], a1 = v[2 * j + 1];
-    if (PREC == DSPH_PREC_BF16X3) {
-      // per pair: one packed convert for the two hi halves, a shift and a mask to get them back as floats, two subtractions,
-      // one packed convert for the lo halves (cheb_strip_kernel.h, xstore)
-      const unsigned hu = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{a0, a1}, bf16x2));
-      const float h0 = __builtin_bit_cast(float, hu << 16), h1 = __builtin_bit_cast(float, hu & 0xffff0000u);
-      w[0][j] = hu;
-      w[1][j] = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{a0 - h0, a1 - h1}, bf16x2));
-    } else {
-      // exact split into 8 + 8 + 8 mantissa bits by truncation (cheb_struct_kernel.h, st_contract): a = h + m + l
-      const unsigned u0 = __builtin_bit_cast(unsigned, a0), u1 = __builtin_bit_cast(unsigned, a1);
-      const float r0 = a0 - __builtin_bit_cast(float, u0 & 0xffff0000u), r1 = a1 - __builtin_bit_cast(float, u1 & 0xffff0000u);
-      const unsigned q0 = __builtin_bit_cast(unsigned, r0), q1 = __builtin_bit_cast(unsigned, r1);
-      const float l0 = r0 - __builtin_bit_cast(float, q0 & 0xffff0000u), l1 = r1 - __builtin_bit_cast(float, q1 & 0xffff0000u);
-      w[0][j] = (u0 >> 16) | (u1 & 0xffff0000u);
-      w[1][j] = (q0 >> 16) | (q1 & 0xffff0000u);
-      w[2][j] = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{l0, l1}, bf16x2));  // (at most 8 significant bits left: exact)
-    }
-  }
-  IsFrag f;
-#pragma unroll
-  for (int t = 0; t < 3; ++t) f.t[t] = __builtin_bit_cast(sp_bf16x8, w[t]);
-  return f;
-}
-
-// acc (+)= W_level . row: the contraction of one plane row with the weights of its level
-template <int CH, int PREC, bool INIT>
-__device__ __forceinline__ void is_contract(sp_f32x16& acc, const float (&row)[CH], const unsigned char* __restrict__ wlev, int lane) {
-  if (INIT) {
-#pragma unroll
-    for (int c = 0; c < 16; ++c) acc[c] = 0.f;
-  }
-  if (PREC == DSPH_PREC_FP32) {
-    // v_mfma_f32_32x32x2_f32: inner index = 2 s + (lane >> 5); the lane's operand of step s is slot j = s of the OTHER layout,
-    // so the eight steps walk the lane's eight slots: step s contracts channels {slot s of half 0, slot s of half 1}
-#pragma unroll
-    for (int s = 0; s < CH; ++s) {
-      const float b = row[s];
-      const float wa = *reinterpret_cast<const float*>(wlev + s * 256 + lane * 4);
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wa, b, acc, 0, 0, 0);
-    }
-    return;
-  }
-  const IsFrag f = is_split<CH, PREC>(row);
-  const sp_bf16x8 w0 = *reinterpret_cast<const sp_bf16x8*>(wlev + lane * 16);
-  const sp_bf16x8 w1 = *reinterpret_cast<const sp_bf16x8*>(wlev + 1024 + lane * 16);
-  if (PREC == DSPH_PREC_BF16X3) {
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0, f.t[1], acc, 0, 0, 0);  // small terms first
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w1, f.t[0], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0, f.t[0], acc, 0, 0, 0);
-  } else {
-    const sp_bf16x8 w2 = *reinterpret_cast<const sp_bf16x8*>(wlev + 2048 + lane * 16);
-    // the six products down to 2^-16: hl, lh, mm, hm, mh, hh (w index first)
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0, f.t[2], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w2, f.t[0], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w1, f.t[1], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0, f.t[1], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w1, f.t[0], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w0, f.t[0], acc, 0, 0, 0);
-  }
-}
-
 template <int K, int CH, int PREC>
 __global__ __launch_bounds__(IS_THREADS, 2) void cheb_istrip_kernel(IStripArgs a) {
   constexpr int D = K - 1;
   constexpr int G = K - 1 < 2 ? K - 1 : 2;          // y[r] is opened in the step that makes T_G[r]
   constexpr int NP = K - 1;                          // planes with a ring: T_0 .. T_{K-2}
-  constexpr int WLEVB = is_terms(PREC) * is_term_bytes(PREC);
+  constexpr int WLEVB = wf_terms(PREC) * wf_term_bytes(PREC);
   __shared__ __attribute__((aligned(16))) unsigned char smem[IS_WAVES * IS_WAVEB + K * WLEVB + 128];
   unsigned char* const sW = smem + IS_WAVES * IS_WAVEB;   // the weights of all levels (read per contraction: 2 - 3 ds_read_b128)
   float* const sBias = reinterpret_cast<float*>(sW + K * WLEVB);
@@ -334,17 +256,17 @@ __global__ __launch_bounds__(IS_THREADS, 2) void cheb_istrip_kernel(IStripArgs a
           // T_k[ytop - G]: index t - G in T_k's ring (k <= K-2), or the transient top row (k == K-1 == G)
           if (k <= K - 2) {
             const int s = ((PH - G) % 3 + 3) % 3;
-            if (k == 0) is_contract<CH, PREC, true>(Y[sy], P[k][s], sW + k * WLEVB, lane);
-            else is_contract<CH, PREC, false>(Y[sy], P[k][s], sW + k * WLEVB, lane);
+            if (k == 0) wf_contract<CH, PREC, true>(Y[sy], P[k][s], sW + k * WLEVB, lane);
+            else wf_contract<CH, PREC, false>(Y[sy], P[k][s], sW + k * WLEVB, lane);
           } else {
-            is_contract<CH, PREC, false>(Y[sy], top, sW + k * WLEVB, lane);
+            wf_contract<CH, PREC, false>(Y[sy], top, sW + k * WLEVB, lane);
           }
         }
 #pragma unroll
         for (int k = G + 1; k <= K - 1; ++k) {
           const int syk = ((PH - k) % 3 + 3) % 3;
-          if (k <= K - 2) is_contract<CH, PREC, false>(Y[syk], P[k][((PH - k) % 3 + 3) % 3], sW + k * WLEVB, lane);
-          else is_contract<CH, PREC, false>(Y[syk], top, sW + k * WLEVB, lane);
+          if (k <= K - 2) wf_contract<CH, PREC, false>(Y[syk], P[k][((PH - k) % 3 + 3) % 3], sW + k * WLEVB, lane);
+          else wf_contract<CH, PREC, false>(Y[syk], top, sW + k * WLEVB, lane);
         }
       }
       // y of row ytop - (K-1): through the staging block so that eight lanes store 128 contiguous bytes (cheb_strip_kernel.h)
@@ -463,7 +385,7 @@ __global__ __launch_bounds__(IS1_THREADS, 3) void cheb_istrip1_kernel(IStripArgs
     for (int s_ = 0; s_ < K; ++s_) wx[s_] = *reinterpret_cast<const float*>(a.wimg + s_ * 256 + lane * 4);
   } else {
 #pragma unroll
-    for (int t_ = 0; t_ < is_terms(PREC); ++t_) wf[t_] = *reinterpret_cast<const sp_bf16x8*>(a.wimg + t_ * 1024 + lane * 16);
+    for (int t_ = 0; t_ < wf_terms(PREC); ++t_) wf[t_] = *reinterpret_cast<const sp_bf16x8*>(a.wimg + t_ * 1024 + lane * 16);
   }
   if (tid < 32) sBias[tid] = (a.bias != nullptr && tid < a.Fout) ? a.bias[tid] : 0.f;
   __syncthreads();
@@ -683,9 +605,9 @@ __global__ __launch_bounds__(IS1_THREADS, 3) void cheb_istrip1_kernel(IStripArgs
       } else {
 #pragma unroll
         for (int c = 0; c < 16; ++c) Yd[c] = 0.f;
-        const IsFrag f = is_split<8, PREC>(row);
+        const WfFrag f = wf_split<8, PREC>(row);
         if (PREC == DSPH_PREC_BF16X3) {
-          Yd = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[0], f.t[1], Yd, 0, 0, 0);  // small terms first (is_contract)
+          Yd = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[0], f.t[1], Yd, 0, 0, 0);  // small terms first (wf_contract)
           Yd = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[1], f.t[0], Yd, 0, 0, 0);
           Yd = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[0], f.t[0], Yd, 0, 0, 0);
         } else {

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "cheb_qstrip_kernel.h"
+#include "dsphere_wfrag.h"
 
 namespace dsph {
 
@@ -30,11 +31,9 @@ __global__ __launch_bounds__(256) void qstrip_wprep_kernel(const float* __restri
     if (blk == 0 && threadIdx.x == 0) *reinterpret_cast<float*>(out + (size_t)2 * 4 * 3 * 2 * 2 * QS_FRAG) = 1.f / pw;
   }
   unsigned char* base = out + (size_t)blk * 2 * QS_FRAG;
-  for (int e = threadIdx.x; e < 512; e += 256) {
-    const int l = e >> 3, i = e & 7;
-    const int ch = 32 * kb + 8 * (l >> 4) + i, col = 16 * oq + (l & 15);
-    const float v = (have && ch < Fin && col < Fout) ? sc * w[((int64_t)ch * K + j) * ld + col] : 0.f;
-    qt_wimg_put(base, l * 8 + i, v, f16 != 0);
+  for (int e = threadIdx.x; e < WF_ELEMS; e += 256) {
+    const WfElem p = wf_elem16(e);
+    wf_put(base, f16 ? WF_F16X3 : WF_BF16X3, p.l, p.j, have ? wf_gather(w, 32 * kb + p.inner, 16 * oq + p.col, Fin, Fout, K, j, ld, sc) : 0.f);
   }
 }
 

@@ -230,20 +230,7 @@ __device__ __forceinline__ float qt_wimg_pow2(const float* __restrict__ w, int n
   if (mx > 0.f && mx < 3.0e38f) { (void)frexpf(mx, &ex); pw = ldexpf(1.f, 12 - ex); }  // mx = f 2^ex, f in [0.5, 1): mx pw in [2048, 4096)
   return pw;
 }
-// element `idx` (lane * 8 + i) of the hi fragment at `base` and of the lo fragment behind it
-__device__ __forceinline__ void qt_wimg_put(unsigned char* base, int idx, float v, bool f16) {
-  if (f16) {
-    const _Float16 hi = (_Float16)v;
-    const _Float16 lo = (_Float16)(v - (float)hi);
-    reinterpret_cast<_Float16*>(base)[idx] = hi;
-    reinterpret_cast<_Float16*>(base + QS_FRAG)[idx] = lo;
-  } else {
-    const __bf16 hi = (__bf16)v;
-    const __bf16 lo = (__bf16)(v - (float)hi);
-    reinterpret_cast<__bf16*>(base)[idx] = hi;
-    reinterpret_cast<__bf16*>(base + QS_FRAG)[idx] = lo;
-  }
-}
+// (the elements go in through wf_put of dsphere_wfrag.h: WF_BF16X3 or WF_F16X3)
 
 // ---- host: a launch record into a kernel's arguments ------------------------------------------------------------------------
 // What QStripArgs, Q8Args and QWgradArgs have in common, and the cut of the tape with the kernel's run-in; returns the grid.

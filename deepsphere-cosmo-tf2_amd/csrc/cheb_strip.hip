@@ -22,14 +22,9 @@ __global__ __launch_bounds__(256) void strip_wprep_kernel(const float* __restric
   const bool have = role == 0 ? lev < K - S : lev < S;
   const float sgn = sp_wsign(cheb != 0, j);
   unsigned char* base = out + (size_t)blk * 2 * SP_FRAG;
-  for (int e = threadIdx.x; e < 512; e += 256) {
-    const int l = e >> 3, i = e & 7;
-    const int ch = 16 * ib + 8 * (l >> 5) + i, col = 32 * ob + (l & 31);
-    const float v = (have && ch < Fin && col < Fout) ? sgn * w[((int64_t)ch * K + j) * ld + col] : 0.f;
-    const __bf16 hi = (__bf16)v;
-    const __bf16 lo = (__bf16)(v - (float)hi);
-    reinterpret_cast<__bf16*>(base)[l * 8 + i] = hi;
-    reinterpret_cast<__bf16*>(base + SP_FRAG)[l * 8 + i] = lo;
+  for (int e = threadIdx.x; e < WF_ELEMS; e += 256) {
+    const WfElem p = wf_elem32(e);
+    wf_put(base, WF_BF16X3, p.l, p.j, have ? wf_gather(w, 16 * ib + p.inner, 32 * ob + p.col, Fin, Fout, K, j, ld, sgn) : 0.f);
   }
 }
 

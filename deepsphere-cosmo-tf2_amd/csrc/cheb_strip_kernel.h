@@ -38,6 +38,7 @@
 
 #include "cheb_struct_kernel.h"
 #include "dsphere_common.h"
+#include "dsphere_wfrag.h"
 
 namespace dsph {
 
@@ -46,11 +47,7 @@ constexpr int SP_DMAX = 4;      // halo columns on either side: K <= 5
 constexpr int SP_USE = SP_PX - 2 * SP_DMAX;  // 24 output columns per strip
 constexpr int SP_THREADS = 512;
 constexpr int SP_STRIPS = 2;    // strips per workgroup
-constexpr int SP_FRAG = 1024;   // bytes of one MFMA operand fragment (64 lanes x 16 B)
-
-typedef float sp_f32x16 __attribute__((ext_vector_type(16)));
-typedef float sp_f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 sp_bf16x8 __attribute__((ext_vector_type(8)));
+constexpr int SP_FRAG = WF_FRAG;  // bytes of one MFMA operand fragment (the vector types sp_f32x16, sp_f32x4, sp_bf16x8: dsphere_wfrag.h)
 
 // One workgroup item: two strips side by side over the same rows.
 struct StripPair {

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "cheb_struct_kernel.h"
+#include "dsphere_wfrag.h"
 
 namespace dsph {
 
@@ -89,41 +90,18 @@ __global__ __launch_bounds__(256) void struct_tiles_kernel(const unsigned char* 
   cls[t] = struct_tile_body(t, flag, D, n_rows, n_cols, out_rows, dlimit);
 }
 
-// Weight fragments of the structured kernel, one 2 KiB block per (slice c, order k, column block nb), a slice
-// contiguous (it is streamed into LDS as one piece):
-//   bf16x3: lane l, element j <- w[(c*16 + 8*(l>>5) + j)*K + k][32*nb + (l&31)], hi at +0, lo at +1024
-//   fp32  : lane l, half e, i <- w[(c*16 + 8*(l>>5) + 4e + i)*K + k][32*nb + (l&31)] at e*1024 + l*16 + 4i
-// pack (StructArgs::pack): one slice, two column blocks, block diagonal -- inner index 4 q + c against columns 16 q + o.
+// Weight fragments of the structured kernel (dsphere_wfrag.h: the 32x32 geometry), one 2 KiB block (3 KiB: bf16x6) per (slice c,
+// order k, column block nb), a slice contiguous (it is streamed into LDS as one piece): WF_BF16X3, WF_BF16X6 or WF_FP32_HALVES of
+// w[(16 c + inner)*K + k][32 nb + col].  pack (StructArgs::pack): one slice, two column blocks, block diagonal (wf_gather_pack).
 __global__ __launch_bounds__(256) void struct_wprep_kernel(const float* __restrict__ w, unsigned char* __restrict__ out,
                                                            int Fin, int Fout, int K, int C, int NB, int prec, int ld, int pack) {
   const int blk = blockIdx.x;  // (c*K + k)*NB + nb
   const int nb = blk % NB, k = (blk / NB) % K, c = blk / (NB * K);
   unsigned char* base = out + (size_t)blk * (prec == DSPH_PREC_BF16X6 ? ST_WBLK3 : 2048);
-  for (int e = threadIdx.x; e < 512; e += 256) {
-    const int l = e >> 3, j = e & 7;
-    const int ch = c * 16 + 8 * (l >> 5) + j, col = 32 * nb + (l & 31);
-    float v;
-    if (pack) {  // pack = P maps: 16 / P inner indices and 64 / P columns each
-      const int ci = 16 / pack, cm = 64 / pack;
-      v = (ch / ci == col / cm && ch % ci < Fin && col % cm < Fout) ? w[((int64_t)(ch % ci) * K + k) * ld + col % cm] : 0.f;
-    }
-    else v = (ch < Fin && col < Fout) ? w[((int64_t)ch * K + k) * ld + col] : 0.f;
-    if (prec == DSPH_PREC_BF16X6) {  // exact three-way split by truncation (st_contract): hi | mid | lo, 1 KiB each
-      const unsigned u = __float_as_uint(v);
-      const float r = v - __uint_as_float(u & 0xffff0000u);
-      const unsigned s = __float_as_uint(r);
-      const float q = r - __uint_as_float(s & 0xffff0000u);
-      reinterpret_cast<unsigned short*>(base)[l * 8 + j] = (unsigned short)(u >> 16);
-      reinterpret_cast<unsigned short*>(base + 1024)[l * 8 + j] = (unsigned short)(s >> 16);
-      reinterpret_cast<unsigned short*>(base + 2048)[l * 8 + j] = (unsigned short)(__float_as_uint(q) >> 16);
-    } else if (prec == DSPH_PREC_BF16X3) {
-      const __bf16 hi = (__bf16)v;
-      const __bf16 lo = (__bf16)(v - (float)hi);
-      reinterpret_cast<__bf16*>(base)[l * 8 + j] = hi;
-      reinterpret_cast<__bf16*>(base + 1024)[l * 8 + j] = lo;
-    } else {
-      reinterpret_cast<float*>(base + (j >> 2) * 1024)[l * 4 + (j & 3)] = v;
-    }
+  for (int e = threadIdx.x; e < WF_ELEMS; e += 256) {
+    const WfElem p = wf_elem32(e);
+    wf_put(base, prec == DSPH_PREC_FP32 ? WF_FP32_HALVES : prec, p.l, p.j,
+           wf_gather_pack(w, c * 16 + p.inner, 32 * nb + p.col, Fin, Fout, K, k, ld, pack));
   }
 }
 

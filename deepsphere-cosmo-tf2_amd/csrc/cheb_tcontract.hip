@@ -2,14 +2,14 @@
 //     y[n, m, o] = act( sum_k sum_f planes[k][n, m, f] * w[f * K + k, o] + bias[o] )            (reference gnn_layers.py:144-150)
 // A plane row of 16 channels is 64 contiguous bytes and 32 consecutive rows are 2 KiB: a wave loads them straight into the B-operand
 // layout of v_mfma_f32_32x32x16_bf16 -- lane = (row of the block, half g), 8 channels per lane, two 16-byte loads -- splits them
-// to bf16 in registers and contracts (cheb_istrip_kernel.h, is_contract: the three arithmetics of the fused kernels; the unfused
+// to bf16 in registers and contracts (dsphere_wfrag.h, wf_contract: the three arithmetics of the fused kernels; the unfused
 // path used to run exact fp32 whatever the layer asked for, padded to 32 channels per order).  The weights are turned into
 // A-operand fragments in LDS by the workgroup itself (a few KiB), the accumulator tile (32 rows x 32 columns, lane = row) is stored
 // with 16-byte stores.  HBM-bound: K planes in, y out.  Used by the unfused path (graphs the fused kernels do not take) whenever
 // Fin * K > 64 and the fragments fit the LDS (channel counts that are not multiples of four: scalar loads); cheb_contract.hip otherwise.
 #include <algorithm>
 
-#include "cheb_istrip_kernel.h"
+#include "dsphere_wfrag.h"
 
 namespace dsph {
 
@@ -29,31 +29,16 @@ struct TContractArgs {
 template <int PREC, int NB, bool VEC>  // VEC: channel count a multiple of four, planes 16-byte aligned
 __global__ __launch_bounds__(TC_THREADS, 2) void cheb_tcontract_kernel(TContractArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char tc_smem[];
-  constexpr int TERMS = is_terms(PREC), TB = is_term_bytes(PREC), LEVB = TERMS * TB;
+  constexpr int TERMS = wf_terms(PREC), TB = wf_term_bytes(PREC), LEVB = TERMS * TB;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int px = lane & 31, g = lane >> 5;
   const int C = (a.Fin + 15) / 16, NBT = (a.Fout + 31) / 32;
   // fragments [slice c][order k][column block nb][term]: element (lane l, slot j) <- w[(16 c + 8 (l >> 5) + j) * K + k][32 nb + (l & 31)]
-  for (int e = tid; e < C * a.K * NBT * 512; e += TC_THREADS) {
-    const int blk = e >> 9, l = (e >> 3) & 63, j = e & 7;
+  for (int e = tid; e < C * a.K * NBT * WF_ELEMS; e += TC_THREADS) {
+    const int blk = e / WF_ELEMS;
+    const WfElem p = wf_elem32(e);
     const int nb = blk % NBT, k = (blk / NBT) % a.K, c = blk / (NBT * a.K);
-    const int ch = 16 * c + 8 * (l >> 5) + j, col = 32 * nb + (l & 31);
-    const float v = (ch < a.Fin && col < a.Fout) ? a.w[((int64_t)ch * a.K + k) * a.Fout + col] : 0.f;
-    unsigned char* base = tc_smem + (size_t)blk * LEVB;
-    if (PREC == DSPH_PREC_FP32) {
-      reinterpret_cast<float*>(base)[j * 64 + l] = v;
-    } else if (PREC == DSPH_PREC_BF16X3) {
-      const __bf16 hi = (__bf16)v;
-      reinterpret_cast<__bf16*>(base)[l * 8 + j] = hi;
-      reinterpret_cast<__bf16*>(base + 1024)[l * 8 + j] = (__bf16)(v - (float)hi);
-    } else {
-      const unsigned au = __builtin_bit_cast(unsigned, v);
-      const float r = v - __builtin_bit_cast(float, au & 0xffff0000u);
-      const unsigned ru = __builtin_bit_cast(unsigned, r);
-      reinterpret_cast<unsigned short*>(base)[l * 8 + j] = (unsigned short)(au >> 16);
-      reinterpret_cast<unsigned short*>(base + 1024)[l * 8 + j] = (unsigned short)(ru >> 16);
-      reinterpret_cast<__bf16*>(base + 2048)[l * 8 + j] = (__bf16)(r - __builtin_bit_cast(float, ru & 0xffff0000u));
-    }
+    wf_put<PREC>(tc_smem + (size_t)blk * LEVB, p.l, p.j, wf_gather(a.w, 16 * c + p.inner, 32 * nb + p.col, a.Fin, a.Fout, a.K, k, a.Fout));
   }
   __syncthreads();
   const int64_t blocks_per_map = (a.rows + 31) / 32, total = blocks_per_map * a.N;
@@ -85,7 +70,7 @@ __global__ __launch_bounds__(TC_THREADS, 2) void cheb_tcontract_kernel(TContract
 #pragma unroll
           for (int q = 0; q < NB; ++q)
             if (nb0 + q < NBT)
-              is_contract<8, PREC, false>(acc[q], row, tc_smem + (size_t)((c * a.K + k) * NBT + nb0 + q) * LEVB, lane);
+              wf_contract<8, PREC, false>(acc[q], row, tc_smem + (size_t)((c * a.K + k) * NBT + nb0 + q) * LEVB, lane);
         }
       }
 #pragma unroll
@@ -117,7 +102,7 @@ bool launch_cheb_tcontract(const float* const* planes, int64_t plane_rows, const
   *rc = DSPH_OK;
   if (K > TC_KMAX || N > (1 << 24)) return false;
   const int C = (Fin + 15) / 16, NBT = (Fout + 31) / 32;
-  const size_t lds = (size_t)C * K * NBT * is_terms(precision) * is_term_bytes(precision);
+  const size_t lds = (size_t)C * K * NBT * wf_terms(precision) * wf_term_bytes(precision);
   if (lds > (size_t)TC_LDS_MAX) return false;
   TContractArgs a;
   for (int k = 0; k < TC_KMAX; ++k) a.p[k] = k < K ? planes[k] : nullptr;

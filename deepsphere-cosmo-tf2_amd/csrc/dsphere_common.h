@@ -300,6 +300,16 @@ __device__ __forceinline__ float apply_act(float v, int act) {
     default: return v;
   }
 }
+// d(act)/d(pre-activation) from the activation's OUTPUT z
+__device__ __forceinline__ float act_grad(float z, int act) {
+  switch (act) {
+    case DSPH_ACT_RELU: return z > 0.f ? 1.f : 0.f;
+    case DSPH_ACT_ELU: return z > 0.f ? 1.f : z + 1.f;
+    case DSPH_ACT_SIGMOID: return z * (1.f - z);
+    case DSPH_ACT_TANH: return 1.f - z * z;
+    default: return 1.f;
+  }
+}
 
 // Blocks are dealt round-robin over the 8 XCDs (each with a private L2).  Give every XCD one
 // contiguous range of tiles so that neighbouring pixel rows -- which gather each other's data --

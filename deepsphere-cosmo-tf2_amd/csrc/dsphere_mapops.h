@@ -1,6 +1,7 @@
 // What the map operators share: the kernel families on channels-last (rows, channels) fp32 maps outside the Chebyshev plan
-// (healpix_pool, nbr_attention, dense_attention, ell_smooth, basis_change, batch_norm, layer_norm .hip).  Vector access on the
-// device; the vector-width rule, the argument checks and the launch by width on the host.  Only what two operators use.
+// (healpix_pool, nbr_attention, dense_attention, ell_smooth, basis_change, batch_norm, layer_norm, patch_gemm .hip).  Vector access
+// and the merge of float64 partials on the device; the vector-width rule, the argument checks and the launch by width on the host.
+// Only what two operators use.
 #pragma once
 
 #include <initializer_list>
@@ -67,6 +68,33 @@ inline bool workspace_ok(const char* who, const void* ptr, size_t have, size_t n
   }
   return true;
 }
+
+// The second launch of a two-launch column reduction (layer_norm's dbeta / dgamma, patch_gemm's dbias): out[c] = the sum over p < NP of
+// part[p * stride + blockIdx.y * ystep + c], c < n, in a fixed order -- a workgroup of MERGE_THREADS merges MERGE_COLS columns,
+// MERGE_SLICES threads per column taking every MERGE_SLICES-th partial, then the first of them adds the others' sums in ascending
+// order.  grid merge_grid(n, NOUT), NOUT = 1 or 2 outputs: row y of the grid writes out0 / out1 (a NULL one: nothing to do).
+// (A template, so that only the operators that launch it carry it.)
+constexpr int MERGE_THREADS = 256, MERGE_COLS = 16, MERGE_SLICES = MERGE_THREADS / MERGE_COLS;
+template <int NOUT>
+__global__ __launch_bounds__(MERGE_THREADS) void partials_merge_kernel(const double* __restrict__ part, int64_t NP, int64_t stride, int64_t ystep,
+                                                                             int32_t n, float* __restrict__ out0, float* __restrict__ out1) {
+  __shared__ double acc[MERGE_SLICES][MERGE_COLS];
+  float* out = (NOUT > 1 && blockIdx.y) ? out1 : out0;
+  if (!out) return;  // (the whole workgroup)
+  part += (int64_t)blockIdx.y * ystep;
+  const int cl = (int)threadIdx.x % MERGE_COLS, s = (int)threadIdx.x / MERGE_COLS;
+  const int c = (int)blockIdx.x * MERGE_COLS + cl;
+  double v = 0.0;
+  if (c < n)
+    for (int64_t p = s; p < NP; p += MERGE_SLICES) v += part[p * stride + c];
+  acc[s][cl] = v;
+  __syncthreads();
+  if (s == 0 && c < n) {
+    for (int t = 1; t < MERGE_SLICES; ++t) v += acc[t][cl];
+    out[c] = (float)v;
+  }
+}
+inline dim3 merge_grid(int32_t n, int outputs) { return dim3((unsigned)((n + MERGE_COLS - 1) / MERGE_COLS), (unsigned)outputs); }
 
 inline bool select_device(const char* who, int device, const DeviceGuard& guard) {
   if (!guard.ok) set_error("%s: cannot select device %d", who, device);

@@ -40,7 +40,6 @@ constexpr int64_t LN_PARTIAL_ELEMS = 8192;  // elements of the map per partial, 
 constexpr int64_t LN_FWD_ELEMS = 4096;      // elements of the map per workgroup of the forward, at least (until LN_MAX_GRID)
 constexpr int64_t LN_MAX_GRID = 8192;
 constexpr int64_t LN_MAX_ROWS = (int64_t)1 << 40;
-constexpr int LN_MERGE_COLS = 16, LN_MERGE_SLICES = LN_THREADS / LN_MERGE_COLS;
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
@@ -300,27 +299,6 @@ __global__ __launch_bounds__(LN_THREADS) void ln_bwd_kernel(const float* __restr
   }
 }
 
-// -- backward, second launch: the P partials of a channel in a fixed order.  grid (ceil(d / 16), 2): y = 0 dbeta, y = 1 dgamma; a
-//    workgroup merges 16 channels, 16 lanes per channel taking every 16th partial, then lane 0 of the channel adds the 16 ----------
-__global__ __launch_bounds__(LN_THREADS) void ln_bwd_merge_kernel(const double* __restrict__ part, int64_t P, int32_t d, float* __restrict__ dbeta,
-                                                                   float* __restrict__ dgamma) {
-  __shared__ double acc[LN_MERGE_SLICES][LN_MERGE_COLS];
-  const int which = (int)blockIdx.y;
-  float* out = which ? dgamma : dbeta;
-  if (!out) return;  // (the whole workgroup)
-  const int cl = (int)threadIdx.x % LN_MERGE_COLS, s = (int)threadIdx.x / LN_MERGE_COLS;
-  const int c = (int)blockIdx.x * LN_MERGE_COLS + cl;
-  double v = 0.0;
-  if (c < d)
-    for (int64_t p = s; p < P; p += LN_MERGE_SLICES) v += part[(p * 2 + which) * d + c];
-  acc[s][cl] = v;
-  __syncthreads();
-  if (s == 0 && c < d) {
-    for (int t = 1; t < LN_MERGE_SLICES; ++t) v += acc[t][cl];
-    out[c] = (float)v;
-  }
-}
-
 LnGeo ln_geo(int64_t rows, int32_t d, int vec) {
   LnGeo g;
   g.rows = rows;
@@ -461,8 +439,9 @@ int dsph_ln_backward(const float* a, const float* dz, const float* dsum, const f
   LN_DISPATCH(ln_bwd_kernel, vec, npl, grid, stream, a, dz, dsum, gamma, (double)eps, da, part, want_part ? 1 : 0, g);
   DSPH_HIP(hipGetLastError());
   if (want_part) {
-    hipLaunchKernelGGL(ln_bwd_merge_kernel, dim3((unsigned)((d + LN_MERGE_COLS - 1) / LN_MERGE_COLS), 2), dim3(LN_THREADS), 0, stream,
-                       (const double*)part, P, d, dbeta, dgamma);
+    // second launch: the P partials [p][dbeta | dgamma][d] of a channel in a fixed order
+    hipLaunchKernelGGL(partials_merge_kernel<2>, merge_grid(d, 2), dim3(MERGE_THREADS), 0, stream, (const double*)part, P, (int64_t)2 * d, (int64_t)d, d,
+                       dbeta, dgamma);
     DSPH_HIP(hipGetLastError());
   }
   return DSPH_OK;

@@ -8,8 +8,8 @@
 //
 // gfx950 mapping of the GEMM (the layout of cheb_tcontract.hip, which it generalises to any contraction length):
 //   * a wave owns 32 rows; lane = (row px, half g) loads 8 neighbouring floats of its row per 16-long slice of Kd -- two 16-byte
-//     loads, straight into the B operand of v_mfma_f32_32x32x16_bf16, split to bf16 in registers (is_contract of
-//     cheb_istrip_kernel.h: exact fp32 on v_mfma_f32_32x32x2_f32, the six-term and the three-term bf16 split) -- four slices
+//     loads, straight into the B operand of v_mfma_f32_32x32x16_bf16, split to bf16 in registers (wf_contract of
+//     dsphere_wfrag.h: exact fp32 on v_mfma_f32_32x32x2_f32, the six-term and the three-term bf16 split) -- four slices
 //     in flight per lane.  No LDS round trip for the map.
 //   * W goes through LDS as A-operand fragments, already split: [slice][32-column tile][term].  Where the whole image fits
 //     (PG_LDS_MAX; every p = 1 layer up to 64 -> 64, p = 2 up to 32 -> 32) a workgroup builds it once and walks row groups
@@ -22,8 +22,8 @@
 // Nothing here allocates, synchronises or reads the host: every launch goes on the caller's stream and is legal under capture.
 #include <algorithm>
 
-#include "cheb_istrip_kernel.h"
 #include "dsphere_mapops.h"
+#include "dsphere_wfrag.h"
 
 namespace dsph {
 
@@ -41,7 +41,6 @@ constexpr int PE_THREADS = 256;
 constexpr int64_t PE_MAX_PARTIALS = 2048;
 constexpr int64_t PE_PARTIAL_ELEMS = 8192;      // elements of the map per partial, at least (until PE_MAX_PARTIALS)
 constexpr int PE_ITEMS = 16;                    // floats of a period a thread holds at most (P <= 4096 = 256 threads x 16)
-constexpr int PE_MERGE_COLS = 16, PE_MERGE_SLICES = PE_THREADS / PE_MERGE_COLS;
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
@@ -55,37 +54,23 @@ struct PatchArgs {
 };
 
 // fragments of W rows [16 c0, 16 (c0 + nc)) x column tiles [t0, t0 + nt) -> LDS [slice][tile][term], the element order of
-// is_contract: (lane l, slot j) <- W[16 c + 8 (l >> 5) + j][32 t + (l & 31)], zero outside W
+// wf_contract: (lane l, slot j) <- W[16 c + 8 (l >> 5) + j][32 t + (l & 31)], zero outside W
 template <int PREC>
 __device__ __forceinline__ void pg_stage(unsigned char* smem, const PatchArgs& a, int c0, int nc, int t0, int nt) {
-  constexpr int LEVB = is_terms(PREC) * is_term_bytes(PREC);
-  for (int e = threadIdx.x; e < nc * nt * 512; e += PG_THREADS) {
-    const int blk = e >> 9, l = (e >> 3) & 63, j = e & 7;
+  constexpr int LEVB = wf_terms(PREC) * wf_term_bytes(PREC);
+  for (int e = threadIdx.x; e < nc * nt * WF_ELEMS; e += PG_THREADS) {
+    const int blk = e / WF_ELEMS;
+    const WfElem p = wf_elem32(e);
     const int t = blk % nt, c = blk / nt;
-    const int ch = 16 * (c0 + c) + 8 * (l >> 5) + j, col = 32 * (t0 + t) + (l & 31);
-    const float v = (ch < a.Kd && t0 + t < a.ntiles && col < a.C) ? a.w[(int64_t)ch * a.C + col] : 0.f;
-    unsigned char* base = smem + (size_t)blk * LEVB;
-    if (PREC == DSPH_PREC_FP32) {
-      reinterpret_cast<float*>(base)[j * 64 + l] = v;
-    } else if (PREC == DSPH_PREC_BF16X3) {
-      const __bf16 hi = (__bf16)v;
-      reinterpret_cast<__bf16*>(base)[l * 8 + j] = hi;
-      reinterpret_cast<__bf16*>(base + 1024)[l * 8 + j] = (__bf16)(v - (float)hi);
-    } else {
-      const unsigned au = __builtin_bit_cast(unsigned, v);
-      const float r = v - __builtin_bit_cast(float, au & 0xffff0000u);
-      const unsigned ru = __builtin_bit_cast(unsigned, r);
-      reinterpret_cast<unsigned short*>(base)[l * 8 + j] = (unsigned short)(au >> 16);
-      reinterpret_cast<unsigned short*>(base + 1024)[l * 8 + j] = (unsigned short)(ru >> 16);
-      reinterpret_cast<__bf16*>(base + 2048)[l * 8 + j] = (__bf16)(r - __builtin_bit_cast(float, ru & 0xffff0000u));
-    }
+    // (a tile past the last one lies past column C: zero like every column there)
+    wf_put<PREC>(smem + (size_t)blk * LEVB, p.l, p.j, wf_gather(a.w, 16 * (c0 + c) + p.inner, 32 * (t0 + t) + p.col, a.Kd, a.C, 1, 0, a.C));
   }
 }
 
 template <int PREC, int NB, bool VEC>  // VEC: Kd a multiple of four and x 16-byte aligned
 __global__ __launch_bounds__(PG_THREADS) void patch_gemm_kernel(PatchArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char pg_smem[];
-  constexpr int LEVB = is_terms(PREC) * is_term_bytes(PREC);
+  constexpr int LEVB = wf_terms(PREC) * wf_term_bytes(PREC);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int px = lane & 31, g = lane >> 5;
   if (a.resident) {
@@ -134,7 +119,7 @@ __global__ __launch_bounds__(PG_THREADS) void patch_gemm_kernel(PatchArgs a) {
 #pragma unroll
                 for (int q = 0; q < NB; ++q)
                   if (nb0 + q < tend)
-                    is_contract<8, PREC, false>(acc[q], row[u], pg_smem + (size_t)((cb + u) * a.tg + (nb0 - t0) + q) * LEVB, lane);
+                    wf_contract<8, PREC, false>(acc[q], row[u], pg_smem + (size_t)((cb + u) * a.tg + (nb0 - t0) + q) * LEVB, lane);
               }
             }
           }
@@ -176,16 +161,6 @@ struct EpiGeo {
   int64_t prow, nsteps;  // period rows R C / P, ceil(prow / rpb)
   int32_t P, nv, L, lshift, rpb, npl;
 };
-
-__device__ __forceinline__ float act_grad(float y, int act) {
-  switch (act) {
-    case DSPH_ACT_RELU: return y > 0.f ? 1.f : 0.f;
-    case DSPH_ACT_ELU: return y > 0.f ? 1.f : y + 1.f;
-    case DSPH_ACT_SIGMOID: return y * (1.f - y);
-    case DSPH_ACT_TANH: return 1.f - y * y;
-    default: return 1.f;
-  }
-}
 
 template <int VEC>
 __global__ __launch_bounds__(PE_THREADS) void patch_epilogue_bwd_kernel(const float* __restrict__ y, const float* dy, float* dz, double* __restrict__ part,
@@ -235,22 +210,6 @@ __global__ __launch_bounds__(PE_THREADS) void patch_epilogue_bwd_kernel(const fl
         part[(int64_t)blockIdx.x * g.P + (int64_t)cv * VEC + e] = s;
       }
     }
-  }
-}
-
-// grid ceil(P / 16): a workgroup merges 16 columns, 16 threads per column taking every 16th partial, then the first adds the 16
-__global__ __launch_bounds__(PE_THREADS) void patch_epilogue_merge_kernel(const double* __restrict__ part, int64_t NP, int32_t P, float* __restrict__ dbias) {
-  __shared__ double acc[PE_MERGE_SLICES][PE_MERGE_COLS];
-  const int cl = (int)threadIdx.x % PE_MERGE_COLS, s = (int)threadIdx.x / PE_MERGE_COLS;
-  const int c = (int)blockIdx.x * PE_MERGE_COLS + cl;
-  double v = 0.0;
-  if (c < P)
-    for (int64_t p = s; p < NP; p += PE_MERGE_SLICES) v += part[p * P + c];
-  acc[s][cl] = v;
-  __syncthreads();
-  if (s == 0 && c < P) {
-    for (int t = 1; t < PE_MERGE_SLICES; ++t) v += acc[t][cl];
-    dbias[c] = (float)v;
   }
 }
 
@@ -335,7 +294,7 @@ int dsph_patch_gemm(const float* x, const float* w, const float* bias, float* y,
   a.nslices = (Kd + 15) / 16;
   a.ntiles = (C + 31) / 32;
   const int nb = a.ntiles >= 4 ? 4 : (a.ntiles >= 2 ? 2 : 1);
-  const size_t levb = (size_t)is_terms(precision) * is_term_bytes(precision);
+  const size_t levb = (size_t)wf_terms(precision) * wf_term_bytes(precision);
   size_t lds = (size_t)a.nslices * a.ntiles * levb;
   a.resident = lds <= (size_t)PG_LDS_MAX;
   if (a.resident) {
@@ -395,8 +354,8 @@ int dsph_patch_epilogue_backward(const float* y, const float* dy, float* dz, flo
   else hipLaunchKernelGGL((patch_epilogue_bwd_kernel<1>), grid, block, 0, stream, y, dy, dz, part, dbias ? 1 : 0, (int)act, g);
   DSPH_HIP(hipGetLastError());
   if (dbias) {
-    hipLaunchKernelGGL(patch_epilogue_merge_kernel, dim3((unsigned)((P + PE_MERGE_COLS - 1) / PE_MERGE_COLS)), dim3(PE_THREADS), 0, stream,
-                       (const double*)part, NP, P, dbias);
+    hipLaunchKernelGGL(partials_merge_kernel<1>, merge_grid(P, 1), dim3(MERGE_THREADS), 0, stream, (const double*)part, NP, (int64_t)P, (int64_t)0, P,
+                       dbias, (float*)nullptr);
     DSPH_HIP(hipGetLastError());
   }
   return DSPH_OK;

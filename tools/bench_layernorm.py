@@ -266,8 +266,8 @@ def kernel_stats(directory, shape):
                     avg_ms = float(r["AverageNs"]) / 1e6
                     out[key] = {"calls": int(r["Calls"]), "avg_ms": avg_ms, "passes": reads + writes,
                                 "TB_per_s": (reads + writes) * map_bytes / (avg_ms * 1e-3) / 1e12}
-            if "ln_bwd_merge_kernel" in r["Name"]:
-                out["ln_bwd_merge_kernel"] = {"calls": int(r["Calls"]), "avg_ms": float(r["AverageNs"]) / 1e6}
+            if "partials_merge_kernel" in r["Name"]:
+                out["partials_merge_kernel"] = {"calls": int(r["Calls"]), "avg_ms": float(r["AverageNs"]) / 1e6}
     print(f"{shape}: one pass over the map is {map_bytes / 1e9:.3f} GB")
     for key, v in out.items():
         extra = f"{v['passes']} passes, {v['TB_per_s']:.2f} TB/s" if "passes" in v else "the fixed-order merge of the partials"
