@@ -483,57 +483,6 @@ static int32_t bfs_arithmetic(int32_t precision) {
   return struct_arithmetic(precision) == DSPH_PREC_BF16X6 ? DSPH_PREC_FP32 : precision;
 }
 
-// Diagnostic build only (make ABLATE=1): DSPH_DBG_ONLY=s / b launches only the structured-tile / only the BFS-tile kernel
-// (wrong results by construction: the other tiles of y stay unwritten), DSPH_FUSED_DEBUG sets FusedArgs::dbg (timing-only
-// ablations).  The shipped library always launches both and never skips work.
-static inline bool dbg_only(char which) {
-#ifdef DSPH_ABLATE
-  const char* e = getenv("DSPH_DBG_ONLY");
-  return e && e[0] == which;
-#else
-  (void)which;
-  return false;
-#endif
-}
-static inline int dbg_bits() {
-#ifdef DSPH_ABLATE
-  const char* dbg = getenv("DSPH_FUSED_DEBUG");
-  return dbg ? atoi(dbg) : 0;
-#else
-  return 0;
-#endif
-}
-
-// Diagnostic build only (make STAMPS=1): the BFS-tile kernel of a forward writes its clock stamps into a buffer that
-// DSPH_STAMPS_DUMP=1 prints after the launch.  Nothing in the shipped library.
-#ifdef DSPH_STAMPS
-static constexpr size_t STAMP_WORDS = 8 * 8 * 32;
-static unsigned long long* d_stamps = nullptr;
-static int stamps_begin(FusedArgs& args, hipStream_t stream) {
-  if (!d_stamps) DSPH_HIP(hipMalloc(&d_stamps, STAMP_WORDS * 8));
-  DSPH_HIP(hipMemsetAsync(d_stamps, 0, STAMP_WORDS * 8, stream));
-  args.stamps = d_stamps;
-  return DSPH_OK;
-}
-static int stamps_end(int rc, hipStream_t stream) {
-  if (rc != DSPH_OK || !getenv("DSPH_STAMPS_DUMP")) return rc;
-  std::vector<unsigned long long> h(STAMP_WORDS);
-  if (hipStreamSynchronize(stream) != hipSuccess) return rc;
-  if (hipMemcpy(h.data(), d_stamps, STAMP_WORDS * 8, hipMemcpyDeviceToHost) != hipSuccess) return rc;
-  for (int w = 0; w < 8; ++w)
-    for (int it = 0; it < 8; ++it) {
-      fprintf(stderr, "STAMP wave %d item %d:", w, it + 4);
-      const unsigned long long* r = &h[((size_t)w * 8 + it) * 32];
-      for (int i = 1; i < 32; ++i) fprintf(stderr, " %lld", r[i] && r[i - 1] ? (long long)(r[i] - r[i - 1]) : -1LL);
-      fprintf(stderr, " | t0 %llu\n", r[0]);
-    }
-  return rc;
-}
-#else
-static inline int stamps_begin(FusedArgs&, hipStream_t) { return DSPH_OK; }
-static inline int stamps_end(int rc, hipStream_t) { return rc; }
-#endif
-
 // What every launch checks first: the shape runs on these tables (ft: tiles_for), the block's images fit, the pointers the
 // kernels load and store in 16-byte pieces are aligned (out: the planes, or the slabs of the weight gradient).
 static int check_request(const FusedRequest& rq, const FusedTiles* ft, size_t ws_bytes, size_t ws_need, const void* out) {
@@ -593,7 +542,6 @@ static int launch_strips(const FusedRequest& rq, const Route& rt, const WeightIm
     st.wimg = rq.ws + img.strip;
     st.pairs = ft.d_pairs;
     st.npairs = ft.n_pairs; st.Fin = rq.Fin; st.Fout = rq.Fout; st.K = rq.K; st.precision = struct_arithmetic(rq.precision);
-    st.generic = plan->opt.strip_generic;
     st.prep_weights = fused_images_claim(plan, rq.ws, IMG_STRIP);
     return launch_cheb_strip(st, rq.stream);
   }
@@ -611,7 +559,6 @@ static int launch_strips(const FusedRequest& rq, const Route& rt, const WeightIm
 // The structured half of a forward: the strip kernel on the rectangles, then the structured-tile kernel on the class-R tiles
 // (without tables) and the class-T tiles (with per-tile tables) of the route.
 static int forward_structured(const FusedRequest& rq, const Route& rt, const WeightImages& img) {
-  if (dbg_only('b')) return DSPH_OK;
   const dsph_plan* plan = rq.plan;
   const LaunchBase base = launch_base(rq);
   if (rt.run_strips) {
@@ -685,7 +632,6 @@ static FusedArgs fused_args(const FusedRequest& rq, const Route& rt) {
   args.act = rq.act;
   args.alpha_rest = rq.alpha_rest;
   args.beta_rest = rq.beta_rest;
-  args.dbg = dbg_bits();
   return args;
 }
 
@@ -712,10 +658,7 @@ static int launch_bfs_tiles(const FusedRequest& rq, const Route& rt, FusedArgs& 
   if (args.ntiles == 0) return DSPH_OK;
   args.wfrag_bytes = (int)wfrag_bytes;
   const size_t lds = (size_t)2 * rt.pr * FUSED_CH * 4 + wfrag_bytes;
-  const int rc = stamps_begin(args, rq.stream);
-  if (rc != DSPH_OK) return rc;
-  return stamps_end(launch_fused_variant(rt.pr, rt.ft.width, args, nb, bfs_arithmetic(rq.precision), fused_grid(rq.plan, args.ntiles), lds,
-                                         rq.stream), rq.stream);
+  return launch_fused_variant(rt.pr, rt.ft.width, args, nb, bfs_arithmetic(rq.precision), fused_grid(rq.plan, args.ntiles), lds, rq.stream);
 }
 
 // The BFS half of a forward: the class-G tiles on the BFS-tile kernel; at K = 8, 32 -> 32 the rectangles first, on the quad strips.
@@ -753,7 +696,7 @@ static int forward_block(const FusedRequest& rq, const FusedTiles* ft, size_t ws
   if (rt.has_struct) {
     const int rc_s = forward_structured(rq, rt, img);
     if (rc_s != DSPH_OK) return rc_s;
-    if (!rt.has_bfs || dbg_only('s')) return DSPH_OK;
+    if (!rt.has_bfs) return DSPH_OK;
   }
   return forward_bfs(rq, rt, img);
 }

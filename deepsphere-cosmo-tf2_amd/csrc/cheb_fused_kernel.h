@@ -44,9 +44,6 @@ struct FusedArgs {
   int N, Fin, Fout, K, ntiles, nchunks, act, wfrag_bytes;
   int ld;  // row stride (floats) of y, dy: Fout of the whole layer when this launch handles one 64-column block of it
   float alpha_rest, beta_rest;  // step k >= 2: T_k = alpha * L~ T_{k-1} - beta * T_{k-2} (2,1 Chebyshev; 1,0 monomial)
-#ifdef DSPH_STAMPS
-  unsigned long long* stamps;  // diagnostic build only: [8 waves][8 items][32 points] s_memtime values
-#endif
   // Forward of a layer with at most FOUR input channels and at most 16 output columns (a network's first layers): FOUR MAPS per
   // item (pack = 4).  The 16-channel slice the recurrence works on is [map 4 n | 4 n + 1 | 4 n + 2 | 4 n + 3] x 4 channels instead
   // of 4 channels + 12 zeros (the recurrence is per channel: nothing changes), the weight image is block diagonal -- inner
@@ -60,7 +57,9 @@ struct FusedArgs {
   int64_t ypool_rows;
   int pool;
   int num_cu;  // (host side: CUs of the device, for the split of a small map's batch over gridDim.y)
-  int dbg;  // timing-only ablation bits (DSPH_FUSED_DEBUG): 1 no recurrence, 2 no contraction, 8 no y store
+  int dbg;  // always 0.  Once the timing-only ablation bits (1 no recurrence, 2 no contraction, 8 no y store); nothing sets them any
+            // more.  The kernel's four tests of it stay for now: without them hipcc allocates the registers differently, and while
+            // nearly every instantiation spills fewer SGPRs, 60 of the 171 gain scratch (4 to 56 B per lane, VGPR spills)
 };
 
 // Byte offset of 16-byte slot `slot` (0..3) of region row `row` inside a [rows][16] fp32 plane.
@@ -270,23 +269,6 @@ __device__ __forceinline__ void wgrad_plane_bf16(unsigned char* __restrict__ til
   }
   *reinterpret_cast<f32x4*>(tile) = t;
 }
-
-// Diagnostic build (make STAMPS=1; never the shipped library): s_memtime at the phase boundaries of a few
-// items of one workgroup, into a buffer nothing else reads.  Read the shares, not the run time.
-#ifdef DSPH_STAMPS
-#define DSPH_STAMP(id)                                                                        \
-  do {                                                                                        \
-    if (stamp_on) {                                                                           \
-      __builtin_amdgcn_sched_barrier(0);                                                      \
-      unsigned long long t_;                                                                  \
-      asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");              \
-      __builtin_amdgcn_sched_barrier(0);                                                      \
-      if (lane == 0) a.stamps[((size_t)wave * 8 + (item - 4)) * 32 + (id)] = t_;              \
-    }                                                                                         \
-  } while (0)
-#else
-#define DSPH_STAMP(id)
-#endif
 
 // PR: rows each LDS plane is sized for; RP: recurrence rows per lane (rows with an ELL row <= 128*RP);
 // WT: ELL width; NB: 32-column output blocks; PREC: contraction arithmetic.
@@ -533,12 +515,7 @@ __global__ __launch_bounds__(FUSED_THREADS, 2) void cheb_fused_kernel(FusedArgs 
 
     for (int item = 0; item < items; ++item) {
       const int ni = item / a.c_count, n = n_first + ni, c = a.c_begin + item - ni * a.c_count;
-#ifdef DSPH_STAMPS
-      const bool stamp_on = blockIdx.x == 72 && t == t_begin + slot0 + nslots && item >= 4 && item < 12;
-#endif
-      DSPH_STAMP(0);
       __syncthreads();  // the previous slice's last plane is still being read
-      DSPH_STAMP(1);
       // ---- T_0: the prefetched x slice goes to plane X; fetch the next slice meanwhile -------
       const bool ch_ok = pack_ || c * FUSED_CH + 4 * (tid & 3) < a.Fin;
 #pragma unroll
@@ -555,23 +532,19 @@ __global__ __launch_bounds__(FUSED_THREADS, 2) void cheb_fused_kernel(FusedArgs 
       // staging needed anyway; otherwise each phase's load waits vmcnt(0) for them, i.e. for the load before it
 #pragma unroll
       for (int s = 0; s < NS; ++s) asm volatile("" : "+v"(rid[s]));
-      DSPH_STAMP(2);
       // The next slice (of this tile, or the first one of this workgroup's next tile): its loads go out
       // one per phase, unconditionally -- after the very last slice they re-read valid rows for nothing --
       // because a conditional load is merged into pf[] by moves behind a vmcnt(0).
       const int nitem = item + 1 < items ? item + 1 : 0;
       issue_loads(nitem, 0);
-      DSPH_STAMP(3);
       if (MODE == 0) {
       if (pend && !(a.dbg & 8)) store_pending();
-      DSPH_STAMP(4);
       if (c == 0) {
 #pragma unroll
         for (int b = 0; b < NB; ++b)
 #pragma unroll
           for (int q = 0; q < 16; ++q) acc[b][q] = 0.f;
       }
-      DSPH_STAMP(5);
       // (WG: a level's fragments come from global memory behind that level's x prefetch, and the memory counter is in order --
       // the wait for them at the level's barrier is a trip to HBM at every level.  Requesting them a level ahead needs a second
       // set of fragment registers: tried in round 6 on the 1,168-row variant, 24 -> 59 spilled registers and K = 10 slower, 2.26
@@ -581,46 +554,35 @@ __global__ __launch_bounds__(FUSED_THREADS, 2) void cheb_fused_kernel(FusedArgs 
       load_wfrag<NB, PREC>(wblk, lane, wf);
       __builtin_amdgcn_sched_barrier(0);
       __syncthreads();
-      DSPH_STAMP(6);
       if (do_m) mfma_plane<NB, PREC>(planeX, wf, wave, lane, acc);
-      DSPH_STAMP(7);
 
       // ---- recurrence, two steps per trip so that the plane roles are compile-time ----------
       issue_loads(nitem, 1);
       if (do_g) gather_step<WT, RP, false, false, VW>(planeX, planeY, re(D - 1), row_l, val, pre, own);
-      DSPH_STAMP(8);
       load_wfrag<NB, PREC>(wblk + wstride, lane, wf);
       __builtin_amdgcn_sched_barrier(0);
       __syncthreads();
-      DSPH_STAMP(9);
       if (do_m) mfma_plane<NB, PREC>(planeY, wf, wave, lane, acc);
-      DSPH_STAMP(10);
       for (int k = 2; k < a.K; k += 2) {
         issue_loads(nitem, k);
         if (do_g) {
           if (cheb) gather_step<WT, RP, true, false, VW>(planeY, planeX, re(D - k), row_l, val, pre, own);
           else gather_step<WT, RP, false, false, VW>(planeY, planeX, re(D - k), row_l, val, pre, own);
         }
-        DSPH_STAMP(11 + (k - 2) * 3);
         load_wfrag<NB, PREC>(wblk + (size_t)k * wstride, lane, wf);
         __builtin_amdgcn_sched_barrier(0);
         __syncthreads();
-        DSPH_STAMP(12 + (k - 2) * 3);
         if (do_m) mfma_plane<NB, PREC>(planeX, wf, wave, lane, acc);
-        DSPH_STAMP(13 + (k - 2) * 3);
         if (k + 1 < a.K) {
           issue_loads(nitem, k + 1);
           if (do_g) {
             if (cheb) gather_step<WT, RP, true, false, VW>(planeX, planeY, re(D - k - 1), row_l, val, pre, own);
             else gather_step<WT, RP, false, false, VW>(planeX, planeY, re(D - k - 1), row_l, val, pre, own);
           }
-          DSPH_STAMP(14 + (k - 2) * 3);
           load_wfrag<NB, PREC>(wblk + (size_t)(k + 1) * wstride, lane, wf);
           __builtin_amdgcn_sched_barrier(0);
           __syncthreads();
-          DSPH_STAMP(15 + (k - 2) * 3);
           if (do_m) mfma_plane<NB, PREC>(planeY, wf, wave, lane, acc);
-          DSPH_STAMP(16 + (k - 2) * 3);
         }
       }
       } else if (MODE == 2) {

@@ -312,13 +312,6 @@ int launch_cheb_struct(const StructLaunch& s, hipStream_t stream) {
   a.ypool = s.ypool;
   a.ypool_rows = s.ypool_rows;
   const int grid = std::max(8, std::min(s.num_cu, (s.ntiles + 7) / 8 * 8));
-#ifdef DSPH_STAMPS
-  static unsigned long long* d_stamps = nullptr;
-  constexpr size_t NST = 8 * 8 * 32;
-  if (!d_stamps) DSPH_HIP(hipMalloc(&d_stamps, NST * 8));
-  DSPH_HIP(hipMemsetAsync(d_stamps, 0, NST * 8, stream));
-  a.stamps = d_stamps;
-#endif
   void (*kern)(StructArgs) = nullptr;
   const bool tab = s.tabrow != nullptr;
   const bool px = a.pack != 0 || a.pool != 0;
@@ -335,20 +328,6 @@ int launch_cheb_struct(const StructLaunch& s, hipStream_t stream) {
   const int gy = std::max(1, std::min<int>(a.N, s.num_cu / grid));
   hipLaunchKernelGGL(kern, dim3(grid, gy), dim3(ST_THREADS), 0, stream, a);
   DSPH_HIP(hipGetLastError());
-#ifdef DSPH_STAMPS
-  if (getenv("DSPH_STAMPS_DUMP")) {
-    std::vector<unsigned long long> h(NST);
-    if (hipStreamSynchronize(stream) == hipSuccess && hipMemcpy(h.data(), d_stamps, NST * 8, hipMemcpyDeviceToHost) == hipSuccess)
-      for (int w = 0; w < 8; ++w)
-        for (int it = 0; it < 8; ++it) {
-          fprintf(stderr, "STSTAMP wave %d item %d:", w, it + 4);
-          const unsigned long long* r = &h[((size_t)w * 8 + it) * 32];
-          for (int i = 1; i < 18; ++i) fprintf(stderr, " %lld", r[i] && r[i - 1] ? (long long)(r[i] - r[i - 1]) : -1LL);
-          fprintf(stderr, " | k2: A %lld B %lld C %lld", (long long)(r[18] - r[6]), (long long)(r[19] - r[18]), (long long)(r[7] - r[19]));
-          fprintf(stderr, " | t0 %llu\n", r[0]);
-        }
-  }
-#endif
   return DSPH_OK;
 }
 

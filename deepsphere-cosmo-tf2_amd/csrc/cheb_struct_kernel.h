@@ -46,26 +46,6 @@
 
 namespace dsph {
 
-// Tuning builds only (tools/ab_ablate.sh; the results are wrong by construction, the shipped library defines neither):
-// -DDSPH_ST_ABL_DIRS=n sums n of the 8 directions, -DDSPH_ST_ABL_READS=1 reads only window row 0 from LDS.
-#ifdef DSPH_ST_ABL_DIRS
-#define ST_ABL_DIRS DSPH_ST_ABL_DIRS
-#else
-#define ST_ABL_DIRS 8
-#endif
-#ifdef DSPH_ST_ABL_READS
-#define ST_ABL_READS 1
-#else
-#define ST_ABL_READS 0
-#endif
-// -DDSPH_ST_ABL_SKIP=bits: 1 no recurrence step at all, 2 no contraction, 4 no LDS-DMA, 8 no y store
-#ifdef DSPH_ST_ABL_SKIP
-#define ST_ABL_SKIP DSPH_ST_ABL_SKIP
-#else
-#define ST_ABL_SKIP 0
-#endif
-
-
 constexpr int ST_TILE = 16;                     // tile side in pixels: 256 consecutive NEST rows
 constexpr int ST_DMAX = 4;                      // halo rings held: K <= 5
 constexpr int ST_S = ST_TILE + 2 * ST_DMAX;     // plane side, 24 cells
@@ -112,27 +92,7 @@ struct StructArgs {
   float* ypool;
   int64_t ypool_rows;
   int pool;
-#ifdef DSPH_STAMPS
-  unsigned long long* stamps;  // diagnostic build only: [8 waves][8 items][32 points] s_memtime values
-#endif
 };
-
-// Diagnostic build (make STAMPS=1; never the shipped library): s_memtime at the phase boundaries of eight items of
-// one workgroup, into a buffer nothing else reads.  Read the shares, not the run time.
-#ifdef DSPH_STAMPS
-#define ST_STAMP(id)                                                                       \
-  do {                                                                                     \
-    if (stamp_on) {                                                                        \
-      __builtin_amdgcn_sched_barrier(0);                                                   \
-      unsigned long long t_;                                                               \
-      asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");           \
-      __builtin_amdgcn_sched_barrier(0);                                                   \
-      if (lane == 0) a.stamps[((size_t)(wave < 8 ? wave : 7) * 8 + (item - 4)) * 32 + (id)] = t_;  \
-    }                                                                                      \
-  } while (0)
-#else
-#define ST_STAMP(id)
-#endif
 
 // Summation order of a row: the diagonal, then SW, W, NW, N, NE, E, SE, S (dx, dy below) -- the slot order of the
 // repo's own grid-stencil producer (deepsphere/healpix.py), so that on those graphs the sums are the unfused
@@ -185,7 +145,6 @@ __device__ __forceinline__ void st_glds16_off(const void* sbase_in, unsigned vof
   const unsigned long long ubits = (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)bits) |
                                    ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(bits >> 32)) << 32);
   const void* sbase = reinterpret_cast<const void*>(ubits);
-  if (ST_ABL_SKIP & 4) return;
   unsigned keep;
   asm volatile(
       "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
@@ -205,16 +164,12 @@ template <bool FIRST, bool CHEB>
 __device__ __forceinline__ void st_gather(const unsigned char* __restrict__ smem, unsigned pin, unsigned pout,
                                           const unsigned (&gb)[4], const float (&v)[4][9], float4 (&cur)[4],
                                           float4 (&prev)[4], bool wr, unsigned dummy) {
-  if (ST_ABL_SKIP & 1) return;
   unsigned ob[4];
 #pragma unroll
   for (int p = 0; p < 4; ++p)
     ob[p] = (wr ? gb[st_cell_f((p & 1) + 1, (p >> 1) + 1)] + st_woff((p & 1) + 1, (p >> 1) + 1) : dummy) + pout;
   float4 W[4][4];
   auto rd = [&](int wx, int wy) {
-#if ST_ABL_READS
-    if (wy > 0 && !(FIRST && (wy == 1 || wy == 2) && (wx == 1 || wx == 2))) { W[wy][wx] = W[0][wx]; return; }
-#endif
     W[wy][wx] = *reinterpret_cast<const float4*>(smem + (gb[st_cell_f(wx, wy)] + pin) + st_woff(wx, wy));
   };
   // The sum of a pixel runs in the unfused kernel's order: the diagonal, then the eight directions.
@@ -227,7 +182,7 @@ __device__ __forceinline__ void st_gather(const unsigned char* __restrict__ smem
     s.z = fmaf(v[p][0], c.z, s.z);
     s.w = fmaf(v[p][0], c.w, s.w);
 #pragma unroll
-    for (int d = 0; d < ST_ABL_DIRS; ++d) {
+    for (int d = 0; d < 8; ++d) {
       const float4 u = W[j + 1 + kDirY[d]][i + 1 + kDirX[d]];
       const float w = v[p][d + 1];
       s.x = fmaf(w, u.x, s.x);
@@ -273,7 +228,6 @@ __device__ __forceinline__ void st_gather(const unsigned char* __restrict__ smem
 template <int NB, int PREC>
 __device__ __forceinline__ void st_contract(const unsigned char* __restrict__ smem, unsigned plane, unsigned wblk,
                                             const unsigned (&mb)[2], int lane, st_f32x16 (&acc)[2][NB]) {
-  if (ST_ABL_SKIP & 2) return;
   if (PREC == DSPH_PREC_BF16X6) {
     // fp32-equivalent on the bf16 pipe: v = h + m + l with 8 + 8 + 8 mantissa bits, six products (hh, hm, mh, mm, hl, lh).
     // The weights arrive pre-split (struct_wprep_kernel: 3 KiB per block, hi | mid | lo; `wblk`: the order's first block,
@@ -377,7 +331,6 @@ __device__ __forceinline__ void st_store(const st_f32x16 (&acc)[2][NB], unsigned
                                          int lane, int Fout, float floor_v, bool vec, int pack = 0, int64_t map_stride = 0,
                                          int maps_left = 4,  // pack = P: ytile is map P n's, maps_left = n_maps - P n
                                          int pool = 0) {     // pool: ytile / map_stride are the POOLED map's (64 rows per tile)
-  if (ST_ABL_SKIP & 8) return;
   const unsigned r = lane & 31, h = lane >> 5, j = lane & 7, pq = lane >> 3;
   // byte a of the 4 KiB block lives in chunk a >> 9 (512 B = the 8 cells of one column parity of one tile pixel row)
   auto scr = [&](unsigned a) -> unsigned {
@@ -636,24 +589,17 @@ __global__ __launch_bounds__(ST_THREADS, 3) void cheb_struct_kernel(StructArgs a
       }
       int n = n_first, c = 0;  // map and slice of the current item
       for (int item = 0; item < items; ++item) {
-#ifdef DSPH_STAMPS
-        const bool stamp_on = wave < 7 && blockIdx.x == 72 && t == t_begin + slot0 + nslots && item >= 4 && item < 12;
-#endif
-        ST_STAMP(0);
         if (!early) {
           asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's pieces of the item's x slice
           __syncthreads();  // B_a: the whole slice and the weights have landed
         }
-        ST_STAMP(1);
         const unsigned pxn = px ^ (2u * ST_PLANE_BYTES);
         const unsigned wbnG = wbG == (unsigned)ST_LDS_W ? (unsigned)(ST_LDS_W + ST_WSLICE_BYTES) : (unsigned)ST_LDS_W;
         const bool more = item + 1 < items || t + nslots < t_end;
         const int cn = (c + 1 == a.C || item + 1 == items) ? 0 : c + 1;
         const int nn = item + 1 == items ? n_first : (c + 1 == a.C ? n + 1 : n);
         st_gather<true, false>(smem, px, py, gb, v, ta, tb, (lact & 2u) != 0, dummy);  // ta <- T_0, tb <- T_1
-        ST_STAMP(2);
         __syncthreads();
-        ST_STAMP(3);
         if (a.K > 2) {
           if (wact & 4u) st_gather<false, CHEB>(smem, py, px, gb, v, tb, ta, (lact & 4u) != 0, dummy);  // ta <- T_2
           if (more) gdma_group(0, nn, cn, pxn, wbnG);
@@ -661,9 +607,7 @@ __global__ __launch_bounds__(ST_THREADS, 3) void cheb_struct_kernel(StructArgs a
             worder(4, itG, c, 0);
             if (more) worder(0, itG + 1, cn, 6);
           }
-          ST_STAMP(4);
           __syncthreads();
-          ST_STAMP(5);
         }
         if (a.K > 3) {
           // (a wave whose blocks all lie outside this step's region -- the border blocks sit in the last waves -- skips it)
@@ -671,18 +615,14 @@ __global__ __launch_bounds__(ST_THREADS, 3) void cheb_struct_kernel(StructArgs a
           if (more) gdma_group(1, nn, cn, pxn, wbnG);
           if (more && early) gdma_group(2, nn, cn, pxn, wbnG);
           if (stag && more) { worder(1, itG + 1, cn, 4); worder(3, itG + 1, cn, 2); }
-          ST_STAMP(6);
           __syncthreads();
-          ST_STAMP(7);
         }
         if (a.K > 4) {
           if (stag && more) worder(2, itG + 1, cn, 0);  // (first: the blocks need the interval to land)
           if (wact & 16u) st_gather<false, CHEB>(smem, py, px, gb, v, tb, ta, (lact & 16u) != 0, dummy);  // ta <- T_4
           if (more && !early) gdma_group(2, nn, cn, pxn, wbnG);
-          ST_STAMP(8);
           if (early) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (issued an interval ago: long landed)
           __syncthreads();
-          ST_STAMP(9);
         }
         if (more) {  // pieces that the shorter recurrences have not sent yet
           if (a.K <= 2) gdma_group(0, nn, cn, pxn, wbnG);
@@ -849,17 +789,11 @@ __global__ __launch_bounds__(ST_THREADS, 3) void cheb_struct_kernel(StructArgs a
     const unsigned row0 = (unsigned)a.tiles[t] * 256u;
     int n = n_first, c = 0;  // map and slice of the current item
     for (int item = 0; item < items; ++item) {
-#ifdef DSPH_STAMPS
-      const bool stamp_on = cw == 0 && blockIdx.x == 72 && t == t_begin + slot0 + nslots && item >= 4 && item < 12;
-#endif
-      ST_STAMP(0);
       // ---- B_a: this wave's pieces of the item's x slice and weights have landed ----------------------------------------
       if (!early) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        ST_STAMP(1);
         __syncthreads();
       }
-      ST_STAMP(2);
       const unsigned pxn = px ^ (2u * ST_PLANE_BYTES);
       const unsigned wbn = wb == (unsigned)ST_LDS_W ? (unsigned)(ST_LDS_W + ST_WSLICE_BYTES) : (unsigned)ST_LDS_W;
       const bool more = item + 1 < items || t + nslots < t_end;
@@ -869,37 +803,25 @@ __global__ __launch_bounds__(ST_THREADS, 3) void cheb_struct_kernel(StructArgs a
       // ---- interval 1: the previous item's last plane (and y of a finished map), then T_0 ----------------------------------
       if (item + 1 == items && more) build_rows(t + nslots);
       flush_pending();
-      ST_STAMP(3);
       st_contract<NB, PREC>(smem, px, wof(0), mb, lane, acc);
-      ST_STAMP(4);
       __syncthreads();
-      ST_STAMP(5);
       // ---- intervals 2 .. K-1: T_{k-1}, and the next item's pieces ---------------------------------------------------------
       if (a.K > 2) {
         st_contract<NB, PREC>(smem, py, wof(1), mb, lane, acc);
-        ST_STAMP(6);
         if (more) dma_group(0, nn, cn, pxn, wbn);
-        ST_STAMP(7);
         __syncthreads();
-        ST_STAMP(8);
       }
       if (a.K > 3) {
         st_contract<NB, PREC>(smem, px, wof(2), mb, lane, acc);
-        ST_STAMP(9);
         if (more) dma_group(1, nn, cn, pxn, wbn);
         if (more && early) dma_group(2, nn, cn, pxn, wbn);
-        ST_STAMP(10);
         __syncthreads();
-        ST_STAMP(11);
       }
       if (a.K > 4) {
         st_contract<NB, PREC>(smem, py, wof(3), mb, lane, acc);
-        ST_STAMP(12);
         if (more && !early) dma_group(2, nn, cn, pxn, wbn);
-        ST_STAMP(13);
         if (early) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // pieces (an interval old) and this wave's y stores
         __syncthreads();
-        ST_STAMP(14);
       }
       if (more) {  // pieces that the shorter recurrences have not sent yet
         if (a.K <= 2) dma_group(0, nn, cn, pxn, wbn);

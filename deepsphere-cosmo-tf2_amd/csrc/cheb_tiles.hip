@@ -346,15 +346,6 @@ static void build_strips(const std::vector<int32_t>& r_interior, int D, int num_
     if (!r.used)
       for (int y = r.y0; y < r.y1; ++y) rest.push_back((int32_t)st_morton((unsigned)r.tx, (unsigned)y));
   std::sort(rest.begin(), rest.end());
-#ifdef DSPH_ABLATE  // (diagnostic build only: the shipped library reads no environment variable)
-  if (getenv("DSPH_STRIP_DEBUG")) {
-    long a3 = 0, a45 = 0;
-    int hmin = 1 << 30, hmax = 0;
-    for (const TileRect& r : take) { (r.wt == 3 ? a3 : a45) += (long)r.wt * r.ht; hmin = std::min(hmin, r.ht); hmax = std::max(hmax, r.ht); }
-    fprintf(stderr, "build_strips: %zu rectangles (3 wide: %ld tiles, 4-5 wide: %ld tiles, heights %d..%d), %zu tiles left over\n",
-            take.size(), a3, a45, take.empty() ? 0 : hmin, hmax, rest.size());
-  }
-#endif
   if (take.empty()) return;
   // Segment height: every segment pays 2 D + 1 run-in rows, every workgroup should get the same number of steps.  Candidates
   // from the whole rectangle down to 256 rows (measured on the partial sky of BASELINE configs[4], batch 16, strips forced:
@@ -377,16 +368,9 @@ static void build_strips(const std::vector<int32_t>& r_interior, int D, int num_
       if (best_span < 0 || span < best_span) { best_span = span; best_h = h; }
     }
   }
-  if (opt.strip_seg > 0) best_h = std::max(16, opt.strip_seg);  // (tuning, DSPH_OPT_STRIP_SEG: the segment height, in rows)
   cut_strip_pairs(take, D, best_h, pairs);
   steps_of(pairs, steps);
   cut_strip_pairs(take, D, 1 << 30, whole);
-#ifdef DSPH_ABLATE
-  if (getenv("DSPH_STRIP_DEBUG"))
-    fprintf(stderr, "build_strips: segments of %d rows, %zu pairs, busiest workgroup %ld / %ld / %ld steps for 1 / 4 / 16 maps; tile cost "
-            "per map in the same unit %ld\n", best_h, pairs.size(), (long)strip_makespan(steps, 1, num_cu), (long)strip_makespan(steps, 4, num_cu),
-            (long)strip_makespan(steps, 16, num_cu), (long)(*n_taken * 187 / (30 * num_cu)));
-#endif
 }
 
 // ---- table-addressed quad strips (round 6) ----------------------------------------------------------------------------------
@@ -959,12 +943,7 @@ static void quad_strips5(const Graph& g, int D, const Classes& c, FusedTiles& ft
       if (q.nbr[d] == ragged) return true;
     return false;
   };
-#ifdef DSPH_ABLATE  // (diagnostic build only -- make ABLATE=1: the shipped library reads no environment variable)
-  const bool only_r = getenv("DSPH_QT_ONLY_R") != nullptr;  // (the strips of round 5's tile set on this round's kernel: tools/ab_r5_r6.sh)
-#else
-  const bool only_r = false;
-#endif
-  for (size_t i = 0; i < c.t_in.tiles.size() && !only_r; ++i) {
+  for (size_t i = 0; i < c.t_in.tiles.size(); ++i) {
     QCand q{};
     q.tile = c.t_in.tiles[i]; q.tix = (int32_t)i; q.taken = false;
     if (links_from_table(&c.t_in.rows[i * ST_CELLS], D, g.ntiles, q.nbr)) cands.push_back(q);

@@ -141,15 +141,10 @@ int dsph_plan_set_option(dsph_plan* p, int32_t option, int64_t value) {
     case DSPH_OPT_STRUCT: o.use_struct = value != 0; break;
     case DSPH_OPT_TABLES: o.use_tables = value != 0; break;
     case DSPH_OPT_FORK: o.fork = value != 0; tables = false; break;
-    case DSPH_OPT_STRIP_SEG:
-      if (value < 0 || value > (1 << 20)) { set_error("plan_set_option: DSPH_OPT_STRIP_SEG takes rows, 0 = automatic"); return DSPH_E_BADARG; }
-      o.strip_seg = (int)value;
-      break;
     case DSPH_OPT_STRIP_MINROWS:
       if (value < 4 || value > (1 << 20)) { set_error("plan_set_option: DSPH_OPT_STRIP_MINROWS takes tiles, at least 4"); return DSPH_E_BADARG; }
       o.strip_min_rows = (int)value;
       break;
-    case DSPH_OPT_STRIP_GENERIC: o.strip_generic = value != 0; tables = false; break;
     case DSPH_OPT_SPLIT:
       if (value < 0 || value > 2) { set_error("plan_set_option: DSPH_OPT_SPLIT takes 0 (automatic), 1 (always), 2 (never)"); return DSPH_E_BADARG; }
       o.split_order = (int)value;

@@ -42,9 +42,7 @@ struct PlanOptions {
   bool use_struct = true;    // DSPH_OPT_STRUCT: structured-tile kernel for the tiles that verify as a 2-D stencil
   bool use_tables = true;    // DSPH_OPT_TABLES: class-T tiles (per-tile tables) on the structured kernel
   bool fork = true;          // DSPH_OPT_FORK: BFS-tile launch on the plan's side stream beside the structured ones
-  int strip_seg = 0;         // DSPH_OPT_STRIP_SEG: rows per strip segment (0: chosen by the makespan rule)
   int strip_min_rows = 4;    // DSPH_OPT_STRIP_MINROWS: least height of a strip rectangle, in tiles
-  bool strip_generic = false;  // DSPH_OPT_STRIP_GENERIC: compiler-scheduled strip kernel instead of the hand-ordered one
   int split_order = 0;       // DSPH_OPT_SPLIT: K > 5 by the product identity (0 auto, 1 always when possible, 2 never)
   bool tstep = true;         // DSPH_OPT_TSTEP: wide graphs step through LDS tiles (cheb_tstep.hip) instead of the gather kernel
   int strip_form = 0;        // DSPH_OPT_STRIP_FORM: 0 quad strips (cheb_qstrip_kernel.h), 1 strip pairs (cheb_strip_kernel.h)
@@ -212,7 +210,6 @@ struct StripLaunch : LaunchBase {
   const StripPair* pairs;    // device list of strip pairs
   int32_t npairs, Fin, Fout, K, precision;
   bool prep_weights = true;
-  bool generic = false;      // DSPH_OPT_STRIP_GENERIC: the compiler-scheduled template also at K = 5
 };
 bool strip_shape_ok(int32_t Fin, int32_t Fout, int32_t K);
 size_t strip_wimg_bytes(int32_t Fin, int32_t Fout, int32_t K);

@@ -24,7 +24,7 @@ POOL_MAX, POOL_AVG = 0, 1
 PREPARE_BACKWARD, PREPARE_RELEASE_HOST = 1, 2
 BASIS_CHEBYSHEV, BASIS_MONOMIAL = 0, 1
 # dsph_plan_set_option (include/dsphere.h: DSPH_OPT_*)
-OPT_STRIPS, OPT_STRUCT, OPT_TABLES, OPT_FORK, OPT_STRIP_SEG, OPT_STRIP_MINROWS, OPT_STRIP_GENERIC, OPT_SPLIT, OPT_TSTEP = 1, 2, 3, 4, 5, 6, 7, 8, 9
+OPT_STRIPS, OPT_STRUCT, OPT_TABLES, OPT_FORK, OPT_STRIP_MINROWS, OPT_SPLIT, OPT_TSTEP = 1, 2, 3, 4, 6, 8, 9  # (5 and 7: retired, never reused)
 OPT_PACK = 10
 OPT_STRIP_FORM = 11
 OPT_F16_XEXP = 12

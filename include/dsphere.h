@@ -28,7 +28,8 @@ extern "C" {
 #endif
 
 #define DSPH_ABI_VERSION 3  /* 3: DSPH_OPT_F16_XEXP, dsph_plan_strip_rows, dsph_plan_uses_chain (round 6); 2: dsph_plan_prepare_layer; the entry points added
-                              * since version 1 (set_option, forward_ex, forward_pool, healpix_pool, strip_pairs) are part of it */
+                              * since version 1 (set_option, forward_ex, forward_pool, healpix_pool, strip_pairs) are part of it;
+                              * still 3 without the options 5 and 7: no symbol or struct changed */
 
 /* error codes */
 #define DSPH_OK 0
@@ -144,9 +145,7 @@ int dsph_plan_prepare_layer(dsph_plan* plan, int32_t K, int32_t Fin, int32_t Fou
  *                           every tile to the breadth-first-table kernel
  *   DSPH_OPT_TABLES         1 (default) / 0: per-tile tables (base-pixel borders, halo rows) on the structured kernel
  *   DSPH_OPT_FORK           1 (default) / 0: the BFS-tile launch of a large forward on a plan-owned side stream
- *   DSPH_OPT_STRIP_SEG      rows per strip segment, 0 (default) = chosen by the makespan rule          (tuning)
  *   DSPH_OPT_STRIP_MINROWS  least height of a strip rectangle in tiles, default 4                      (tuning)
- *   DSPH_OPT_STRIP_GENERIC  0 (default) / 1: the compiler-scheduled strip kernel at K = 5              (diagnosis)
  *   DSPH_OPT_STRIP_FORM     which strip kernel takes the rectangles of the 64 -> 64, K = 5, three-term shape: 0 (default) the
  *                           quad strips of round 5 (64-column strips, four pixels per lane, csrc/cheb_qstrip_kernel.h),
  *                           1 the strip pairs of round 3 (32-column strips, csrc/cheb_strip_kernel.h).  Same rectangles, same
@@ -167,9 +166,8 @@ int dsph_plan_prepare_layer(dsph_plan* plan, int32_t K, int32_t Fin, int32_t Fou
 #define DSPH_OPT_STRUCT 2
 #define DSPH_OPT_TABLES 3
 #define DSPH_OPT_FORK 4
-#define DSPH_OPT_STRIP_SEG 5
+/* (5 and 7 were DSPH_OPT_STRIP_SEG and DSPH_OPT_STRIP_GENERIC: unknown options now, DSPH_E_BADARG; the numbers are never reused) */
 #define DSPH_OPT_STRIP_MINROWS 6
-#define DSPH_OPT_STRIP_GENERIC 7
 #define DSPH_OPT_SPLIT 8
 #define DSPH_OPT_TSTEP 9
 #define DSPH_OPT_PACK 10

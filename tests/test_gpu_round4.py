@@ -204,7 +204,8 @@ def test_plan_options_replace_the_environment_switches():
     assert plan.tile_counts(K) == (0, ns0 + nb0)
     y_bfs, _ = _native.cheb_forward(plan, x, W, None, K, **kw)
     assert float((y_bfs - y_auto).abs().max()) / s < 2 * TOL
-    for opt, bad in ((_native.OPT_STRIPS, 3), (_native.OPT_STRIP_MINROWS, 1), (99, 0), (_native.OPT_SPLIT, -1)):
+    for opt, bad in ((_native.OPT_STRIPS, 3), (_native.OPT_STRIP_MINROWS, 1), (99, 0), (_native.OPT_SPLIT, -1),
+                     (5, 0), (7, 1)):  # (5, 7: the retired STRIP_SEG / STRIP_GENERIC, unknown like 99)
         with pytest.raises(ValueError):
             plan.set_option(opt, bad)
     plan.set_option(_native.OPT_STRUCT, 1)
