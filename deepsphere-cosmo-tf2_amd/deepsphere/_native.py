@@ -111,6 +111,7 @@ SIGNATURES = {
                                                _c_i32, _c_i32, _c_i32, _c_vp, ctypes.c_size_t, _c_vp]),
     "dsph_healpix_pool": (ctypes.c_int, [_c_vp, _c_vp, _c_i64, _c_i64, _c_i32, _c_i32, _c_i32, ctypes.c_int, _c_vp]),
     "dsph_healpix_pool_backward": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i32, _c_i32, _c_i32, ctypes.c_int, _c_vp]),
+    "dsph_healpix_reorder": (ctypes.c_int, [_c_vp, _c_vp, _c_i64, _c_i32, _c_i32, _c_i32, ctypes.c_int, _c_vp]),
     "dsph_residual_epilogue": (ctypes.c_int, [_c_vp, _c_vp, _c_i64, ctypes.c_float, _c_i32, _c_i32, ctypes.c_int, _c_vp]),
     "dsph_nbr_attention_forward": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, _c_i64, _c_vp, _c_vp, _c_vp, _c_i32, _c_i64, _c_i64, _c_i32, _c_i32,
                                                    ctypes.c_int, _c_vp]),
@@ -572,6 +573,42 @@ def healpix_pool_backward(x, dy, group, pool_type=POOL_MAX):
                                           int(pool_type), dy.device.index, _stream_ptr(dy.device))
     check(rc, "dsph_healpix_pool_backward")
     return dx
+
+
+REORDER_MAX_NSIDE = 8192  # dsph_healpix_reorder keeps pixel indices in int32
+
+
+def healpix_reorder(x, nside, to_nest, out=None):
+    """The full-sky (N, 12 nside^2, F) map ``x`` in the other pixel ordering (``dsph_healpix_reorder``): ``to_nest`` true takes a
+    RING-ordered map to NEST order, false a NEST-ordered one to RING order.  ``out`` must not share memory with ``x``; allocated
+    when None.  The arguments are checked before the library or the GPU is touched."""
+    import torch
+
+    nside = int(nside)
+    if nside < 1 or nside & (nside - 1):
+        raise ValueError(f"healpix_reorder: nside = {nside} is not a power of two >= 1")
+    if nside > REORDER_MAX_NSIDE:
+        raise ValueError(f"healpix_reorder: nside = {nside} is beyond the kernel's limit of {REORDER_MAX_NSIDE} (int32 pixel indices)")
+    if not (isinstance(x, torch.Tensor) and x.dtype == torch.float32 and x.dim() == 3 and x.is_contiguous()):
+        raise ValueError("healpix_reorder works on a contiguous float32 (N, 12 nside^2, F) tensor")
+    N, M, F = x.shape
+    if M != 12 * nside * nside or F < 1:
+        raise ValueError(f"healpix_reorder: a map of {M} pixels and {F} channels is not a full sky of nside {nside} "
+                         f"({12 * nside * nside} pixels) with at least one channel")
+    if out is not None and not (isinstance(out, torch.Tensor) and out.dtype == torch.float32 and out.is_contiguous()
+                                and out.shape == x.shape and out.device == x.device):
+        raise ValueError("out must be a contiguous float32 tensor of x's shape on x's device")
+    if not x.is_cuda:
+        raise ValueError("healpix_reorder works on a HIP tensor")
+    require_gpu()
+    if out is None:
+        out = torch.empty_like(x)
+    if N == 0:  # (an empty tensor has no address to hand over)
+        return out
+    rc = lib().dsph_healpix_reorder(_ptr(x), _ptr(out), int(N), nside, int(F), 1 if to_nest else 0, x.device.index,
+                                    _stream_ptr(x.device))
+    check(rc, "dsph_healpix_reorder")
+    return out
 
 
 def rows_layout(t):

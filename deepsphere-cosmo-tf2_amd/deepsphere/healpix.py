@@ -1,4 +1,4 @@
-"""HEALPix NEST geometry and graph-Laplacian producer (host side, numpy/scipy only).
+"""HEALPix geometry (NEST, and the RING <-> NEST index maps) and graph-Laplacian producer (host side, numpy/scipy only).
 
 The reference obtains its Laplacians from two third-party packages that exist on
 neither box (healpy, and the ``SphereHealpix`` class of a pygsp fork):
@@ -21,6 +21,10 @@ __all__ = [
     "isnsideok",
     "nest2xyf",
     "xyf2nest",
+    "nest2ring",
+    "ring2nest",
+    "reorder",
+    "reorder_table",
     "pix2vec",
     "neighbours",
     "kernel_width",
@@ -117,6 +121,113 @@ def xyf2nest(nside, ix, iy, face):
     iy = np.asarray(iy, dtype=np.int64).astype(np.uint64)
     m = _spread_bits(ix) | (_spread_bits(iy) << np.uint64(1))
     return np.asarray(face, dtype=np.int64) * (int(nside) * int(nside)) + m.astype(np.int64)
+
+
+def _check_nside(nside):
+    nside = int(nside)
+    if not isnsideok(nside):
+        raise ValueError(f"nside = {nside} is not a power of two >= 1")
+    return nside
+
+
+def nest2ring(nside, pix):
+    """NEST index -> RING index (int64, pixelwise): ring ``jr`` and position ``jp`` in it from (face, ix, iy), the arithmetic
+    of ``pix2vec``; rings are numbered from the north pole, the pixels of a ring by increasing phi."""
+    nside = _check_nside(nside)
+    ix, iy, face = nest2xyf(nside, pix)
+    nl4 = 4 * nside
+    jr = _JRLL[face] * nside - ix - iy - 1
+    north = jr < nside
+    south = jr > 3 * nside
+    nr = np.where(north, jr, np.where(south, nl4 - jr, nside))
+    before = np.where(north, 2 * nr * (nr - 1),
+                      np.where(south, 12 * nside * nside - 2 * (nr + 1) * nr, 2 * nside * (nside - 1) + (jr - nside) * nl4))
+    kshift = np.where(north | south, 0, (jr - nside) & 1)
+    jp = (_JPLL[face] * nr + ix - iy + 1 + kshift) // 2
+    jp = np.where(jp > nl4, jp - nl4, jp)
+    jp = np.where(jp < 1, jp + nl4, jp)
+    return before + jp - 1
+
+
+def _isqrt(v):
+    """floor(sqrt(v)) of non-negative int64, exact: the float64 root corrected by one either way."""
+    v = np.asarray(v, dtype=np.int64)
+    r = np.sqrt(v.astype(np.float64)).astype(np.int64)
+    r = np.where(r * r > v, r - 1, r)
+    return np.where((r + 1) * (r + 1) <= v, r + 1, r)
+
+
+def ring2nest(nside, pix):
+    """RING index -> NEST index (int64, pixelwise); the inverse of ``nest2ring``."""
+    nside = _check_nside(nside)
+    pix = np.asarray(pix, dtype=np.int64)
+    npix = 12 * nside * nside
+    ncap = 2 * nside * (nside - 1)
+    nl4 = 4 * nside
+    north = pix < ncap
+    south = pix >= npix - ncap
+    belt = ~(north | south)
+    # caps: ring i (counted from the nearer pole) starts 2 i (i - 1) pixels from it and holds 4 i
+    ip_n = np.where(north, pix, 0)
+    ip_s = np.where(south, npix - pix, 1)  # 1 .. ncap from the south pole
+    i_n = (1 + _isqrt(1 + 2 * ip_n)) >> 1
+    i_s = (1 + _isqrt(2 * ip_s - 1)) >> 1
+    ip_b = np.where(belt, pix - ncap, 0)
+    i_b = ip_b // nl4 + nside
+    iring = np.where(north, i_n, np.where(south, nl4 - i_s, i_b))  # ring number from the north pole, 1 .. 4 nside - 1
+    nr = np.where(north, i_n, np.where(south, i_s, nside))
+    iphi = np.where(north, ip_n + 1 - 2 * i_n * (i_n - 1),
+                    np.where(south, 4 * i_s + 1 - (ip_s - 2 * i_s * (i_s - 1)), ip_b % nl4 + 1))
+    kshift = np.where(belt, (iring + nside) & 1, 0)
+    # the face: in the caps the quarter of the ring; in the belt from the two diagonals through the pixel
+    ire = iring - nside + 1
+    irm = 2 * nside + 2 - ire
+    ifm = (iphi - ire // 2 + nside - 1) // nside
+    ifp = (iphi - irm // 2 + nside - 1) // nside
+    face_b = np.where(ifp == ifm, ifp | 4, np.where(ifp < ifm, ifp, ifm + 8))
+    face = np.where(north, (iphi - 1) // nr, np.where(south, 8 + (iphi - 1) // nr, face_b))
+    irt = iring - _JRLL[face] * nside + 1
+    ipt = 2 * iphi - _JPLL[face] * nr - kshift - 1
+    ipt = np.where(ipt >= 2 * nside, ipt - 8 * nside, ipt)
+    ix = (ipt - irt) >> 1
+    iy = (-ipt - irt) >> 1
+    return xyf2nest(nside, ix, iy, face)
+
+
+def reorder(m, r2n=False, n2r=False, axis=0):
+    """A full-sky map (numpy, any dtype) in the other pixel ordering along ``axis``, like ``hp.reorder``: ``r2n`` RING -> NEST,
+    ``n2r`` NEST -> RING; exactly one of them."""
+    if bool(r2n) == bool(n2r):
+        raise ValueError("reorder: set exactly one of r2n and n2r")
+    m = np.asarray(m)
+    npix = m.shape[axis]
+    nside = npix2nside(npix)  # ValueError for a length that is not 12 nside^2
+    _check_nside(nside)
+    ids = np.arange(npix, dtype=np.int64)
+    src = ring2nest(nside, ids) if n2r else nest2ring(nside, ids)  # out[i] = m[src[i]]
+    return np.take(m, src, axis=axis)
+
+
+def reorder_table(nside, indices, r2n=True):
+    """The row permutation that reorders a partial-sky map: -> (perm int32, indices_ring int64).
+
+    ``indices``: sorted unique NEST ids, the argument of ``HealpyGCNN``.  A RING-ordered map of the set holds its pixels sorted by
+    RING id (``indices_ring``), a NEST-ordered one in the order of ``indices``.  ``r2n``: out[i] = in[perm[i]] takes RING rows to
+    NEST rows; with ``r2n=False`` perm is the inverse (NEST rows to RING rows)."""
+    nside = _check_nside(nside)
+    indices = np.asarray(indices, dtype=np.int64).reshape(-1)
+    if indices.size > 1 and not np.all(np.diff(indices) > 0):
+        raise ValueError("indices must be sorted unique NEST ids")
+    if indices.size and (indices[0] < 0 or indices[-1] >= nside2npix(nside)):
+        raise ValueError(f"indices outside [0, {nside2npix(nside)})")
+    ring = nest2ring(nside, indices)
+    order = np.argsort(ring, kind="stable")  # RING row j is NEST row order[j]
+    if r2n:
+        perm = np.empty(indices.size, dtype=np.int64)
+        perm[order] = np.arange(indices.size, dtype=np.int64)
+    else:
+        perm = order
+    return perm.astype(np.int32), ring[order]
 
 
 def pix2vec(nside, pix=None, dtype=np.float64):
@@ -326,10 +437,11 @@ def extend_indices(indices, nside_in, nside_out, nest=True):
     Same contract as the reference's ``utils.extend_indices`` (``utils.py:9-37``, which
     degrades and re-upgrades a 0/1 map with healpy): in NEST order a pixel's parent at
     nside_out is ``pix >> 2*log2(nside_in/nside_out)``, so the answer is every child of
-    every touched parent.  RING order is not supported here.
+    every touched parent.  With ``nest=False`` the ids are RING ids on both sides (sorted on the way out): through
+    ``ring2nest``, the NEST rule and ``nest2ring``.
     """
     if not nest:
-        raise NotImplementedError("only NEST ordering is supported")
+        return np.sort(nest2ring(nside_in, extend_indices(ring2nest(nside_in, indices), nside_in, nside_out, nest=True)))
     indices = np.asarray(indices, dtype=np.int64)
     ratio = int(nside_in) // int(nside_out)
     if ratio < 1 or ratio * int(nside_out) != int(nside_in) or not isnsideok(ratio):

@@ -733,5 +733,91 @@ class HealpySmoothing(torch.nn.Module):
         return theta * np.pi / (60 * 180)
 
 
+class _ReorderFunction(torch.autograd.Function):
+    """``HealpyReorder``: a permutation of rows; the input gradient is the upstream gradient through the opposite direction of the
+    same operator."""
+
+    @staticmethod
+    def forward(ctx, x, layer, r2n):
+        ctx.layer, ctx.r2n = layer, r2n
+        return layer._reorder(x, r2n)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return ctx.layer._reorder(dy, not ctx.r2n), None, None
+
+
+# THE SHAPE RULE of HealpyReorder on a full-sky HIP map: the channel counts F for which the table-free kernel
+# (dsph_healpix_reorder) is not ahead of dsph_rows_pack on a cached int32 table by more than that contender's own spread run on
+# the table instead (tools/bench_reorder.py, DESIGN.md 4.12).  ``_native.healpix_reorder`` always runs the kernel.
+def _reorder_on_table(F):
+    return False
+
+
+class HealpyReorder(torch.nn.Module):
+    """RING <-> NEST reordering of (batch, pixels, channels) maps as a layer: what the reference's users do with
+    ``hp.reorder(m, r2n=True)`` in front of ``HealpyGCNN`` (HEALPix maps are stored in RING order, the network needs NEST) and
+    with ``n2r=True`` behind it.  It has no ``p`` and no ``Fout``: ``HealpyGCNN`` passes it through unchanged, so it can stand
+    first (``r2n=True``) or last (``r2n=False``) in the list of layers.
+
+    :param nside: nside of the maps
+    :param indices: sorted NEST ids of a partial-sky map (the argument of ``HealpyGCNN``), None for the full sky.  The RING side
+        of a partial-sky map holds the same pixels sorted by RING id (``indices_ring``)
+    :param r2n: True RING -> NEST, False NEST -> RING
+
+    A full-sky float32 map on a HIP device runs the table-free kernel (``dsph_healpix_reorder``; see the shape rule above); a
+    partial-sky one ``dsph_rows_pack`` on the int32 table of ``healpix.reorder_table``, moved to the device once; CPU tensors
+    (loaders) ``index_select`` on the same table.  Differentiable: the backward is the opposite direction."""
+
+    def __init__(self, nside, indices=None, r2n=True):
+        super().__init__()
+        self.nside = int(nside)
+        if not healpix.isnsideok(self.nside):
+            raise ValueError(f"nside = {nside} is not a power of two >= 1")
+        self.r2n = bool(r2n)
+        self.full_sky = indices is None
+        if self.full_sky:
+            if self.nside > _native.REORDER_MAX_NSIDE:
+                raise ValueError(f"a full-sky map of nside {self.nside} is beyond the int32 pixel indices of the kernel and of the "
+                                 f"tables (nside <= {_native.REORDER_MAX_NSIDE}); pass the pixel set as indices")
+            self.n_pix = healpix.nside2npix(self.nside)
+            self.indices = self.indices_ring = None  # (the whole sky: arange on either side, not materialised)
+        else:
+            self.indices = np.asarray(indices, dtype=np.int64).reshape(-1)
+            self.n_pix = int(self.indices.size)
+            self._perm = {}
+            self._perm[True], self.indices_ring = healpix.reorder_table(self.nside, self.indices, r2n=True)
+            self._perm[False], _ = healpix.reorder_table(self.nside, self.indices, r2n=False)
+        self._tables = {}  # (to_nest, device) -> int32 tensor
+
+    def _table(self, to_nest, device):
+        key = (bool(to_nest), str(device))
+        if key not in self._tables:
+            if self.full_sky:
+                ids = np.arange(self.n_pix, dtype=np.int64)
+                perm = (healpix.nest2ring(self.nside, ids) if to_nest else healpix.ring2nest(self.nside, ids)).astype(np.int32)
+            else:
+                perm = self._perm[bool(to_nest)]
+            self._tables[key] = torch.as_tensor(perm, dtype=torch.int32).to(device)
+        return self._tables[key]
+
+    def _reorder(self, x, to_nest):
+        if x.is_cuda and x.dtype == torch.float32:
+            x = x.contiguous()
+            if self.full_sky and not _reorder_on_table(int(x.shape[2])):
+                return _native.healpix_reorder(x, self.nside, to_nest)
+            return _native.rows_pack(x, self._table(to_nest, x.device))
+        return x.index_select(1, self._table(to_nest, x.device))
+
+    def forward(self, input_tensor):
+        x = _as_tensor(input_tensor)
+        if x.dim() != 3 or x.shape[1] != self.n_pix:
+            raise ValueError(f"HealpyReorder: input of shape {tuple(x.shape)} has {x.shape[1] if x.dim() > 1 else 0} pixels, "
+                             f"the layer was built for {self.n_pix} (nside {self.nside})")
+        return _ReorderFunction.apply(x, self, self.r2n)
+
+    call = forward
+
+
 __all__ = ["HealpyPool", "HealpyPseudoConv", "HealpyPseudoConv_Transpose", "HealpyChebyshev", "HealpyMonomial", "HealpyBernstein",
-           "Healpy_ResidualLayer", "Healpy_Transformer", "Healpy_ViT", "HealpySmoothing"]
+           "Healpy_ResidualLayer", "Healpy_Transformer", "Healpy_ViT", "HealpySmoothing", "HealpyReorder"]

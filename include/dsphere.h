@@ -408,6 +408,21 @@ int dsph_healpix_pool(const float* x, float* y, int64_t N, int64_t rows_out, int
 int dsph_healpix_pool_backward(const float* x, const float* dy, float* dx, int64_t N, int64_t rows_out, int32_t F, int32_t group,
                                int32_t type, int device, void* hip_stream);
 
+/* RING <-> NEST reordering of full-sky HEALPix maps (plan-free; csrc/healpix_reorder.hip).
+ * Replaces: hp.reorder(m, r2n=True) in front of healpy_networks.HealpyGCNN and hp.reorder(m, n2r=True) behind it (the reference's
+ * workflow for maps stored in RING order, healpy's default), i.e. a gather through an int64 table of 12 nside^2 entries.
+ *   x, y     device (N, 12 nside^2, F) fp32, contiguous; they must not overlap
+ *   to_nest  1: x is in RING order, y in NEST order;  0: x is in NEST order, y in RING order
+ *     y[n, nest(p), f] = x[n, p, f]  (to_nest = 1),   y[n, p, f] = x[n, nest(p), f]  (to_nest = 0),   p a RING index
+ * No table: a workgroup owns an aligned block of pixels of one face (one run of NEST rows) and computes every pixel's RING index
+ * from (face, ix, iy); rows under 32 floats turn through an LDS image of the block, wider rows are copied row by row.  Values are
+ * moved, never computed: bit for bit.  Vector accesses where F is a multiple of 4 (2) and the maps are aligned, scalar otherwise.
+ * nside a power of two, 1 <= nside <= 8192 (pixel indices are int32; DSPH_E_UNSUPPORTED beyond), F >= 1, N >= 0 (N = 0: DSPH_OK,
+ * no launch); every element offset is 64-bit.  Grid: the blocks of one map x min(N, 65535); further maps on further trips.
+ * Bad arguments (NULL, nside not a power of two, F < 1, N < 0, to_nest not 0 or 1, x overlapping y): DSPH_E_BADARG before any launch.
+ * Only enqueues on `hip_stream`. */
+int dsph_healpix_reorder(const float* x, float* y, int64_t N, int32_t nside, int32_t F, int32_t to_nest, int device, void* hip_stream);
+
 /* Attention over the edges of the pixel graph (plan-free; csrc/nbr_attention.hip).
  * Replaces: gnn_transformers.scaled_dot_product_sparse_attention (reference gnn_transformers.py:54-106: three embedding lookups that
  * materialise q, k, v per edge, exp, two segment sums) and the split_heads transposes around it (:189-196, :225-231).
