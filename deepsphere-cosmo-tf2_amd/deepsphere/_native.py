@@ -112,6 +112,7 @@ SIGNATURES = {
     "dsph_healpix_pool": (ctypes.c_int, [_c_vp, _c_vp, _c_i64, _c_i64, _c_i32, _c_i32, _c_i32, ctypes.c_int, _c_vp]),
     "dsph_healpix_pool_backward": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i32, _c_i32, _c_i32, ctypes.c_int, _c_vp]),
     "dsph_healpix_reorder": (ctypes.c_int, [_c_vp, _c_vp, _c_i64, _c_i32, _c_i32, _c_i32, ctypes.c_int, _c_vp]),
+    "dsph_healpix_knn": (ctypes.c_int, [_c_i32, _c_i32, _c_vp, _c_vp, _c_i64, _c_vp, _c_vp, _c_vp, ctypes.c_int, _c_vp]),
     "dsph_residual_epilogue": (ctypes.c_int, [_c_vp, _c_vp, _c_i64, ctypes.c_float, _c_i32, _c_i32, ctypes.c_int, _c_vp]),
     "dsph_nbr_attention_forward": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, _c_i64, _c_vp, _c_vp, _c_vp, _c_i32, _c_i64, _c_i64, _c_i32, _c_i32,
                                                    ctypes.c_int, _c_vp]),
@@ -609,6 +610,66 @@ def healpix_reorder(x, nside, to_nest, out=None):
                                     _stream_ptr(x.device))
     check(rc, "dsph_healpix_reorder")
     return out
+
+
+KNN_MAX_NSIDE = 8192  # dsph_healpix_knn keeps pixel indices in int32
+KNN_MAX_K = 64  # ... and the neighbours of a row in the lanes of one wave
+
+
+def healpix_knn(nside, k, indices=None, lut=None, device=None, out=None):
+    """The ``k`` nearest pixels of every pixel of a HEALPix map in NEST order (``dsph_healpix_knn``) ->
+    ``(nbr int32 [M, k], d2 float64 [M, k], ok uint8 [M])`` on ``device``.
+
+    ``indices``: sorted NEST ids of a partial-sky set, an int64 tensor on the device; None: the full sky, M = 12 nside^2.
+    ``lut``: with ``indices``, the int32 table of length 12 nside^2 that maps a NEST id to its row of the set, or -1.
+    A row with ``ok = 1`` holds the rows of the k nearest other pixels of the set by chord distance between pixel centres, ascending
+    by (d2, row), and their squared chords; the contents of a row with ``ok = 0`` are unspecified (the search window held fewer than
+    k pixels of the set, or could not prove the k-th of them nearest: the edge of a footprint).  ``out``: the three tensors to write
+    into.  The arguments are checked before the library or the GPU is touched."""
+    import torch
+
+    nside, k = int(nside), int(k)
+    if nside < 1 or nside & (nside - 1):
+        raise ValueError(f"healpix_knn: nside = {nside} is not a power of two >= 1")
+    if nside > KNN_MAX_NSIDE:
+        raise ValueError(f"healpix_knn: nside = {nside} is beyond the kernel's limit of {KNN_MAX_NSIDE} (int32 pixel indices)")
+    if not 1 <= k <= KNN_MAX_K:
+        raise ValueError(f"healpix_knn: k = {k} neighbours, the kernel takes 1 .. {KNN_MAX_K}")
+    npix = 12 * nside * nside
+    if (indices is None) != (lut is None):
+        raise ValueError("healpix_knn: indices and lut come together (both None: the full sky)")
+    if indices is not None:
+        if not (isinstance(indices, torch.Tensor) and indices.dtype == torch.int64 and indices.dim() == 1 and indices.is_contiguous()):
+            raise ValueError("healpix_knn: indices must be a contiguous int64 tensor [M]")
+        if not (isinstance(lut, torch.Tensor) and lut.dtype == torch.int32 and lut.dim() == 1 and lut.is_contiguous()
+                and lut.shape[0] == npix):
+            raise ValueError(f"healpix_knn: lut must be a contiguous int32 tensor of 12 nside^2 = {npix} entries")
+        if lut.device != indices.device:
+            raise ValueError(f"healpix_knn: lut lives on {lut.device}, indices on {indices.device}")
+        if device is not None and torch.device(device) != indices.device:
+            raise ValueError(f"healpix_knn: indices live on {indices.device}, device = {device}")
+        dev, M = indices.device, int(indices.shape[0])
+    else:
+        dev, M = torch.device("cuda" if device is None else device), npix
+    if M <= k:
+        raise ValueError(f"healpix_knn: a set of M = {M} pixels has no {k} neighbours per pixel (M > k is required)")
+    if M > npix or M >= 2**31:
+        raise ValueError(f"healpix_knn: M = {M} rows, a map of nside {nside} has at most {min(npix, 2**31 - 1)}")
+    if dev.type != "cuda":
+        raise ValueError("healpix_knn works on a HIP device")
+    require_gpu()
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    if out is None:
+        out = (torch.empty((M, k), dtype=torch.int32, device=dev), torch.empty((M, k), dtype=torch.float64, device=dev),
+               torch.empty((M,), dtype=torch.uint8, device=dev))
+    nbr, d2, ok = out
+    for t, dt, shape, name in ((nbr, torch.int32, (M, k), "nbr"), (d2, torch.float64, (M, k), "d2"), (ok, torch.uint8, (M,), "ok")):
+        if not (isinstance(t, torch.Tensor) and t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous() and t.device == dev):
+            raise ValueError(f"healpix_knn: out {name} must be a contiguous {dt} tensor of shape {shape} on {dev}")
+    rc = lib().dsph_healpix_knn(nside, k, _ptr(indices), _ptr(lut), M, _ptr(nbr), _ptr(d2), _ptr(ok), dev.index, _stream_ptr(dev))
+    check(rc, "dsph_healpix_knn")
+    return nbr, d2, ok
 
 
 def rows_layout(t):

@@ -743,7 +743,9 @@ class Chebyshev(torch.nn.Module):
         """Layer over an already rescaled Laplacian given as padded ELL arrays (cols int32,
         vals float32, shape [M, W]), skipping the ARPACK eigen-solve of the constructor -- for
         graphs too large for it (nside >= 512) and for tests that share one prepared L~ between
-        the oracle and the kernels.  Not part of the reference API."""
+        the oracle and the kernels.  Not part of the reference API.  The layer holds no scipy matrix: its ``L`` is None, its
+        ``lmax`` what the caller says the table was rescaled with.  Arrays that are already contiguous int32 / float32 are kept
+        as they are, so layers built from the same arrays share them (``HealpyGCNN(build="device")``)."""
         self = cls.__new__(cls)
         torch.nn.Module.__init__(self)
         cols = np.ascontiguousarray(ell_cols, dtype=np.int32)
@@ -865,6 +867,8 @@ class GCNN_ResidualLayer(torch.nn.Module):
     (``:370``), unknown ``norm_type`` ``ValueError`` (``:379``).
     """
 
+    LAYER_TYPES = {"CHEBY": Chebyshev, "MONO": Monomial}
+
     def __init__(self, layer_type, layer_kwargs, activation=None, act_before=False, use_bn=False,
                  norm_type="batch_norm", bn_kwargs=None, alpha=1.0):
         super().__init__()
@@ -880,14 +884,19 @@ class GCNN_ResidualLayer(torch.nn.Module):
             self.bn_kwargs = bn_kwargs
             if "axis" not in self.bn_kwargs and norm_type != "moving_norm":
                 self.bn_kwargs.update({"axis": -1})
-        if self.layer_type == "CHEBY":
-            self.layer1 = Chebyshev(**self.layer_kwargs)
-            self.layer2 = Chebyshev(**self.layer_kwargs)
-        elif self.layer_type == "MONO":
-            self.layer1 = Monomial(**self.layer_kwargs)
-            self.layer2 = Monomial(**self.layer_kwargs)
-        else:
+        cls = self.LAYER_TYPES.get(self.layer_type)
+        if cls is None:
             raise IOError(f"Layertype not understood: {self.layer_type}")
+        # ``prepared_ell`` = (cols, vals, lmax) in place of ``L`` (not a reference key): both sub-layers over one Laplacian that is
+        # already rescaled and laid out (``utils.prepare_ell``), through ``from_prepared_ell``; they share the two arrays
+        if "prepared_ell" in self.layer_kwargs:
+            kw = {k: v for k, v in self.layer_kwargs.items() if k not in ("prepared_ell", "L")}
+            cols, vals, lmax = self.layer_kwargs["prepared_ell"]
+            self.layer1 = cls.from_prepared_ell(cols, vals, lmax=lmax, **kw)
+            self.layer2 = cls.from_prepared_ell(cols, vals, lmax=lmax, **kw)
+        else:
+            self.layer1 = cls(**self.layer_kwargs)
+            self.layer2 = cls(**self.layer_kwargs)
         self.bn1 = self.bn2 = None
         if use_bn and norm_type not in ("layer_norm", "batch_norm"):
             raise ValueError(f"norm_type <{norm_type}> not understood!")

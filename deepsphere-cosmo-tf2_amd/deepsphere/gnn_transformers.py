@@ -380,7 +380,9 @@ class Graph_Transformer(torch.nn.Module):
     ``mha_layers.{i}.wqkv / dense / layer_norm1 / layer_norm2`` (``wqkv``: wq, wk, wv fused, see ``MultiHeadAttention``).
     ``embed`` and the position embedding are built on the first call, like Keras builds them.  Runs on a HIP device only."""
 
-    def __init__(self, A, key_dim, num_heads, positional_encoding=True, n_layers=1, activation="relu", layer_norm=True):
+    def __init__(self, A, key_dim, num_heads, positional_encoding=True, n_layers=1, activation="relu", layer_norm=True, tables=None):
+        """``tables`` (not a reference argument): the int32 neighbour tables (nbr, nbrT) of the graph where they exist already
+        (``healpix.healpix_adjacency_tables``; the same tensor twice for a symmetric graph); ``A`` is then not read and may be None."""
         super().__init__()
         if not n_layers >= 1:
             raise ValueError("Number of attention layers should be at least 1")
@@ -392,7 +394,13 @@ class Graph_Transformer(torch.nn.Module):
         self.n_layers = n_layers
         self.activation = activation
         self.layer_norm = layer_norm
-        nbr, nbrT = neighbour_tables(A)
+        if tables is None:
+            nbr, nbrT = neighbour_tables(A)
+        else:
+            nbr, nbrT = tables
+            for t in (nbr, nbrT):
+                if not (isinstance(t, torch.Tensor) and t.dtype == torch.int32 and t.dim() == 2 and t.is_contiguous()):
+                    raise ValueError("tables: expected (nbr, nbrT) contiguous int32 tensors [M, W]")
         self.register_buffer("nbr", nbr, persistent=False)
         if nbrT is not nbr:
             self.register_buffer("nbrT_", nbrT, persistent=False)

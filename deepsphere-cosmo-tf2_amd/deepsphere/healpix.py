@@ -10,6 +10,9 @@ graph builders (symmetrised k-NN with a Gaussian kernel, and the fixed 8-neighbo
 grid stencil of the north-star text).  The convolution never depends on *how* L was
 produced (L is an input of the layer, ``gnn_layers.py:17``), so nothing here is on
 the parity path; it only feeds tests and the benchmark with realistic matrices.
+
+The last part of the module builds the same graphs on the device (``healpix_graph_device``, ``healpix_laplacian_ell``,
+``healpix_adjacency_tables``): neighbours from the HIP kernel ``dsph_healpix_knn``, the rest as torch operators.
 """
 
 import numpy as np
@@ -32,6 +35,11 @@ __all__ = [
     "healpix_laplacian",
     "grid_laplacian_ell",
     "grid_laplacian_ell_torch",
+    "healpix_knn_device",
+    "DeviceGraph",
+    "healpix_graph_device",
+    "healpix_laplacian_ell",
+    "healpix_adjacency_tables",
     "cap_indices",
     "extend_indices",
     "superpixel_padding_mask",
@@ -528,53 +536,299 @@ def _t_pix2vec(nside, ix, iy, face, jrll, jpll):
     return torch.stack((st * torch.cos(phi), st * torch.sin(phi), z), dim=-1)
 
 
+class _GridTables:
+    """The face tables of ``neighbours`` as tensors on one device."""
+
+    def __init__(self, dev):
+        import torch
+
+        self.jrll = torch.as_tensor(_JRLL, device=dev)
+        self.jpll = torch.as_tensor(_JPLL, device=dev)
+        self.nbface = torch.as_tensor(_NB_FACE, device=dev)
+        self.nbswap = torch.as_tensor(_NB_SWAP, device=dev)
+
+
+def _t_grid_pixels(nside, p, tab):
+    """(ix, iy, face, unit vectors) of the NEST pixels ``p`` (int64 tensor)."""
+    import torch
+
+    npface = nside * nside
+    face = torch.div(p, npface, rounding_mode="floor")
+    pm = p - face * npface
+    ix = _t_compress(pm)
+    iy = _t_compress(pm >> 1)
+    return ix, iy, face, _t_pix2vec(nside, ix, iy, face, tab.jrll, tab.jpll)
+
+
+def _t_grid_neighbour(nside, kw, p, ix, iy, face, v0, i, tab):
+    """Grid neighbour ``i`` (the direction order of ``neighbours``) of the pixels ``p``: -> (ok, q, w) -- whether it exists, its
+    NEST id (``p`` itself where it does not) and the kernel weight exp(-(d / kw)^2) (0 where it does not)."""
+    import torch
+
+    npface = nside * nside
+    x = ix + int(_NB_XOFF[i])
+    y = iy + int(_NB_YOFF[i])
+    lo, hi = x < 0, x >= nside
+    x = torch.where(lo, x + nside, torch.where(hi, x - nside, x))
+    nb = 4 - lo.to(torch.int64) + hi.to(torch.int64)
+    lo, hi = y < 0, y >= nside
+    y = torch.where(lo, y + nside, torch.where(hi, y - nside, y))
+    nb = nb - 3 * lo.to(torch.int64) + 3 * hi.to(torch.int64)
+    f = tab.nbface[nb, face]
+    bits = tab.nbswap[nb, face >> 2]
+    x = torch.where((bits & 1) != 0, nside - x - 1, x)
+    y = torch.where((bits & 2) != 0, nside - y - 1, y)
+    sw = (bits & 4) != 0
+    x, y = torch.where(sw, y, x), torch.where(sw, x, y)
+    ok = f >= 0
+    fq = torch.clamp(f, min=0)
+    q = torch.where(ok, fq * npface + (_t_spread(x) | (_t_spread(y) << 1)), p)
+    d = torch.linalg.norm(_t_pix2vec(nside, x, y, fq, tab.jrll, tab.jpll) - v0, dim=1)
+    return ok, q, torch.where(ok, torch.exp(-((d / kw) ** 2)), torch.zeros_like(d))
+
+
 def grid_laplacian_ell_torch(nside, kw=None, device="cpu", chunk=1 << 22):
     """``grid_laplacian_ell`` on torch tensors: (cols int32 [M,9], vals float64 [M,9]) on ``device``."""
     import torch
 
     nside = int(nside)
-    npface = nside * nside
-    npix = 12 * npface
+    npix = 12 * nside * nside
     if kw is None:
         kw = kernel_width(nside, 8)
     dev = torch.device(device)
-    jrll = torch.as_tensor(_JRLL, device=dev)
-    jpll = torch.as_tensor(_JPLL, device=dev)
-    nbface = torch.as_tensor(_NB_FACE, device=dev)
-    nbswap = torch.as_tensor(_NB_SWAP, device=dev)
+    tab = _GridTables(dev)
     cols = torch.empty((npix, 9), dtype=torch.int32, device=dev)
     w = torch.zeros((npix, 9), dtype=torch.float64, device=dev)
     for s in range(0, npix, chunk):
         e = min(npix, s + chunk)
         p = torch.arange(s, e, dtype=torch.int64, device=dev)
-        face = torch.div(p, npface, rounding_mode="floor")
-        pm = p - face * npface
-        ix = _t_compress(pm)
-        iy = _t_compress(pm >> 1)
-        v0 = _t_pix2vec(nside, ix, iy, face, jrll, jpll)
+        ix, iy, face, v0 = _t_grid_pixels(nside, p, tab)
         cols[s:e, 0] = p.to(torch.int32)
         for i in range(8):
-            x = ix + int(_NB_XOFF[i])
-            y = iy + int(_NB_YOFF[i])
-            lo, hi = x < 0, x >= nside
-            x = torch.where(lo, x + nside, torch.where(hi, x - nside, x))
-            nb = 4 - lo.to(torch.int64) + hi.to(torch.int64)
-            lo, hi = y < 0, y >= nside
-            y = torch.where(lo, y + nside, torch.where(hi, y - nside, y))
-            nb = nb - 3 * lo.to(torch.int64) + 3 * hi.to(torch.int64)
-            f = nbface[nb, face]
-            bits = nbswap[nb, face >> 2]
-            x = torch.where((bits & 1) != 0, nside - x - 1, x)
-            y = torch.where((bits & 2) != 0, nside - y - 1, y)
-            sw = (bits & 4) != 0
-            x, y = torch.where(sw, y, x), torch.where(sw, x, y)
-            ok = f >= 0
-            fq = torch.clamp(f, min=0)
-            q = torch.where(ok, fq * npface + (_t_spread(x) | (_t_spread(y) << 1)), p)
-            d = torch.linalg.norm(_t_pix2vec(nside, x, y, fq, jrll, jpll) - v0, dim=1)
+            _, q, wi = _t_grid_neighbour(nside, kw, p, ix, iy, face, v0, i, tab)
             cols[s:e, i + 1] = q.to(torch.int32)
-            w[s:e, i + 1] = torch.where(ok, torch.exp(-((d / kw) ** 2)), torch.zeros_like(d))
+            w[s:e, i + 1] = wi
     dis = 1.0 / torch.sqrt(w.sum(dim=1))
     vals = -(w * dis[:, None]) * dis[cols.to(torch.int64)]
     vals[:, 0] = 1.0
     return cols, vals
+
+
+# ----------------------------------------------------------------------------------------------
+# Graphs built on the device: the k nearest pixels from the HIP kernel (csrc/healpix_knn.hip), everything
+# between them and the padded-ELL Laplacian as torch operators on the same device.  What HealpyGCNN(build="device")
+# runs in place of healpix_graph / healpix_laplacian / utils.csr_to_ell.
+# ----------------------------------------------------------------------------------------------
+
+
+def _index_set(nside, indices):
+    """``indices`` as a checked int64 array of sorted unique NEST ids, or None for the full sky (also a set that is all of it)."""
+    nside = _check_nside(nside)
+    npix = nside2npix(nside)
+    if indices is None:
+        return None
+    ind = np.ascontiguousarray(np.asarray(indices).reshape(-1), dtype=np.int64)
+    if ind.size > 1 and not np.all(np.diff(ind) > 0):
+        raise ValueError("indices must be sorted unique NEST ids")
+    if ind.size and (ind[0] < 0 or ind[-1] >= npix):
+        raise ValueError(f"indices outside [0, {npix})")
+    return None if ind.size == npix else ind
+
+
+def _device_lut(nside, ind, dev):
+    """(indices int64 [M], lut int32 [npix]: NEST id -> row of the set or -1) on ``dev``."""
+    import torch
+
+    ti = torch.as_tensor(ind, device=dev)
+    lut = torch.full((nside2npix(nside),), -1, dtype=torch.int32, device=dev)
+    lut[ti] = torch.arange(ti.shape[0], dtype=torch.int32, device=dev)
+    return ti, lut
+
+
+def healpix_knn_device(nside, indices=None, n_neighbors=8, device="cuda"):
+    """The ``n_neighbors`` nearest pixels of every pixel of the set, on the device: -> (nbr int32 [M, k], d2 float64 [M, k],
+    completed) -- rows of the set and squared chords, every row ascending by distance; ``completed``: how many rows the kernel
+    flagged (``_native.healpix_knn``: its window could not guarantee them -- the edge of a footprint) and a ``cKDTree`` over the
+    set's vectors filled in on the host, those rows only.
+
+    At the k-th neighbour HEALPix has exact ties (mirror pairs of pixels); which member of a tied pair a row holds is not
+    specified, and need not be the one ``healpix_graph(mode="knn")`` picks."""
+    import torch
+
+    from . import _native
+
+    nside, k = _check_nside(nside), int(n_neighbors)
+    ind = _index_set(nside, indices)
+    dev = torch.device(device)
+    if ind is None:
+        nbr, d2, ok = _native.healpix_knn(nside, k, device=dev)
+    else:
+        nbr, d2, ok = _native.healpix_knn(nside, k, *_device_lut(nside, ind, dev))
+    bad = torch.nonzero(ok == 0).reshape(-1)
+    if bad.numel():
+        from scipy.spatial import cKDTree
+
+        rows = bad.cpu().numpy()
+        vec = pix2vec(nside, ind)
+        _, nb = cKDTree(vec).query(vec[rows], k=k + 1)
+        nb = nb.reshape(rows.shape[0], k + 1)
+        # the row itself (distance 0) is among the k + 1: to the end; the others by (d2, row), as the kernel orders a row
+        order = np.argsort(nb == rows[:, None], axis=1, kind="stable")
+        nb = np.take_along_axis(nb, order, axis=1)[:, :k]
+        dd = ((vec[nb] - vec[rows][:, None, :]) ** 2).sum(axis=2)
+        order = np.lexsort((nb, dd), axis=1)
+        nb, dd = np.take_along_axis(nb, order, axis=1), np.take_along_axis(dd, order, axis=1)
+        nbr[bad] = torch.as_tensor(nb.astype(np.int32), device=nbr.device)
+        d2[bad] = torch.as_tensor(dd, device=d2.device)
+    return nbr, d2, int(bad.numel())
+
+
+class DeviceGraph:
+    """The symmetrised weighted graph of ``healpix_graph`` as sorted coordinate lists on a device: ``rows``, ``cols`` (int64) and
+    ``w`` (float64), ascending by (row, col), zero diagonal, no zero weights.  ``M``: number of pixels; ``completed``: rows of
+    the k-NN search that were completed on the host."""
+
+    def __init__(self, M, rows, cols, w, completed=0):
+        self.M, self.rows, self.cols, self.w, self.completed = int(M), rows, cols, w, int(completed)
+
+    @property
+    def nnz(self):
+        return int(self.rows.shape[0])
+
+    def _table(self, rows, cols, vals, pad_col, pad_val):
+        """Entries sorted by (row, col) as a padded table [M, W], W = the longest row (at least 1): -> (cols int32, vals)."""
+        import torch
+
+        dev, M = rows.device, self.M
+        lens = torch.bincount(rows, minlength=M)
+        W = max(int(lens.max()) if rows.numel() else 0, 1)
+        slot = torch.arange(rows.shape[0], dtype=torch.int64, device=dev) - (torch.cumsum(lens, 0) - lens)[rows]
+        if pad_col is None:  # the row itself
+            tc = torch.arange(M, dtype=torch.int32, device=dev)[:, None].repeat(1, W)
+        else:
+            tc = torch.full((M, W), pad_col, dtype=torch.int32, device=dev)
+        tc[rows, slot] = cols.to(torch.int32)
+        tv = None
+        if vals is not None:
+            tv = torch.full((M, W), pad_val, dtype=vals.dtype, device=dev)
+            tv[rows, slot] = vals
+        return tc, tv
+
+    def adjacency_table(self):
+        """The neighbour table ``utils.adjacency_to_ell`` gives for this graph: int32 [M, W], the columns of a row ascending,
+        then -1."""
+        return self._table(self.rows, self.cols, None, -1, None)[0]
+
+    def laplacian_ell(self):
+        """I - D^-1/2 W D^-1/2 in the layout of ``utils.csr_to_ell``: (cols int32 [M, W], vals float64 [M, W]), the columns of a
+        row ascending with the diagonal where it falls among them, padding (col = row, val = 0)."""
+        import torch
+
+        dev, M = self.rows.device, self.M
+        diag = torch.arange(M, dtype=torch.int64, device=dev)
+        key, order = torch.sort(torch.cat((self.rows * M + self.cols, diag * (M + 1))))
+        w = torch.cat((self.w, torch.full((M,), -1.0, dtype=torch.float64, device=dev)))[order]  # (-1: marks the diagonal)
+        rows = torch.div(key, M, rounding_mode="floor")
+        cols, w = self._table(rows, key - rows * M, w, None, 0.0)
+        del key, order, rows
+        on_diag = w < 0
+        w = torch.where(on_diag, torch.zeros_like(w), w)
+        deg = w.sum(dim=1)  # (along a row of the table: a fixed order, unlike an atomic scatter)
+        dis = torch.where(deg > 0, 1.0 / torch.sqrt(deg), torch.zeros_like(deg))
+        vals = 0.0 - (dis[:, None] * w) * dis[cols.to(torch.int64)]  # (D W) D as the host multiplies; 0 - x: padding stays +0
+        vals[on_diag] = 1.0
+        return cols, vals
+
+
+def _symmetrise(M, rows, cols, w):
+    """max(A, A^T) of coordinate entries on a device, without its zeros: -> sorted unique (rows, cols, w)."""
+    import torch
+
+    key, order = torch.sort(torch.cat((rows * M + cols, cols * M + rows)))
+    w = torch.cat((w, w))[order]
+    del order
+    key, inv = torch.unique_consecutive(key, return_inverse=True)
+    w = torch.zeros(key.shape, dtype=w.dtype, device=w.device).scatter_reduce_(0, inv, w, "amax", include_self=False)
+    del inv
+    keep = w != 0  # (eliminate_zeros of the host: a weight that underflowed is no edge)
+    key, w = key[keep], w[keep]
+    r = torch.div(key, M, rounding_mode="floor")
+    return r, key - r * M, w
+
+
+def healpix_graph_device(nside, indices=None, n_neighbors=8, mode="knn", kw=None, device="cuda"):
+    """``healpix_graph`` built on the device: -> ``DeviceGraph``.  mode="knn": neighbours from the HIP kernel
+    (``healpix_knn_device``: ties at the k-th neighbour may be broken differently from the host's k-d tree); mode="grid": the
+    8-neighbour stencil, neighbours outside the set dropped.  Weights exp(-(d / kw)^2), max(A, A^T), zero diagonal, as the host."""
+    import torch
+
+    nside = _check_nside(nside)
+    ind = _index_set(nside, indices)
+    dev = torch.device(device)
+    if kw is None:
+        kw = kernel_width(nside, n_neighbors)
+    M = nside2npix(nside) if ind is None else int(ind.shape[0])
+    completed = 0
+    if mode == "knn":
+        k = int(n_neighbors)
+        nbr, d2, completed = healpix_knn_device(nside, ind, k, dev)
+        rows = torch.arange(M, dtype=torch.int64, device=dev).repeat_interleave(k)
+        cols = nbr.reshape(-1).to(torch.int64)
+        w = torch.exp(-((torch.sqrt(d2.reshape(-1)) / kw) ** 2))
+        del nbr, d2
+    elif mode == "grid":
+        if int(n_neighbors) != 8:
+            raise NotImplementedError("the grid stencil has 8 neighbours")
+        tab = _GridTables(dev)
+        if ind is None:
+            p, lut = torch.arange(M, dtype=torch.int64, device=dev), None
+        else:
+            p, lut = _device_lut(nside, ind, dev)
+        ix, iy, face, v0 = _t_grid_pixels(nside, p, tab)
+        rr, cc, ww = [], [], []
+        own = torch.arange(M, dtype=torch.int64, device=dev)
+        for i in range(8):
+            ok, q, wi = _t_grid_neighbour(nside, kw, p, ix, iy, face, v0, i, tab)
+            if lut is not None:
+                q = lut[q].to(torch.int64)
+                ok = ok & (q >= 0)
+            rr.append(own[ok]); cc.append(q[ok]); ww.append(wi[ok])
+        rows, cols, w = torch.cat(rr), torch.cat(cc), torch.cat(ww)
+    else:
+        raise ValueError(f"unknown graph mode <{mode}>")
+    return DeviceGraph(M, *_symmetrise(M, rows, cols, w), completed=completed)
+
+
+def healpix_laplacian_ell(nside, indices=None, n_neighbors=8, mode="knn", kw=None, device="cuda"):
+    """The matrix ``healpix_laplacian`` defines, built on the device and already in the padded-ELL layout of
+    ``utils.csr_to_ell``: -> (cols int32 [M, W], vals float64 [M, W]) torch tensors on ``device``; the columns of a row ascend, the
+    diagonal sits where it falls in that order, padding is (col = row, val = 0) -- so a layer over this table sums a row in the
+    order a layer over the host's matrix does.
+
+    mode="knn": ``healpix_graph_device`` (the HIP k-NN kernel; rows it flags are completed on the host).  Not bit-identical to
+    the host's matrix where the k-th neighbour is tied: either member of a tied pair is a correct k-NN graph.
+    mode="grid": the full sky from ``grid_laplacian_ell_torch``, brought into the layout above; a partial sky with the neighbours
+    outside the set dropped and the degrees taken over what remains, as the host does."""
+    import torch
+
+    nside = _check_nside(nside)
+    ind = _index_set(nside, indices)
+    if mode == "grid" and ind is None:
+        if int(n_neighbors) != 8:
+            raise NotImplementedError("the grid stencil has 8 neighbours")
+        cols, vals = grid_laplacian_ell_torch(nside, kw=kw, device=device)
+        M = cols.shape[0]
+        pad = vals == 0  # (absent neighbours of the 24 corner pixels: col = row, val = 0)
+        order = torch.argsort(torch.where(pad, torch.full_like(cols, M), cols), dim=1, stable=True)
+        return torch.gather(cols, 1, order), torch.gather(vals, 1, order)
+    return healpix_graph_device(nside, ind, n_neighbors, mode, kw, device).laplacian_ell()
+
+
+def healpix_adjacency_tables(nside, indices=None, n_neighbors=8, mode="knn", kw=None, device="cuda", graph=None):
+    """The neighbour tables of ``Healpy_Transformer`` for the graph of ``healpix_graph_device`` (or a ``DeviceGraph`` already
+    built: ``graph``): -> (nbr, nbrT) int32 [M, W] on the device, what ``utils.adjacency_to_ell`` gives for the graph and for its
+    transpose -- ONE tensor, the graph being symmetric."""
+    if graph is None:
+        graph = healpix_graph_device(nside, indices, n_neighbors, mode, kw, device)
+    nbr = graph.adjacency_table()
+    return nbr, nbr

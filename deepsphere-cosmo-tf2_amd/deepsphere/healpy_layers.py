@@ -328,9 +328,21 @@ class HealpyChebyshev:
             **self.kwargs,
         )
 
+    _layer_cls = Chebyshev  # the layer this spec instantiates; its ``_scale`` is the one the prepared table must carry
+
+    def _get_layer_prepared(self, cols, vals, lmax, n_matmul_splits=1):
+        """The second construction path (``HealpyGCNN(build="device")``): the layer over a Laplacian that is already rescaled
+        with ``self._layer_cls._scale`` and laid out as padded ELL (``utils.prepare_ell``), through ``from_prepared_ell`` -- no
+        scipy matrix, no eigen-solve.  Such a layer has ``L = None``; ``lmax`` is recorded as given."""
+        return self._layer_cls.from_prepared_ell(cols, vals, self.K, lmax=lmax, Fout=self.Fout, initializer=self.initializer,
+                                                 activation=self.activation, use_bias=self.use_bias, use_bn=self.use_bn,
+                                                 n_matmul_splits=n_matmul_splits, **self.kwargs)
+
 
 class HealpyMonomial(HealpyChebyshev):
     """Deferred spec of a monomial graph convolution (reference ``healpy_layers.py:267-313``)."""
+
+    _layer_cls = Monomial
 
     def _get_layer(self, L, n_matmul_splits=1):
         return Monomial(L=L, K=self.K, Fout=self.Fout, initializer=self.initializer, activation=self.activation,
@@ -339,6 +351,8 @@ class HealpyMonomial(HealpyChebyshev):
 
 class HealpyBernstein(HealpyChebyshev):
     """Deferred spec of a Bernstein graph convolution of order ``K`` (reference ``healpy_layers.py:462``)."""
+
+    _layer_cls = Bernstein
 
     def _get_layer(self, L, n_matmul_splits=1):
         return Bernstein(L=L, K=self.K, Fout=self.Fout, initializer=self.initializer, activation=self.activation,
@@ -365,6 +379,20 @@ class Healpy_ResidualLayer:
     def _get_layer(self, L, n_matmul_splits=1):
         kwargs = dict(self.layer_kwargs)
         kwargs.update({"L": L, "n_matmul_splits": n_matmul_splits})
+        return GCNN_ResidualLayer(layer_type=self.layer_type, layer_kwargs=kwargs, activation=self.activation,
+                                  act_before=self.act_before, use_bn=self.use_bn, norm_type=self.norm_type,
+                                  bn_kwargs=self.bn_kwargs, alpha=self.alpha)
+
+    @property
+    def _layer_cls(self):
+        """The class of the block's two sub-layers (None for a layer type the block does not know: it raises on construction)."""
+        return GCNN_ResidualLayer.LAYER_TYPES.get(self.layer_type)
+
+    def _get_layer_prepared(self, cols, vals, lmax, n_matmul_splits=1):
+        """As ``HealpyChebyshev._get_layer_prepared``: both sub-layers over the one prepared table (``prepared_ell`` in the
+        block's ``layer_kwargs`` in place of ``L``)."""
+        kwargs = dict(self.layer_kwargs)
+        kwargs.update({"prepared_ell": (cols, vals, lmax), "n_matmul_splits": n_matmul_splits})
         return GCNN_ResidualLayer(layer_type=self.layer_type, layer_kwargs=kwargs, activation=self.activation,
                                   act_before=self.act_before, use_bn=self.use_bn, norm_type=self.norm_type,
                                   bn_kwargs=self.bn_kwargs, alpha=self.alpha)
@@ -396,6 +424,12 @@ class Healpy_Transformer:
         return Graph_Transformer(A=A, key_dim=self.key_dim, num_heads=self.num_heads,
                                  positional_encoding=self.positional_encoding, n_layers=self.n_layers,
                                  activation=self.activation, layer_norm=self.layer_norm)
+
+    def _get_layer_prepared(self, nbr, nbrT):
+        """The layer over neighbour tables that exist already (``healpix.healpix_adjacency_tables``); its ``A`` is None."""
+        return Graph_Transformer(A=None, key_dim=self.key_dim, num_heads=self.num_heads,
+                                 positional_encoding=self.positional_encoding, n_layers=self.n_layers,
+                                 activation=self.activation, layer_norm=self.layer_norm, tables=(nbr, nbrT))
 
 
 class Healpy_ViT(Graph_ViT):

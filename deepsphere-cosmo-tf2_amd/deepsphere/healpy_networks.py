@@ -11,16 +11,71 @@ pooling layers.  Filter plotting (``:190-385``) is not rebuilt.
 import numpy as np
 import torch
 
+from . import _native
 from . import gnn_layers as gnn
 from . import healpix
 from . import healpy_layers as hp_nn
+from . import utils
+
+
+class _DeviceGraphs:
+    """The graphs of one ``HealpyGCNN(build="device")``: one per (nside, pixel set), built on first use and shared by every layer
+    of the model at that resolution -- the symmetrised graph, its Laplacian table, lmax and the rescaled tables per scale (0.75 for
+    ``Chebyshev`` and ``Bernstein``, 1 for ``Monomial``: they share the column table)."""
+
+    class _Graph:
+        def __init__(self, nside, indices, n_neighbors, mode, device):
+            self.graph = healpix.healpix_graph_device(nside, indices, n_neighbors, mode, device=device)
+            self._ell = self._lmax = self._tables = self._cols_host = None
+            self._prepared = {}
+
+        def _laplacian(self):
+            if self._ell is None:
+                self._ell = self.graph.laplacian_ell()
+            return self._ell
+
+        @property
+        def nnz(self):
+            """Entries of the Laplacian (the graph's edges and the diagonal): what the host path reads as ``L.nnz`` for
+            ``n_matmul_splits``."""
+            return self.graph.nnz + self.graph.M
+
+        def prepared(self, scale):
+            """(cols int32, vals float32, lmax) for ``from_prepared_ell``, as host arrays: one ``vals`` per scale, one ``cols`` and
+            one lmax (the first call's: one eigen-solve per graph) for all of them."""
+            if scale not in self._prepared:
+                cols, vals = self._laplacian()
+                # (through the module attribute: the one place the model takes lmax from)
+                _, v32, self._lmax = utils.prepare_ell(cols, vals, scale, lmax=self._lmax)
+                if self._cols_host is None:
+                    self._cols_host = np.ascontiguousarray(cols.cpu().numpy(), dtype=np.int32)
+                self._prepared[scale] = (self._cols_host, np.ascontiguousarray(v32.cpu().numpy(), dtype=np.float32), self._lmax)
+            return self._prepared[scale]
+
+        def tables(self):
+            if self._tables is None:
+                self._tables = healpix.healpix_adjacency_tables(None, graph=self.graph)
+            return self._tables
+
+    def __init__(self, n_neighbors, mode):
+        _native.require_gpu()
+        self.n_neighbors, self.mode = n_neighbors, mode
+        self.device = torch.device("cuda", torch.cuda.current_device())
+        self._graphs = {}
+
+    def get(self, nside, indices):
+        ind = np.ascontiguousarray(np.asarray(indices).reshape(-1), dtype=np.int64)
+        key = (int(nside), ind.shape[0], ind.tobytes() if ind.shape[0] != healpix.nside2npix(nside) else None)
+        if key not in self._graphs:
+            self._graphs[key] = self._Graph(int(nside), ind, self.n_neighbors, self.mode, self.device)
+        return self._graphs[key]
 
 
 class HealpyGCNN(torch.nn.Sequential):
     """A graph convolutional network on a (partial) HEALPix map in NEST ordering."""
 
     def __init__(self, nside, indices, layers, n_neighbors=8, max_batch_size=None, initial_Fin=None,
-                 graph_mode="knn"):
+                 graph_mode="knn", build="host"):
         """
         :param nside: nside of the input maps
         :param indices: sorted NEST pixel ids of the input maps
@@ -30,7 +85,18 @@ class HealpyGCNN(torch.nn.Sequential):
             matmul from them (``:125-134``); the same number is computed and passed on, the HIP kernels ignore it
         :param graph_mode: "knn" (what the reference builds) or "grid" (fixed 8-neighbour stencil) -- not a
             reference argument
+        :param build: where the graphs are built -- not a reference argument.  "host" (default): ``healpix.healpix_laplacian``
+            (a k-d tree over all pixel centres), ARPACK's ``eigsh`` at machine precision and ``utils.csr_to_ell``, once per graph
+            layer: minutes at nside 512, hours at nside 1024.  "device": the graph of one (nside, pixel set) is built ONCE per
+            model on the current HIP device (``healpix.healpix_graph_device``: the HIP k-NN kernel, torch operators behind
+            it) and shared by every layer at that resolution; lmax comes from ``utils.prepare_ell`` (64 Lanczos steps), the layers from
+            ``from_prepared_ell`` -- they have ``L = None`` (a ``Healpy_Transformer`` layer ``A = None``).  A device-built network
+            is NOT bit-identical to a host-built one: lmax carries the Lanczos error (about 1e-4 relative, below ARPACK's value),
+            and where the k-th nearest neighbour is tied (mirror pairs of pixels) the kernel and the k-d tree may keep different
+            members of the pair -- both are correct k-NN graphs.  Anything else raises ValueError
         """
+        if build not in ("host", "device"):
+            raise ValueError(f"build must be \"host\" or \"device\", got <{build}>")
         if n_neighbors not in [8, 20, 40, 60]:
             raise NotImplementedError(
                 f"The requested number of neighbors {n_neighbors} is nor supported. Choose either 8, 20, 40 or 60.")
@@ -58,8 +124,25 @@ class HealpyGCNN(torch.nn.Sequential):
                                  "indices compatible...")
         layers_use = []
         current_nside, current_indices, current_Fin = nside_in, indices, initial_Fin
+        graphs = _DeviceGraphs(n_neighbors, graph_mode) if build == "device" else None
         for layer in layers:
-            if isinstance(layer, (hp_nn.HealpyChebyshev, hp_nn.HealpyMonomial, hp_nn.Healpy_ResidualLayer)):
+            if graphs is not None and isinstance(layer, (hp_nn.HealpyChebyshev, hp_nn.HealpyMonomial, hp_nn.Healpy_ResidualLayer,
+                                                         hp_nn.Healpy_Transformer)):
+                g = graphs.get(current_nside, current_indices)
+                if isinstance(layer, hp_nn.Healpy_Transformer):
+                    layers_use.append(layer._get_layer_prepared(*g.tables()))
+                else:
+                    cls = layer._layer_cls
+                    if cls is None:
+                        raise IOError(f"Layertype not understood: {layer.layer_type}")
+                    cols, vals, lmax = g.prepared(cls._scale)
+                    splits = 1
+                    if max_batch_size is not None and current_Fin is not None:
+                        while not (max_batch_size * current_Fin % splits == 0
+                                   and splits >= max_batch_size * current_Fin * g.nnz / 2**31):
+                            splits += 1
+                    layers_use.append(layer._get_layer_prepared(cols, vals, lmax, splits))
+            elif isinstance(layer, (hp_nn.HealpyChebyshev, hp_nn.HealpyMonomial, hp_nn.Healpy_ResidualLayer)):
                 L = healpix.healpix_laplacian(current_nside, indices=current_indices, n_neighbors=n_neighbors,
                                               mode=graph_mode)
                 if max_batch_size is not None and current_Fin is not None:
@@ -95,6 +178,7 @@ class HealpyGCNN(torch.nn.Sequential):
         self.layers_in, self.layers_use = layers, layers_use
         self.n_neighbors = n_neighbors
         self.reduction_fac = reduction_fac
+        self.build_mode = build
         self._warned_training = False  # (forward warns once about train() mode with the default training=False)
 
     @staticmethod

@@ -9,7 +9,7 @@ from scipy.sparse.linalg import eigsh
 from .healpix import extend_indices  # noqa: F401  (same public name as utils.py:9)
 
 __all__ = ["extend_indices", "rescale_L", "prepare_L", "csr_to_ell", "split_sparse_dense_matmul", "lanczos_lmax",
-           "rescale_ell", "adjacency_to_ell"]
+           "rescale_ell", "adjacency_to_ell", "prepare_ell"]
 
 
 def rescale_L(L, lmax=2, scale=1):
@@ -124,6 +124,36 @@ def rescale_ell(cols, vals, lmax, scale=0.75):
 
         return out.to(torch.float32)
     return out.astype(np.float32)
+
+
+def prepare_ell(cols, vals, scale, lmax=None, iters=64):
+    """``prepare_L`` for a Laplacian already in the padded-ELL layout of ``csr_to_ell``, as torch tensors (what
+    ``healpix.healpix_laplacian_ell`` returns: float64 values, the diagonal among the row's ascending columns, padding
+    (col = row, val = 0)): -> (cols, vals float32 on the same device, lmax), what ``Chebyshev.from_prepared_ell`` takes.
+
+    ``lmax=None``: 1.02 * ``lanczos_lmax`` (``iters`` steps) on a plan of the matrix, on the tensors' HIP device -- not ARPACK's
+    eigenvalue: the Lanczos value lies below it, by about 1e-4 relative at most, and the rescaled values move by as much.  A
+    number is used as given.  Then ``rescale_L`` with ``scale``: vals * (2 scale / lmax), minus 1 on the diagonal, float64 until
+    the final cast."""
+    import torch
+
+    from . import _native
+
+    if cols.dim() != 2 or cols.shape != vals.shape:
+        raise ValueError("ELL arrays must have shape [M, W]")
+    if lmax is None:
+        _native.require_gpu()
+        index = vals.device.index if vals.is_cuda else torch.cuda.current_device()
+        plan = _native.LaplacianPlan(cols.cpu().numpy(), vals.to(torch.float32).cpu().numpy(), device=index)
+        try:
+            lmax = 1.02 * lanczos_lmax(plan, iters=iters)
+        finally:
+            plan.close()
+    lmax = float(lmax)
+    own = cols == torch.arange(cols.shape[0], dtype=cols.dtype, device=cols.device)[:, None]
+    diag = own & (torch.cumsum(own, dim=1) == 1)  # (the first col = row of a row: the padding behind it is col = row too)
+    out = vals.to(torch.float64) * (2.0 * scale / lmax)
+    return cols, torch.where(diag, out - 1.0, out).to(torch.float32), lmax
 
 
 def lanczos_lmax(plan, iters=64, seed=0):

@@ -423,6 +423,24 @@ int dsph_healpix_pool_backward(const float* x, const float* dy, float* dx, int64
  * Only enqueues on `hip_stream`. */
 int dsph_healpix_reorder(const float* x, float* y, int64_t N, int32_t nside, int32_t F, int32_t to_nest, int device, void* hip_stream);
 
+/* The k nearest pixels of every pixel of a (partial) HEALPix map in NEST order (plan-free; csrc/healpix_knn.hip).
+ * Replaces: the k-d tree over all pixel centres behind the graphs of HealpyGCNN (reference healpy_networks.py:110-118 asks the
+ * pygsp fork for SphereHealpix(k = n_neighbors); healpix.healpix_graph(mode="knn") here), for graphs built on the device.
+ *   indices  device int64 [M], sorted NEST ids of the set; NULL: the full sky, M = 12 nside^2 and row = NEST id
+ *   lut      device int32 [12 nside^2], NEST id -> row of the set or -1; NULL exactly when indices is
+ *   nbr      device int32 [M, k]   rows of the k nearest other pixels of the set, ascending by (d2, row)
+ *   d2       device float64 [M, k] their squared chord distances between pixel centres (the geometry of healpix.pix2vec)
+ *   ok       device uint8 [M]      1: the row is guaranteed; 0: the search window held fewer than k pixels of the set, or the k-th
+ *                                  distance found is not below the radius the window provably covers -- the row's contents are then
+ *                                  unspecified and the caller completes it.  On the full sky every row comes out 1 for k <= 60.
+ * One wave per pixel, candidates from a window of rings and ring positions held in registers, k rounds of a wave-wide arg-min;
+ * float64 throughout; no workspace, no atomics, one writer per element.
+ * nside a power of two, 1 <= nside <= 8192 (pixel indices are int32; DSPH_E_UNSUPPORTED beyond), 1 <= k <= 64 (DSPH_E_UNSUPPORTED
+ * beyond), k < M <= 12 nside^2.  Bad arguments (a required pointer NULL, indices without lut or lut without indices, nside not a
+ * power of two, k < 1, M <= k, M != 12 nside^2 without indices): DSPH_E_BADARG before any launch.  Only enqueues on `hip_stream`. */
+int dsph_healpix_knn(int32_t nside, int32_t k, const int64_t* indices, const int32_t* lut, int64_t M, int32_t* nbr, double* d2,
+                     uint8_t* ok, int device, void* hip_stream);
+
 /* Attention over the edges of the pixel graph (plan-free; csrc/nbr_attention.hip).
  * Replaces: gnn_transformers.scaled_dot_product_sparse_attention (reference gnn_transformers.py:54-106: three embedding lookups that
  * materialise q, k, v per edge, exp, two segment sums) and the split_heads transposes around it (:189-196, :225-231).
