@@ -113,6 +113,9 @@ SIGNATURES = {
     "dsph_healpix_pool_backward": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i32, _c_i32, _c_i32, ctypes.c_int, _c_vp]),
     "dsph_healpix_reorder": (ctypes.c_int, [_c_vp, _c_vp, _c_i64, _c_i32, _c_i32, _c_i32, ctypes.c_int, _c_vp]),
     "dsph_healpix_knn": (ctypes.c_int, [_c_i32, _c_i32, _c_vp, _c_vp, _c_i64, _c_vp, _c_vp, _c_vp, ctypes.c_int, _c_vp]),
+    "dsph_healpix_disc_count": (ctypes.c_int, [_c_i32, ctypes.c_double, _c_vp, _c_vp, _c_i64, _c_vp, _c_vp, ctypes.c_int, _c_vp]),
+    "dsph_healpix_gauss_table": (ctypes.c_int, [_c_i32, _c_i32, ctypes.c_double, ctypes.c_double, _c_vp, _c_vp, _c_i64, _c_vp, _c_vp, _c_vp, _c_vp,
+                                                 ctypes.c_int, _c_vp]),
     "dsph_residual_epilogue": (ctypes.c_int, [_c_vp, _c_vp, _c_i64, ctypes.c_float, _c_i32, _c_i32, ctypes.c_int, _c_vp]),
     "dsph_nbr_attention_forward": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, _c_i64, _c_vp, _c_vp, _c_vp, _c_i32, _c_i64, _c_i64, _c_i32, _c_i32,
                                                    ctypes.c_int, _c_vp]),
@@ -670,6 +673,117 @@ def healpix_knn(nside, k, indices=None, lut=None, device=None, out=None):
     rc = lib().dsph_healpix_knn(nside, k, _ptr(indices), _ptr(lut), M, _ptr(nbr), _ptr(d2), _ptr(ok), dev.index, _stream_ptr(dev))
     check(rc, "dsph_healpix_knn")
     return nbr, d2, ok
+
+DISC_MAX_NSIDE = 8192  # dsph_healpix_disc_count / dsph_healpix_gauss_table keep pixel indices in int32
+DISC_MAX_W = 512  # ... and select the entries of a row in the LDS of one workgroup
+
+
+def _disc_set(what, nside, indices, lut, device):
+    """The pixel-set arguments the two disc entry points share, checked: -> (device, M)."""
+    import torch
+
+    if nside < 1 or nside & (nside - 1):
+        raise ValueError(f"{what}: nside = {nside} is not a power of two >= 1")
+    if nside > DISC_MAX_NSIDE:
+        raise ValueError(f"{what}: nside = {nside} is beyond the kernel's limit of {DISC_MAX_NSIDE} (int32 pixel indices)")
+    npix = 12 * nside * nside
+    if (indices is None) != (lut is None):
+        raise ValueError(f"{what}: indices and lut come together (both None: the full sky)")
+    if indices is not None:
+        if not (isinstance(indices, torch.Tensor) and indices.dtype == torch.int64 and indices.dim() == 1 and indices.is_contiguous()):
+            raise ValueError(f"{what}: indices must be a contiguous int64 tensor [M]")
+        if not (isinstance(lut, torch.Tensor) and lut.dtype == torch.int32 and lut.dim() == 1 and lut.is_contiguous()
+                and lut.shape[0] == npix):
+            raise ValueError(f"{what}: lut must be a contiguous int32 tensor of 12 nside^2 = {npix} entries")
+        if lut.device != indices.device:
+            raise ValueError(f"{what}: lut lives on {lut.device}, indices on {indices.device}")
+        if device is not None and torch.device(device) != indices.device:
+            raise ValueError(f"{what}: indices live on {indices.device}, device = {device}")
+        dev, M = indices.device, int(indices.shape[0])
+    else:
+        dev, M = torch.device("cuda" if device is None else device), npix
+    if M < 1 or M > npix or M >= 2**31:
+        raise ValueError(f"{what}: M = {M} rows, a map of nside {nside} has 1 .. {min(npix, 2**31 - 1)}")
+    return dev, M
+
+
+def _disc_out(what, out, specs, dev):
+    """``out`` (or fresh tensors) for the (name, dtype, shape) of ``specs``, checked; a spec whose name is None stays None."""
+    import torch
+
+    if out is None:
+        out = tuple(None if name is None else torch.empty(shape, dtype=dt, device=dev) for name, dt, shape in specs)
+    if len(out) != len(specs):
+        raise ValueError(f"{what}: out takes {len(specs)} tensors")
+    for t, (name, dt, shape) in zip(out, specs):
+        if name is None:
+            if t is not None:
+                raise ValueError(f"{what}: out holds a tensor that was not asked for")
+            continue
+        if not (isinstance(t, torch.Tensor) and t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous() and t.device == dev):
+            raise ValueError(f"{what}: out {name} must be a contiguous {dt} tensor of shape {shape} on {dev}")
+    return tuple(out)
+
+
+def healpix_disc_count(nside, r2, indices=None, lut=None, device=None, out=None):
+    """How many pixels of the set lie within the squared chord ``r2`` of every pixel of a HEALPix map in NEST order, the pixel
+    itself included (``dsph_healpix_disc_count``) -> ``(count int32 [M], ok uint8 [M])`` on ``device``.
+
+    ``r2 = (2 sin(rho / 2))^2`` for a disc of radius ``rho <= pi``.  ``indices``, ``lut``: as for ``healpix_knn`` (the ids in any
+    order).  A row with ``ok = 0`` is one whose window could not guarantee the count; the caller counts it.  ``out``: the two
+    tensors to write into.  The arguments are checked before the library or the GPU is touched."""
+    import torch
+
+    what = "healpix_disc_count"
+    nside, r2 = int(nside), float(r2)
+    dev, M = _disc_set(what, nside, indices, lut, device)
+    if not 0.0 <= r2 <= 4.0:
+        raise ValueError(f"{what}: r2 = {r2} is not the squared chord of a radius in [0, pi]")
+    if dev.type != "cuda":
+        raise ValueError(f"{what} works on a HIP device")
+    require_gpu()
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    count, ok = _disc_out(what, out, (("count", torch.int32, (M,)), ("ok", torch.uint8, (M,))), dev)
+    rc = lib().dsph_healpix_disc_count(nside, r2, _ptr(indices), _ptr(lut), M, _ptr(count), _ptr(ok), dev.index, _stream_ptr(dev))
+    check(rc, "dsph_healpix_disc_count")
+    return count, ok
+
+
+def healpix_gauss_table(nside, W, sigma_rad, rho, indices=None, lut=None, device=None, want_raw=False, out=None):
+    """The finished kernel table of ``HealpySmoothing`` (``dsph_healpix_gauss_table``) -> ``(cols int32 [M, W], vals float32
+    [M, W], raw float32 [M, W] or None, ok uint8 [M])`` on ``device``.
+
+    A row holds the ``W`` nearest pixels of the set, the pixel itself included, selected by (squared chord, row) ascending, its
+    columns ascending; ``vals`` the Gaussian weights of standard deviation ``sigma_rad`` normalised to sum 1, ``raw`` (with
+    ``want_raw``) the weights before the normalisation.  ``rho``: the radius the search window must cover (the radius ``W`` was
+    counted for).  A row with ``ok = 0`` is the caller's to complete.  ``out``: the four tensors to write into (raw None without
+    ``want_raw``).  The arguments are checked before the library or the GPU is touched."""
+    import torch
+
+    what = "healpix_gauss_table"
+    nside, W, sigma_rad, rho = int(nside), int(W), float(sigma_rad), float(rho)
+    dev, M = _disc_set(what, nside, indices, lut, device)
+    if W < 1:
+        raise ValueError(f"{what}: W = {W} entries per row, must be at least 1")
+    if W > DISC_MAX_W:
+        raise ValueError(f"{what}: W = {W} entries per row, the kernel takes 1 .. {DISC_MAX_W}")
+    if M < W:
+        raise ValueError(f"{what}: a set of M = {M} pixels has no rows of W = {W} (M >= W is required)")
+    if not (sigma_rad > 0.0 and 0.0 < rho <= np.pi):
+        raise ValueError(f"{what}: sigma_rad = {sigma_rad}, rho = {rho}: sigma_rad > 0 and 0 < rho <= pi are required")
+    if dev.type != "cuda":
+        raise ValueError(f"{what} works on a HIP device")
+    require_gpu()
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    specs = (("cols", torch.int32, (M, W)), ("vals", torch.float32, (M, W)), ("raw" if want_raw else None, torch.float32, (M, W)),
+             ("ok", torch.uint8, (M,)))
+    cols, vals, raw, ok = _disc_out(what, out, specs, dev)
+    rc = lib().dsph_healpix_gauss_table(nside, W, sigma_rad, rho, _ptr(indices), _ptr(lut), M, _ptr(cols), _ptr(vals), _ptr(raw),
+                                        _ptr(ok), dev.index, _stream_ptr(dev))
+    check(rc, "dsph_healpix_gauss_table")
+    return cols, vals, raw, ok
 
 
 def rows_layout(t):

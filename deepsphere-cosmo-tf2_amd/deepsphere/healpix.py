@@ -12,7 +12,8 @@ produced (L is an input of the layer, ``gnn_layers.py:17``), so nothing here is 
 the parity path; it only feeds tests and the benchmark with realistic matrices.
 
 The last part of the module builds the same graphs on the device (``healpix_graph_device``, ``healpix_laplacian_ell``,
-``healpix_adjacency_tables``): neighbours from the HIP kernel ``dsph_healpix_knn``, the rest as torch operators.
+``healpix_adjacency_tables``): neighbours from the HIP kernel ``dsph_healpix_knn``, the rest as torch operators; and the kernel
+table of ``HealpySmoothing`` (``gauss_table_device``, ``transpose_table``) from the kernels of ``csrc/healpix_disc.hip``.
 """
 
 import numpy as np
@@ -40,6 +41,8 @@ __all__ = [
     "healpix_graph_device",
     "healpix_laplacian_ell",
     "healpix_adjacency_tables",
+    "gauss_table_device",
+    "transpose_table",
     "cap_indices",
     "extend_indices",
     "superpixel_padding_mask",
@@ -832,3 +835,108 @@ def healpix_adjacency_tables(nside, indices=None, n_neighbors=8, mode="knn", kw=
         graph = healpix_graph_device(nside, indices, n_neighbors, mode, kw, device)
     nbr = graph.adjacency_table()
     return nbr, nbr
+
+
+# ----------------------------------------------------------------------------------------------
+# The kernel table of HealpySmoothing built on the device (csrc/healpix_disc.hip): what HealpySmoothing(build="device")
+# runs in place of its k-d tree, numpy sort and scipy transpose.
+# ----------------------------------------------------------------------------------------------
+
+
+def gauss_table_device(nside, indices, sigma_rad, n_sigma_support=3, device="cuda", want_raw=False):
+    """The table of ``HealpySmoothing`` for the pixels ``indices`` (unique NEST ids in any order; rows follow that order), on
+    the device: -> ``(cols int32 [M, W], vals float32 [M, W], raw float32 [M, W] or None, W, completed)``.
+
+    W is the largest number of pixels of the set within ``min(n_sigma_support * sigma_rad, pi)`` of a pixel
+    (``_native.healpix_disc_count``; rows it flags are counted by a ``cKDTree.query_ball_point``, those rows only).  A row holds
+    the W nearest pixels of the set, columns ascending, Gaussian weights normalised to sum 1 (``_native.healpix_gauss_table``;
+    rows it flags are completed on the host with the arithmetic of ``HealpySmoothing._build_tree`` / ``_finish_table``, those
+    rows only, and written into the device tables).  ``raw``: the weights before normalisation, with ``want_raw``.
+    ``completed``: the number of rows that needed the host in either kernel.
+
+    At the W-th neighbour HEALPix has exact ties; which member of a tied pair a row holds is not specified and need not be the
+    one the host-built layer picks."""
+    import torch
+
+    from . import _native
+
+    nside = _check_nside(nside)
+    npix = nside2npix(nside)
+    ind = np.ascontiguousarray(np.asarray(indices).reshape(-1), dtype=np.int64)
+    M = int(ind.shape[0])
+    if M < 1 or ind.min() < 0 or ind.max() >= npix or np.unique(ind).shape[0] != M:
+        raise ValueError(f"indices must be unique NEST ids in [0, {npix})")
+    sigma_rad = float(sigma_rad)
+    rho = min(sigma_rad * float(n_sigma_support), np.pi)
+    if not (sigma_rad > 0.0 and rho > 0.0):
+        raise ValueError("sigma_rad and n_sigma_support must be positive")
+    chord = 2.0 * np.sin(0.5 * rho)
+    dev = torch.device(device)
+    full = M == npix and bool(np.all(ind == np.arange(npix)))
+    pixel_set = (None, None) if full else _device_lut(nside, ind, dev)
+    dev = dev if full else None  # (a set brings its device along)
+    count, ok = _native.healpix_disc_count(nside, chord * chord, *pixel_set, device=dev)
+    bad_count = torch.nonzero(ok == 0).reshape(-1).cpu().numpy()
+    tree = vec = None
+    if bad_count.size:
+        from scipy.spatial import cKDTree
+
+        vec = pix2vec(nside, ind)
+        tree = cKDTree(vec)
+        lens = tree.query_ball_point(vec[bad_count], chord, return_length=True)
+        count[torch.as_tensor(bad_count, device=count.device)] = torch.as_tensor(np.asarray(lens, dtype=np.int32), device=count.device)
+    W = int(count.max())
+    if W > _native.DISC_MAX_W:
+        raise ValueError(f"the smoothing kernel has rows of W = {W} entries; the device build takes up to {_native.DISC_MAX_W} "
+                         f'(_native.DISC_MAX_W): build the layer with build="host"')
+    cols, vals, raw, ok = _native.healpix_gauss_table(nside, W, sigma_rad, rho, *pixel_set, device=dev, want_raw=want_raw)
+    bad = torch.nonzero(ok == 0).reshape(-1)
+    if bad.numel():
+        from scipy.spatial import cKDTree
+
+        rows = bad.cpu().numpy()
+        if tree is None:
+            vec = pix2vec(nside, ind)
+            tree = cKDTree(vec)
+        dist, nb = tree.query(vec[rows], k=W)
+        dist, nb = dist.reshape(-1, W), nb.reshape(-1, W)
+        theta = 2.0 * np.arcsin(np.minimum(0.5 * dist, 1.0))
+        v = np.exp(-0.5 / sigma_rad**2 * theta**2).astype(np.float32)  # (HealpySmoothing.kernel_func)
+        order = np.argsort(nb, axis=1, kind="stable")
+        nb, v = np.take_along_axis(nb, order, axis=1), np.take_along_axis(v, order, axis=1)
+        cols[bad] = torch.as_tensor(nb.astype(np.int32), device=cols.device)
+        vals[bad] = torch.as_tensor((v / v.sum(axis=1, dtype=np.float64, keepdims=True)).astype(np.float32), device=vals.device)
+        if raw is not None:
+            raw[bad] = torch.as_tensor(v, device=raw.device)
+        completed = int(np.union1d(rows, bad_count).shape[0])
+    else:
+        completed = int(bad_count.shape[0])
+    return cols, vals, raw, W, completed
+
+
+def transpose_table(cols, vals):
+    """The table of the transposed matrix in the layout of ``HealpySmoothing._transposed_tables``, with torch operators on the
+    tensors' device: zero values dropped, the columns of a row ascending, every row padded to the longest with (column = the row
+    itself, value = 0); -> (int32 [M, WT], float32 [M, WT]).  A permutation of the entries: no arithmetic on the values."""
+    import torch
+
+    M, W = cols.shape
+    dev = cols.device
+    c = cols.reshape(-1)
+    v = vals.reshape(-1)
+    r = torch.arange(M, dtype=torch.int32, device=dev).repeat_interleave(W)
+    keep = v != 0
+    if not bool(keep.all()):
+        c, v, r = c[keep], v[keep], r[keep]
+    # entries are filed by ascending row: a stable sort by column leaves the rows of a column ascending
+    c, order = torch.sort(c.to(torch.int64), stable=True)
+    v, r = v[order], r[order]
+    del order
+    lens = torch.bincount(c, minlength=M)
+    WT = max(int(lens.max()) if c.numel() else 0, 1)
+    slot = torch.arange(c.shape[0], dtype=torch.int64, device=dev) - (torch.cumsum(lens, 0) - lens)[c]
+    colsT = torch.arange(M, dtype=torch.int32, device=dev)[:, None].repeat(1, WT)
+    valsT = torch.zeros((M, WT), dtype=torch.float32, device=dev)
+    colsT[c, slot] = r
+    valsT[c, slot] = v.to(torch.float32)
+    return colsT, valsT

@@ -487,7 +487,7 @@ class HealpySmoothing(torch.nn.Module):
     sparse matmuls."""
 
     def __init__(self, nside, indices, nest=True, mask=None, fwhm=None, sigma=None, n_sigma_support=3, arcmin=True,
-                 per_channel_repetitions=None, data_path=None, max_batch_size=None):
+                 per_channel_repetitions=None, data_path=None, max_batch_size=None, build="host"):
         """
         :param nside: nside of the input maps
         :param indices: 1d array of the NEST pixel ids of the input maps
@@ -503,10 +503,22 @@ class HealpySmoothing(torch.nn.Module):
             ``val_coo<label>.npy``, the reference's files)
         :param max_batch_size: the reference sizes its sparse-matmul splits by it; the number is computed (``n_matmul_splits``),
             the kernel needs no split
+        :param build: not a reference argument -- where the kernel table is built.  "host" (default): a k-d tree over the pixel
+            centres, numpy and, for the backward, scipy.  "device": the HIP kernels of ``healpix.gauss_table_device`` on the
+            current device (needs a GPU), the transposed table from ``healpix.transpose_table`` on the device; the table never
+            visits the host.  Rows hold up to ``_native.DISC_MAX_W`` entries there; beyond, the constructor raises.  At a tied
+            ``max_neighbors``-th neighbour the two builds may pick different members of the tie; both tables are correct.  An
+            existing ``data_path`` cache is loaded whatever ``build`` says.
         """
         super().__init__()
         if not nest:
             raise NotImplementedError("only NEST ordering is supported")
+        if build not in ("host", "device"):
+            raise ValueError(f'build = {build!r}: "host" or "device"')
+        if build == "device":
+            _native.require_gpu()
+        self.build_mode = build
+        self.completed = 0  # rows of a device build that were completed on the host
         self.nside = nside
         self.indices = indices
         self.nest = nest
@@ -572,6 +584,16 @@ class HealpySmoothing(torch.nn.Module):
                 log.info(f"Successfully loaded sparse kernel indices and values from {self.data_path}")
             except FileNotFoundError:
                 ind_coo = val_coo = None
+        if ind_coo is None and build == "device":
+            dev = torch.device("cuda", torch.cuda.current_device())
+            cols, vals, raw, self.max_neighbors, self.completed = healpix.gauss_table_device(
+                self.nside, self.indices, self.sigma_rad, self.n_sigma_support, device=dev, want_raw=self.data_path is not None)
+            if self.data_path is not None:
+                self._store_kernel(cols.cpu().numpy(), raw.cpu().numpy())
+            del raw
+            self.register_buffer("cols", cols, persistent=False)
+            self.register_buffer("vals", vals, persistent=False)
+            return
         if ind_coo is None:
             cols, vals = self._build_tree()
             if self.data_path is not None:
@@ -654,6 +676,8 @@ class HealpySmoothing(torch.nn.Module):
 
     def _transposed_tables(self, device):
         """The table of the transposed matrix, every row padded to the longest with (column = the row itself, value = 0)."""
+        if self._tables_T is None and self.build_mode == "device":
+            self._tables_T = healpix.transpose_table(*self._tables(device))
         if self._tables_T is None:
             from scipy import sparse
 

@@ -441,6 +441,38 @@ int dsph_healpix_reorder(const float* x, float* y, int64_t N, int32_t nside, int
 int dsph_healpix_knn(int32_t nside, int32_t k, const int64_t* indices, const int32_t* lut, int64_t M, int32_t* nbr, double* d2,
                      uint8_t* ok, int device, void* hip_stream);
 
+/* The kernel matrix of HealpySmoothing built on the device (plan-free; csrc/healpix_disc.hip).
+ * Replaces: the BallTree / k-d tree over all pixel centres, its two queries per pixel and the numpy sort and normalisation behind
+ * HealpySmoothing (reference healpy_layers.py:640-720; HealpySmoothing._build_tree and _finish_table here).
+ * `indices`, `lut` and M as for dsph_healpix_knn (the ids need not be sorted: row i is the pixel indices[i]).
+ *
+ * dsph_healpix_disc_count: for every pixel of the set, how many pixels of the set lie within the squared chord r2 of it (<=, the
+ * pixel itself included).  r2 = (2 sin(rho / 2))^2 for a disc of radius rho <= pi, 0 <= r2 <= 4.
+ *   count    device int32 [M]
+ *   ok       device uint8 [M]   1: the count is guaranteed (every guard of the window lies beyond r2); 0: the caller counts that row
+ *
+ * dsph_healpix_gauss_table: for every pixel one finished row of the matrix: the W nearest pixels of the set, the pixel itself
+ * included, selected by (squared chord, row) ascending.
+ *   W          entries per row, 1 <= W <= 512 (DSPH_E_UNSUPPORTED beyond), W <= M
+ *   sigma_rad  standard deviation of the Gaussian in radians
+ *   rho        the radius the window must cover, 0 < rho <= pi (the kernel's window reaches 1.125 rho); a window of more than 2048
+ *              candidates: DSPH_E_UNSUPPORTED
+ *   cols     device int32 [M, W]    the columns of the row, ascending
+ *   vals     device float32 [M, W]  with theta = 2 asin(min(chord / 2, 1)): exp(-0.5 / sigma^2 * theta^2) in float64, rounded to
+ *                                   float32, divided by the float64 sum of the row's float32 values, rounded to float32
+ *   raw      device float32 [M, W]  the values before the division (the reference's cache files hold these); may be NULL
+ *   ok       device uint8 [M]       1: W pixels were found and the W-th squared chord lies below the smallest guard; 0: the row
+ *                                   is the caller's to complete (cols = -1 where fewer than W pixels were found)
+ * A pixel id outside [0, 12 nside^2): ok = 0, cols = -1, nothing read.  One workgroup per row, candidates and selection in LDS,
+ * float64 distances; no workspace, no global atomics, one writer per element; element offsets are 64-bit (M W may pass 2^31).
+ * nside a power of two, 1 <= nside <= 8192 (DSPH_E_UNSUPPORTED beyond).  Bad arguments (a required pointer NULL, indices without
+ * lut or the reverse, nside not a power of two, M < 1, M != 12 nside^2 without indices, W < 1, W > M, sigma_rad <= 0, rho or r2 out
+ * of range): DSPH_E_BADARG before any launch.  Both only enqueue on `hip_stream`. */
+int dsph_healpix_disc_count(int32_t nside, double r2, const int64_t* indices, const int32_t* lut, int64_t M, int32_t* count,
+                            uint8_t* ok, int device, void* hip_stream);
+int dsph_healpix_gauss_table(int32_t nside, int32_t W, double sigma_rad, double rho, const int64_t* indices, const int32_t* lut,
+                             int64_t M, int32_t* cols, float* vals, float* raw, uint8_t* ok, int device, void* hip_stream);
+
 /* Attention over the edges of the pixel graph (plan-free; csrc/nbr_attention.hip).
  * Replaces: gnn_transformers.scaled_dot_product_sparse_attention (reference gnn_transformers.py:54-106: three embedding lookups that
  * materialise q, k, v per edge, exp, two segment sums) and the split_heads transposes around it (:189-196, :225-231).

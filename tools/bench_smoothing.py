@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Time one pass of HealpySmoothing against two other routes over the same kernel table, on one GPU.
 
-    python tools/bench_smoothing.py [--nside 512] [--factor 1.5] [--batch 8] [--channels 4] [--reps 20] [--warmup 3] [--no-sparse]
+    python tools/bench_smoothing.py [--nside 512] [--factor 1.5] [--batch 8] [--channels 4] [--reps 20] [--warmup 3] [--no-sparse] [--build host|device]
 
 (layer) the layer's forward: one launch of dsph_ell_smooth (a group of lanes per row, the table read once per pass);
 (a) the only route the library had before: _native.cheb_step on a LaplacianPlan built from the same table (alpha = 1, no
@@ -67,16 +67,17 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--no-sparse", action="store_true", help="leave route (b) out")
+    ap.add_argument("--build", choices=("host", "device"), default="host", help="where the layer builds its table")
     args = ap.parse_args()
     _native.require_gpu()
     dev = torch.device("cuda", 0)
     npix = 12 * args.nside * args.nside
     t0 = time.time()
-    layer = HealpySmoothing(args.nside, np.arange(npix), sigma=args.factor * np.sqrt(4 * np.pi / npix), arcmin=False)
+    layer = HealpySmoothing(args.nside, np.arange(npix), sigma=args.factor * np.sqrt(4 * np.pi / npix), arcmin=False, build=args.build)
     M, W, N, C = npix, layer.max_neighbors, args.batch, args.channels
-    print(f"nside {args.nside}: M {M}, W {W}, table {8 * W * M / 1e9:.2f} GB, built on the host in {time.time() - t0:.0f} s", flush=True)
+    print(f"nside {args.nside}: M {M}, W {W}, table {8 * W * M / 1e9:.2f} GB, built on the {args.build} in {time.time() - t0:.0f} s", flush=True)
     t0 = time.time()
-    plan = _native.LaplacianPlan(layer.cols.numpy(), layer.vals.numpy(), device=0)
+    plan = _native.LaplacianPlan(layer.cols.cpu().numpy(), layer.vals.cpu().numpy(), device=0)
     print(f"route (a): plan of the same table created in {time.time() - t0:.0f} s", flush=True)
     cols, vals = layer._tables(dev)
     gen = torch.Generator(device=dev).manual_seed(0)
@@ -126,7 +127,7 @@ def main():
               f"peak {peak[name] / 2**20:8.1f} MiB beside a table of {table_bytes[name] / 1e9:.2f} GB")
     print(f"layer: {alg / 1e9:.3f} GB per pass, {rate / 1e12:.2f} TB/s = {rate / HBM_ACHIEVABLE:.2f} of {HBM_ACHIEVABLE / 1e12:.1f} TB/s")
     print("layer against: " + ", ".join(f"{n} {ms[n] / ms['layer']:.2f} x" for n in cases if n != "layer"))
-    print(json.dumps({"nside": args.nside, "M": M, "W": W, "batch": N, "channels": C, "ms": ms, "spread_ms": spread,
+    print(json.dumps({"nside": args.nside, "build": args.build, "M": M, "W": W, "batch": N, "channels": C, "ms": ms, "spread_ms": spread,
                       "peak_bytes": peak, "table_bytes": table_bytes, "bytes_per_pass": alg,
                       "hbm_fraction": rate / HBM_ACHIEVABLE, "agreement": agree}))
 
