@@ -204,6 +204,8 @@ int fused_prepare(const dsph_plan* plan, int32_t K, int32_t Fin, int32_t flags) 
       std::lock_guard<std::mutex> lock(fp->fork_mu);
       (void)side_stream_ready(plan, fp, nullptr, true);
     }
+    // (the K = 5 quad strips' image of L~ in the Chebyshev basis, the default one: a captured first forward finds it)
+    if (ftp.ok && qstrip_shape_ok(Fin, 64, K) && plan->opt.strip_form == 0) (void)qstrip_cimage(plan, ftp, true, nullptr);
     if (flags & DSPH_PREPARE_BACKWARD) {
       (void)get_tiles(plan, K - 1, true);
       (void)fused_symmetric(plan);  // (what the quad-strip weight gradient asks; the host arrays may be released below)
@@ -533,6 +535,11 @@ static int launch_strips(const FusedRequest& rq, const Route& rt, const WeightIm
     qs.nstrips = ft.q5.n; qs.Fin = rq.Fin; qs.Fout = rq.Fout;
     qs.f16 = rq.precision == DSPH_PREC_F16X3;
     qs.f16_xexp = plan->opt.f16_xexp;
+    qs.cimg = qstrip_cimage(plan, ft, base.cheb, rq.stream);
+    if (!qs.cimg && plan->opt.qstrip_image == 1 && ft.q5.cimg_failed) {
+      set_error("cheb_fused: DSPH_OPT_QSTRIP_IMAGE = on, and no memory for the image (%lld bytes)", (long long)ft.q5.cimg_rows * QS_CROWB);
+      return DSPH_E_HIP;
+    }
     qs.prep_weights = fused_images_claim(plan, rq.ws, IMG_QSTRIP);
     return launch_cheb_qstrip(qs, rq.stream);
   }

@@ -37,6 +37,41 @@ __global__ __launch_bounds__(256) void qstrip_wprep_kernel(const float* __restri
   }
 }
 
+// The packed image of L~ (QStripArgs::cimg): for every strip the ring rows of the steps y = ylo - 1 .. yhi + 6 -- every row a run
+// of steps can ask for, the rows dsph_plan_strip_rows answers for --, each as the H waves filed it from gvals8 / gdiag: QS_CROWB
+// bytes, [diagonal, directions 0..7][p][tile] floats, the values of the pixel in column clamp(xs + 4 p + tile, xlo, xhi) found
+// through the strip's table of tile bases; doubled for the Chebyshev recurrence (dbl).  A constant of the plan: built once (after
+// struct_patch_rows: it holds the patched class-T values), read by every step of every forward.  One block per image row.
+__global__ __launch_bounds__(256) void qstrip_cimage_kernel(const QStrip* __restrict__ strips, int nstrips, const int32_t* __restrict__ tab,
+                                                            const float* __restrict__ gvals8, const float* __restrict__ gdiag,
+                                                            int64_t rows, int dbl, float* __restrict__ out) {
+  for (int64_t r = blockIdx.x; r < rows; r += gridDim.x) {
+    int lo = 0, hi = nstrips;  // the strip of image row r: the last one that starts at or before it
+    while (hi - lo > 1) {
+      const int mid = (lo + hi) >> 1;
+      if ((int64_t)strips[mid].img <= r) lo = mid; else hi = mid;
+    }
+    const QStrip st = strips[lo];
+    const int y = st.ylo - 1 + (int)(r - st.img);
+    for (int e = threadIdx.x; e < QS_CROWB / 4; e += 256) {
+      const int v = e >> 6, p = (e >> 2) & 15, t = e & 3;
+      const int x = min(max(st.xs + 4 * p + t, st.xlo), st.xhi);
+      const size_t rid = (size_t)tab[st.tab + (y >> 4) * st.tws + (x >> 4)] + st_morton((unsigned)x & 15u, (unsigned)y & 15u);
+      const float c = v == 0 ? gdiag[rid] : gvals8[rid * 8 + (size_t)(v - 1)];
+      out[r * (QS_CROWB / 4) + e] = dbl ? c + c : c;
+    }
+  }
+}
+int64_t qstrip_cimage_rows(const QStrip& q) { return (int64_t)q.yhi - q.ylo + 8; }
+int launch_qstrip_cimage(const QStrip* d_strips, int nstrips, const int32_t* d_tab, const float* gvals8, const float* gdiag, int64_t rows,
+                         bool doubled, float* d_out, hipStream_t stream) {
+  if (rows <= 0) return DSPH_OK;
+  hipLaunchKernelGGL(qstrip_cimage_kernel, dim3((unsigned)std::min<int64_t>(rows, 1 << 16)), dim3(256), 0, stream, d_strips, nstrips, d_tab,
+                     gvals8, gdiag, rows, doubled ? 1 : 0, d_out);
+  DSPH_HIP(hipGetLastError());
+  return DSPH_OK;
+}
+
 bool qstrip_shape_ok(int32_t Fin, int32_t Fout, int32_t K) { return K == 5 && Fin == 64 && Fout == 64; }
 
 // The split rule of the quad-strip kernels (dsphere_common.h)
@@ -74,9 +109,13 @@ int launch_cheb_qstrip(const QStripLaunch& s, hipStream_t stream) {
   QStripArgs a;
   a.Fin = s.Fin;
   a.Fout = s.Fout;
+  a.cimg = s.cimg;
   const int grid = qtape_forward_args(a, s, QS_RUNIN);
-  void (*kern)(QStripArgs) = s.f16 ? (s.cheb ? cheb_qstrip5_kernel<true, true> : cheb_qstrip5_kernel<false, true>)
-                                   : (s.cheb ? cheb_qstrip5_kernel<true, false> : cheb_qstrip5_kernel<false, false>);
+  void (*kern)(QStripArgs);
+  if (s.cimg) kern = s.f16 ? (s.cheb ? cheb_qstrip5_kernel<true, true, true> : cheb_qstrip5_kernel<false, true, true>)
+                           : (s.cheb ? cheb_qstrip5_kernel<true, false, true> : cheb_qstrip5_kernel<false, false, true>);
+  else kern = s.f16 ? (s.cheb ? cheb_qstrip5_kernel<true, true, false> : cheb_qstrip5_kernel<false, true, false>)
+                    : (s.cheb ? cheb_qstrip5_kernel<true, false, false> : cheb_qstrip5_kernel<false, false, false>);
 #ifdef DSPH_QS_STAMPS
   static unsigned* d_stamps = nullptr;
   constexpr size_t NST = 8 * 4 * 10;

@@ -29,10 +29,17 @@
 // LDS (161,344 B): ring of 7 rows of x as bf16 hi | lo B-operand fragments (16 KiB per row: [32-channel block][hi | lo][tile]
 //   1 KiB fragments), hand-over 4 x 8 KiB, ring of 6 rows of L~ (2,304 B per row: the diagonal and the eight directions, each a
 //   [p][tile] vector: a lane reads the 16 bytes of its four pixels per direction, 9 reads per level-row), counters.
+// L~: a constant of the plan, so the ring rows are too: every strip's rows ylo - 1 .. yhi + 6 lie packed in an image built once per
+//   plan and basis (cheb_qstrip.hip, qstrip_cimage_kernel: the ring's layout, doubled for the Chebyshev basis) and a step's row comes
+//   in by LDS-DMA, one global_load_lds_dwordx4 of 36 lanes per H wave at the top of the step, from an address that is scalar
+//   arithmetic (QStrip::img + y - (ylo - 1)) -- template parameter CIMG.  Without the image (DSPH_OPT_QSTRIP_IMAGE off, no memory
+//   for it, a capture before it exists) the H waves gather the row from gvals8 / gdiag behind slot s2, double it and file it with
+//   4-byte stores, as they did before the image: the same floats in the ring, the same y bit for bit.
 // The strip record, the walk along the tape, the rows through the tables of tile bases, the hi | lo split and the ring row of L~
 //   are cheb_qtape.h's, shared with the K = 8 forward and the weight gradient; roles, LDS layout, chains and schedule are this file's.
-// x: fetched a step ahead and split into fragments at the end of the step -- by all eight waves, half a tile each (two 16-byte
-//   loads per lane), when level 1's matrix work runs on H (Chebyshev basis); else by the H wave of quarter q, tile q (four loads).  y: straight from the accumulators, 16 pixels x 64 contiguous bytes per instruction.
+// x: fetched a step ahead and split into fragments at the end of the step -- by the H wave of quarter q, tile q (four 16-byte loads
+//   per lane, asked for at the top of the step); without the image of L~ in the Chebyshev basis (level 1's matrix work on H, the
+//   gathered row's registers in use) by all eight waves, half a tile each (two loads), asked for behind slot s1 on H.  y: straight from the accumulators, 16 pixels x 64 contiguous bytes per instruction.
 #pragma once
 
 #include <type_traits>
@@ -54,6 +61,7 @@ struct QStripArgs {
   const unsigned char* wimg;  // qstrip_wprep_kernel: [role][oq][level of the role (3)][32-channel block][hi | lo][64 lanes][16 B]
   const float* gvals8;        // [rows][8] values of L~ by direction (kDirX / kDirY order)
   const float* gdiag;         // [rows]
+  const float* cimg;          // CIMG: the packed image of L~ (qstrip_cimage_kernel): [image row][QS_CROWB bytes], a strip's rows from QStrip::img on
   const QStrip* strips;
   const int32_t* tab;         // tile-base tables of the strips' rectangles (QStrip::tab, ::tws): row numbers of 16 x 16 Morton squares
   const int32_t* prefix;      // [nstrips + 1] rows of the strips before strip s (the "tape" of one map; prefix[nstrips] = all rows)
@@ -204,7 +212,10 @@ __device__ __forceinline__ void qs_unit(QRow& acc, const QRow& src, int e, const
 // multiplier of L~ in level j and the sign kept with the planes: as in the strip kernel (sp_mult / sp_wsign)
 __host__ __device__ constexpr float qs_wsign(bool cheb, int j) { return cheb && ((j & 3) >= 2) ? -1.f : 1.f; }
 
-template <bool CHEB, bool F16>
+// CIMG: the ring rows of L~ come ready-made from the packed image by LDS-DMA (QStripArgs::cimg); else the H waves gather them
+// from gvals8 / gdiag, double them and file them with 4-byte stores (the form before the image: kept as the comparison build
+// and for plans that do without the image's memory, DSPH_OPT_QSTRIP_IMAGE).  Both leave the same floats in the ring.
+template <bool CHEB, bool F16, bool CIMG>
 __global__ __launch_bounds__(QS_THREADS, 2) void cheb_qstrip5_kernel(QStripArgs a) {
   constexpr int K = 5, D = QS_D, RING = K + 2;
   // H1: level 1's matrix work (z_1 = x W_1) runs on the H wave, which otherwise reaches the step's barrier a fifth of a step
@@ -253,14 +264,18 @@ __global__ __launch_bounds__(QS_THREADS, 2) void cheb_qstrip5_kernel(QStripArgs 
   // qh = (lane >> 4) & 1, kk = lane >> 5; instruction i = 0, 1: the 16 bytes at offset (2 i + kk) 64 + (2 qh + h) 16 of the
   // pixel's 256: channels 32 i + 16 kk + 8 qh + 4 h ..+3 -> fragment (block i, tile xt), lane slot (pixel, 2 kk + qh), half h.
   // Who fetches x: the four H waves a tile each (X_BY_H), or all eight waves half a tile each.  With level 1's matrix work on H
-  // (H1) the H wave no longer has the time to spare: all eight is 2.4 % faster there (3.28 against 3.36 us per step on the
-  // probe); without H1 (monomial basis) the H waves alone are 0.6 % faster.  (-DDSPH_QS_XALL / -DDSPH_QS_XBYH: tuning)
+  // (H1) and the rows of L~ gathered by H (no image) the H wave has neither the time nor the registers to spare: all eight is 2.4 %
+  // faster there (3.28 against 3.36 us per step on the probe); without H1 (monomial basis) the H waves alone are 0.6 % faster.
+  // (-DDSPH_QS_XALL / -DDSPH_QS_XBYH: tuning)
 #if defined(DSPH_QS_XALL)
   constexpr bool X_BY_H = false;
 #elif defined(DSPH_QS_XBYH)
   constexpr bool X_BY_H = true;
 #else
-  constexpr bool X_BY_H = !H1;
+  // With the image of L~ (CIMG) the H wave has the registers again to ask for its tile of x at the top of the step beside level 1's
+  // weights (253 VGPRs), and the L waves -- the critical path -- issue no vector load at all: their memory counter holds y stores
+  // alone, which nothing waits for.  10.38 ms against 10.45 with all eight waves (c3, same box, alternating).
+  constexpr bool X_BY_H = !H1 || CIMG;
 #endif
   constexpr int XN = X_BY_H ? 4 : 2;  // 16-byte loads per lane and row
   // X_BY_H: the H wave of quarter q fetches tile q: lane: half h = lane & 1, pixel (lane >> 1) & 15, qh = lane >> 5;
@@ -344,6 +359,12 @@ __global__ __launch_bounds__(QS_THREADS, 2) void cheb_qstrip5_kernel(QStripArgs 
       for (int d = 0; d < 4; ++d) *reinterpret_cast<float*>(q + (unsigned)(1 + 4 * q4 + d) * 256u) = cv[d];
     }
     if (q4 == 2) *reinterpret_cast<float*>(q) = cd;
+  };
+  // CIMG: the H wave of quarter oq moves bytes [576 oq, 576 oq + 576) of the row, 36 lanes x 16 bytes, into the ring slot; the wave
+  // waits for it (qt_wait_vm) in front of the step's barrier, which publishes the row as it published the stores
+  const unsigned c_voff = (unsigned)oq * (QS_CROWB / 4) + lane16;
+  auto cdma = [&](int slot, const unsigned char* crow) __attribute__((always_inline)) {
+    qt_cdma(crow, c_voff, __builtin_amdgcn_readfirstlane((unsigned)LDS_C + (unsigned)slot * QS_CROWB + (unsigned)oq * (QS_CROWB / 4)), lane);
   };
   constexpr bool C_OFF = (QS_ABL & 1024) != 0;
   auto clo_read = [&](int slot) __attribute__((always_inline)) -> QCoefLo { return qt_clo_read<C_OFF>(smem + LDS_C, slot, p); };
@@ -439,18 +460,24 @@ __global__ __launch_bounds__(QS_THREADS, 2) void cheb_qstrip5_kernel(QStripArgs 
           for (int t = 0; t < 4; ++t) R[i][s].t[t] = qs_f4{0.f, 0.f, 0.f, 0.f};
       int ytop = st.y0 - D, slot_top = 0, cs_top = 0;
       qt_step_barrier();  // (the previous item's last reads of the rings)
+      // (CIMG: the image row of step y is row img + y - (ylo - 1) of the image: wave-uniform, stepped with the row)
+      const unsigned char* crow = CIMG ? reinterpret_cast<const unsigned char*>(a.cimg) + (size_t)(st.img + (ytop - st.ylo)) * QS_CROWB : nullptr;
       {
         qs_f4 cv, xv[XN];
         float cd;
-        cfetch(qt_row_in(st, tab_lane(st, ciC, ytop - 1), mXc, ytop - 1), cv, cd);
+        if (CIMG) { cdma(CRING - 1, crow); crow += QS_CROWB; }
+        else cfetch(qt_row_in(st, tab_lane(st, ciC, ytop - 1), mXc, ytop - 1), cv, cd);
         xfetch(xmap, qt_row_in(st, tab_lane(st, ciF, ytop), mXf, ytop), xv);
-        cw_wait(cv, cd);
-        cstore(CRING - 1, cv, cd);
+        if (!CIMG) {
+          cw_wait(cv, cd);
+          cstore(CRING - 1, cv, cd);
+        }
         xw_wait(xv);
         xstore(0, xv);
+        if (CIMG) qt_wait_vm();
       }
       // the lane's tile bases of the rows the steps ask for: x of row ytop + 1, L~ of row ytop
-      unsigned bXf = tab_lane(st, ciF, ytop + 1), bXc = tab_lane(st, ciC, ytop);
+      unsigned bXf = tab_lane(st, ciF, ytop + 1), bXc = CIMG ? 0u : tab_lane(st, ciC, ytop);
       unsigned myX = my_of(ytop + 1), myC = my_of(ytop);
       qt_step_barrier();
       auto step = [&](auto ph_c) __attribute__((always_inline)) {
@@ -471,9 +498,11 @@ __global__ __launch_bounds__(QS_THREADS, 2) void cheb_qstrip5_kernel(QStripArgs 
         QS_STAMP_DECL
         QS_STAMP(0);
         qs_f4 xv[XN];
-        constexpr bool XLATE = H1;  // (the row's registers are H1's weights' in the slots s0, s1: requested behind s1 instead)
+        constexpr bool XLATE = H1 && !X_BY_H;  // (the row's registers are H1's weights' in the slots s0, s1: requested behind s1 instead)
         if (myX == 0) bXf = tab_lane(st, ciF, ytop + 1);
-        if (myC == 0) bXc = tab_lane(st, ciC, ytop);
+        if (!CIMG && myC == 0) bXc = tab_lane(st, ciC, ytop);
+        // (CIMG: the row ytop of L~ on its way into the slot that row ytop - 6 left after the previous step's last read of it)
+        if (CIMG) { cdma(cs_top, crow); crow += QS_CROWB; }
         if (!XLATE) xfetch(xmap, bXf + (mXf | myX), xv);
         const unsigned f0 = (unsigned)slot_top * ROWB + lane16, f1 = (unsigned)slot_ix(1) * ROWB + lane16, f2 = (unsigned)slot_ix(2) * ROWB + lane16;
         const unsigned f3 = (unsigned)slot_ix(3) * ROWB + lane16;
@@ -500,7 +529,7 @@ __global__ __launch_bounds__(QS_THREADS, 2) void cheb_qstrip5_kernel(QStripArgs 
         QS_STAMP(2);
         // s2: z_2 -> b2[new] | b3[new] += b4[new]
         // (the row ytop of L~ is requested in the tail as well: its latency is H's to wait out, H reaches the barrier before L)
-        QS_CHAIN(R[0][L0], false, 2, f2, QS_UPR, { c2h = chi_read(cslot_ix(2)); cfetch(bXc + (mXc | myC), cv, cd); if (H1) { QS_FR0(f3) } },
+        QS_CHAIN(R[0][L0], false, 2, f2, QS_UPR, { c2h = chi_read(cslot_ix(2)); if (!CIMG) cfetch(bXc + (mXc | myC), cv, cd); if (H1) { QS_FR0(f3) } },
                  { QS_UNIT<false, N3>(R[1][L2], R[0][L2], qq, QS_HI(c3h)); })
         qs_settle<9>(R[0][L0]);
         qs_settle<1>(R[1][L2]);
@@ -527,9 +556,10 @@ __global__ __launch_bounds__(QS_THREADS, 2) void cheb_qstrip5_kernel(QStripArgs 
         ++handed;
         QS_STAMP(5);
         xw_wait(xv);  // (waits for the row of L~ as well: requests complete in order)
-        cw_wait(cv, cd);
+        if (CIMG) qt_wait_vm();  // (the row of L~ has landed: in order behind it, the x row's wait was for both already)
+        else cw_wait(cv, cd);
         QS_STAMP(6);
-        cstore(cs_top, cv, cd);
+        if (!CIMG) cstore(cs_top, cv, cd);
         xstore(snew, xv);
         QS_STAMP(7);
         slot_top = snew;

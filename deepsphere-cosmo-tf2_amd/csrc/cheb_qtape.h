@@ -37,7 +37,7 @@ struct QStrip {
   int32_t ylo, yhi;
   int32_t tab, tws;   // the rectangle's table of tile bases (offset into the kernel's `tab`) and its row stride: pixel (x, y) of the
                       // strip's plane is row tab[(y >> 4) * tws + (x >> 4)] + morton(x & 15, y & 15)
-  int32_t pad[1];
+  int32_t img;        // the strip's first row of the packed image of L~ (qstrip_cimage_kernel): the row of y is img + y - (ylo - 1)
 };
 
 // ---- the tape ---------------------------------------------------------------------------------------------------------------
@@ -78,7 +78,7 @@ __device__ __forceinline__ int qt_locate(const int32_t* prefix, const QStrip* st
      // table look-ups' branches then run on the scalar unit)
     const QStrip g = strips[lo];
 #define QS_U(f) st.f = __builtin_amdgcn_readfirstlane(g.f)
-    QS_U(x0); QS_U(w); QS_U(xs); QS_U(y0); QS_U(y1); QS_U(xlo); QS_U(xhi); QS_U(ylo); QS_U(yhi); QS_U(tab); QS_U(tws);
+    QS_U(x0); QS_U(w); QS_U(xs); QS_U(y0); QS_U(y1); QS_U(xlo); QS_U(xhi); QS_U(ylo); QS_U(yhi); QS_U(tab); QS_U(tws); QS_U(img);
 #undef QS_U
   }
   const int h = st.y1 - st.y0;
@@ -181,6 +181,13 @@ __device__ __forceinline__ void qt_cstore(unsigned char* ring, int slot, int p, 
   }
   if (q4 == 2) *reinterpret_cast<float*>(q) = cd;
 }
+// ... or a quarter of it straight from the packed image (cheb_qstrip.hip, qstrip_cimage_kernel) by LDS-DMA: `row` is the image
+// row (wave-uniform), voff the lane's byte in it, lds_dst the quarter's place in the ring slot (wave-uniform); 36 lanes x 16 bytes.
+// The issuing wave calls qt_wait_vm() in front of the barrier that publishes the row.
+__device__ __forceinline__ void qt_cdma(const unsigned char* row, unsigned voff, unsigned lds_dst, int lane) {
+  if (lane < QS_CROWB / 4 / 16) st_glds16_off(row, voff, lds_dst);
+}
+__device__ __forceinline__ void qt_wait_vm() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 // the lane's part of a ring row, and vector v of it (NOREAD: a tuning build's cut -- a constant instead of the LDS read)
 __device__ __forceinline__ const unsigned char* qt_crow(const unsigned char* ring, int slot, int p) {
   return ring + (unsigned)slot * QS_CROWB + (unsigned)p * 16u;

@@ -47,6 +47,13 @@ struct QStripSet {
   int64_t n_tiles = 0;            // tiles the strips take
   std::vector<QStrip> h_strips;   // host copies (dsph_plan_strip_pairs / _rows: what the seam tests read)
   std::vector<int32_t> h_tab;
+  // K = 5: the packed image of L~ (cheb_qstrip.hip, qstrip_cimage_kernel; QStrip::img is a strip's first row of it), one per basis
+  // ([0] as it stands: monomial, [1] doubled: Chebyshev), built by the first forward of the basis that finds none (qstrip_cimage:
+  // never inside a stream capture) or by dsph_plan_prepare (the Chebyshev one), freed with the tables and when
+  // DSPH_OPT_QSTRIP_IMAGE changes.  2,304 bytes per row: cimg_rows x 2,304 per basis.  Under FusedPlan::mu.
+  mutable float* d_cimg[2] = {nullptr, nullptr};
+  mutable bool cimg_failed = false;  // an allocation failed: not tried again on these tables
+  int64_t cimg_rows = 0;
 };
 
 struct FusedTiles {
@@ -139,6 +146,9 @@ struct FusedPlan {
 // run on them).  full: BFS tables of every tile (planes / weight-gradient modes of the BFS kernel); otherwise the tiles are
 // first classified and only the class-G ones (not a plain 2-D stencil square) get BFS tables.
 const FusedTiles& get_tiles(const dsph_plan* plan, int D, bool full = false);
+// The packed image of L~ of the K = 5 quad strips for a basis, built on first use; nullptr: the option says off, the stream is
+// being captured and there is none yet, or there is no memory for it (the kernel then gathers the rows itself: same result).
+const float* qstrip_cimage(const dsph_plan* plan, const FusedTiles& ft, bool cheb, hipStream_t stream);
 // L~ equal to its transpose, entry for entry (to fp32 rounding)
 bool fused_symmetric(const dsph_plan* plan);
 // steps of the busiest workgroup of the strip kernel for `steps` (one entry per pair) x N maps

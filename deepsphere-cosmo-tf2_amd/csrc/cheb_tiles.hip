@@ -21,8 +21,17 @@ static int template_width(int w) {
   return 0;
 }
 
+static void cimage_free(const QStripSet& s) {
+  for (float*& p : s.d_cimg) {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+  }
+  s.cimg_failed = false;
+}
+
 void FusedTiles::release() {
   for (void* p : dev) (void)hipFree(p);
+  cimage_free(q5);
   *this = FusedTiles();
 }
 
@@ -65,6 +74,39 @@ void fused_plan_invalidate(FusedPlan* fp) {
   std::lock_guard<std::mutex> lock(fp->mu);
   for (auto& kv : fp->by_depth) kv.second.release();
   fp->by_depth.clear();
+}
+
+// DSPH_OPT_QSTRIP_IMAGE changed: the images go (hipFree waits for the kernels that read them); the next forward decides anew
+void fused_cimage_drop(FusedPlan* fp) {
+  if (!fp) return;
+  std::lock_guard<std::mutex> lock(fp->mu);
+  for (auto& kv : fp->by_depth) cimage_free(kv.second.q5);
+}
+
+const float* qstrip_cimage(const dsph_plan* plan, const FusedTiles& ft, bool cheb, hipStream_t stream) {
+  const QStripSet& s = ft.q5;
+  if (plan->opt.qstrip_image == 2 || s.n == 0 || s.cimg_rows == 0) return nullptr;
+  FusedPlan* fp = plan->fused;
+  std::lock_guard<std::mutex> lock(fp->mu);
+  float*& img = s.d_cimg[cheb ? 1 : 0];
+  if (img || s.cimg_failed) return img;
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (stream && (hipStreamIsCapturing(stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone)) return nullptr;
+  void* p = nullptr;
+  if (hipMalloc(&p, (size_t)s.cimg_rows * QS_CROWB) != hipSuccess) {
+    (void)hipGetLastError();
+    s.cimg_failed = true;
+    return nullptr;
+  }
+  // (on the null stream and waited for: whichever stream the forwards run on finds the image complete)
+  if (launch_qstrip_cimage(s.d_strips, s.n, s.d_tab, fp->d_gvals8, fp->d_gdiag, s.cimg_rows, cheb, static_cast<float*>(p), nullptr) != DSPH_OK ||
+      hipStreamSynchronize(nullptr) != hipSuccess) {
+    (void)hipFree(p);
+    s.cimg_failed = true;
+    return nullptr;
+  }
+  img = static_cast<float*>(p);
+  return img;
 }
 
 // Class-T tiles: a tile whose own 256 rows are a 16x16 Morton square and whose D-ring region can be laid out as a
@@ -1030,6 +1072,14 @@ static bool upload(FusedTiles& ft, QStripSet& s) {
   std::vector<QStrip> strips = s.h_strips;
   std::vector<int32_t> prefix(1, 0), tab = s.h_tab;
   for (const QStrip& q : strips) prefix.push_back(prefix.back() + (q.y1 - q.y0));
+  // the strips' places in the packed image of L~ (K = 5): rows ylo - 1 .. yhi + 6 each, back to back in list order
+  int64_t img_rows = 0;
+  for (size_t i = 0; i < strips.size(); ++i) {
+    if (img_rows + qstrip_cimage_rows(strips[i]) > INT32_MAX) { img_rows = 0; break; }  // (no image: the kernel gathers)
+    strips[i].img = s.h_strips[i].img = (int32_t)img_rows;
+    img_rows += qstrip_cimage_rows(strips[i]);
+  }
+  s.cimg_rows = img_rows;
   s.n = (int)strips.size();
   s.tape_rows = prefix.back();
   tab.resize(tab.size() + 8, 0);  // (a lane's five tile columns are read by scalar loads from the strip's first column on: readable past the end)
@@ -1157,6 +1207,22 @@ int64_t fused_strip_rows(const dsph_plan* plan, int32_t K, int64_t strip, int64_
   }
   if (strip >= (int64_t)ft.h_pairs.size()) return -1;
   for (int64_t i = 0; i < n; ++i) rows[i] = (int64_t)st_morton((unsigned)xy[2 * i], (unsigned)xy[2 * i + 1]);
+  return n;
+}
+
+// the image rows of strip record `strip` of the K = 5 quad strips (dsph_plan_strip_image), copied to the host: returns the
+// floats of the strip's rows (also when cap is smaller: nothing is copied then), -1 when there is no image
+int64_t fused_strip_image(const dsph_plan* plan, int32_t basis, int64_t strip, float* out, int64_t cap) {
+  if (!plan->fused) return -1;
+  const FusedTiles& ft = get_tiles(plan, QS_D, false);
+  const QStripSet* s = ft.ok ? record_strips(plan, ft, 5) : nullptr;
+  if (!s || strip < 0 || strip >= (int64_t)s->h_strips.size()) return -1;
+  const float* img = qstrip_cimage(plan, ft, basis == DSPH_BASIS_CHEBYSHEV, nullptr);
+  if (!img) return -1;
+  const QStrip& q = s->h_strips[(size_t)strip];
+  const int64_t n = qstrip_cimage_rows(q) * (QS_CROWB / 4);
+  if (q.img < 0 || (int64_t)q.img + qstrip_cimage_rows(q) > s->cimg_rows) return -1;
+  if (n <= cap && hipMemcpy(out, img + (int64_t)q.img * (QS_CROWB / 4), (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess) return -1;
   return n;
 }
 

@@ -161,6 +161,15 @@ int dsph_plan_set_option(dsph_plan* p, int32_t option, int64_t value) {
       o.f16_xexp = (int)value;
       tables = false;
       break;
+    case DSPH_OPT_QSTRIP_IMAGE:
+      if (value < 0 || value > 2) { set_error("plan_set_option: DSPH_OPT_QSTRIP_IMAGE takes 0 (automatic), 1 (on), 2 (off)"); return DSPH_E_BADARG; }
+      o.qstrip_image = (int)value;
+      tables = false;
+      if (p->fused && o.qstrip_image != p->opt.qstrip_image) {  // (the tables stay; the images are rebuilt by the next forward that wants one)
+        DeviceGuard guard(p->device);
+        fused_cimage_drop(p->fused);
+      }
+      break;
     default: set_error("plan_set_option: unknown option %d", (int)option); return DSPH_E_BADARG;
   }
   if (tables && p->fused) {
@@ -187,6 +196,18 @@ int dsph_plan_strip_rows(const dsph_plan* p, int32_t K, int64_t strip, int64_t n
   if (!p || n < 0 || (n > 0 && (!xy || !rows))) { set_error("plan_strip_rows: bad arguments"); return DSPH_E_BADARG; }
   DeviceGuard guard(p->device);
   if (fused_strip_rows(p, K, strip, n, xy, rows) < 0) { set_error("plan_strip_rows: no strip record %lld for K = %d", (long long)strip, (int)K); return DSPH_E_UNSUPPORTED; }
+  return DSPH_OK;
+}
+
+int dsph_plan_strip_image(const dsph_plan* p, int32_t basis, int64_t strip, float* out, int64_t capacity, int64_t* n_floats) {
+  if (!p || !n_floats || capacity < 0 || (capacity > 0 && !out) || (basis != DSPH_BASIS_CHEBYSHEV && basis != DSPH_BASIS_MONOMIAL)) {
+    set_error("plan_strip_image: bad arguments");
+    return DSPH_E_BADARG;
+  }
+  DeviceGuard guard(p->device);
+  const int64_t n = fused_strip_image(p, basis, strip, out, capacity);
+  if (n < 0) { *n_floats = 0; set_error("plan_strip_image: no image of L~ for strip record %lld (no K = 5 quad strips, or DSPH_OPT_QSTRIP_IMAGE off)", (long long)strip); return DSPH_E_UNSUPPORTED; }
+  *n_floats = n;
   return DSPH_OK;
 }
 

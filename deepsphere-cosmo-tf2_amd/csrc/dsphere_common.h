@@ -48,6 +48,7 @@ struct PlanOptions {
   int strip_form = 0;        // DSPH_OPT_STRIP_FORM: 0 quad strips (cheb_qstrip_kernel.h), 1 strip pairs (cheb_strip_kernel.h)
   bool pack = true;          // DSPH_OPT_PACK: narrow layers run several maps per item / wave when the batch has more than one
   int f16_xexp = 0;          // DSPH_OPT_F16_XEXP: x enters the f16 split of DSPH_PREC_F16X3 times 2^f16_xexp (y times 2^-f16_xexp)
+  int qstrip_image = 0;      // DSPH_OPT_QSTRIP_IMAGE: the K = 5 quad strips' packed image of L~ (0 auto: wherever they run, 1 on, 2 off)
 };
 
 }  // namespace dsph
@@ -108,6 +109,8 @@ int64_t fused_strip_tiles(const dsph_plan* plan, int64_t N, int32_t Fin, int32_t
 int64_t fused_strip_pairs(const dsph_plan* plan, int32_t K, int32_t* out, int64_t cap);
 int64_t fused_strip_rows(const dsph_plan* plan, int32_t K, int64_t strip, int64_t n, const int32_t* xy, int64_t* rows);
 bool fused_strip_split(const dsph_plan* plan, int64_t N, int32_t* grid, int32_t* pieces, int32_t* wg_per_piece, int64_t* tape_rows);
+int64_t fused_strip_image(const dsph_plan* plan, int32_t basis, int64_t strip, float* out, int64_t cap);
+void fused_cimage_drop(FusedPlan* fp);
 // conv + HealpyPool(p = 1) in one forward: the pooled map (N, n_rows / 4, Fout) and the kind of reduction (1 max, 2 mean)
 struct FusedPool {
   float* y;
@@ -239,7 +242,13 @@ int64_t qtape_split(int num_cu, int64_t tape_rows, int64_t N, int64_t mean_heigh
 // K = 5, 64 -> 64 (cheb_qstrip.hip, round 5)
 struct QStripLaunch : QTapeLaunch {
   int32_t Fin, Fout;
+  const float* cimg = nullptr;  // the packed image of L~ for this basis (launch_qstrip_cimage; QStrip::img); null: the kernel gathers the rows itself
 };
+// the strips' ring rows of L~, packed once per plan and basis: QS_CROWB bytes per row, qstrip_cimage_rows rows per strip from its
+// QStrip::img on (cheb_qstrip.hip)
+int64_t qstrip_cimage_rows(const QStrip& q);
+int launch_qstrip_cimage(const QStrip* d_strips, int nstrips, const int32_t* d_tab, const float* gvals8, const float* gdiag, int64_t rows,
+                         bool doubled, float* d_out, hipStream_t stream);
 bool qstrip_shape_ok(int32_t Fin, int32_t Fout, int32_t K);
 size_t qstrip_wimg_bytes();
 int64_t qstrip_split(int num_cu, int64_t tape_rows, int64_t N, int64_t mean_height, int* grid, int* pieces, int* wg_per_piece);  // qtape_split with this kernel's run-in

@@ -28,6 +28,7 @@ OPT_STRIPS, OPT_STRUCT, OPT_TABLES, OPT_FORK, OPT_STRIP_MINROWS, OPT_SPLIT, OPT_
 OPT_PACK = 10
 OPT_STRIP_FORM = 11
 OPT_F16_XEXP = 12
+OPT_QSTRIP_IMAGE = 13  # the K = 5 quad strips' packed image of L~: 0 automatic (on), 1 on, 2 off
 STRIP_FORM_QUAD, STRIP_FORM_PAIRS = 0, 1
 STRIPS_AUTO, STRIPS_ALWAYS, STRIPS_NEVER = 0, 1, 2
 SPLIT_AUTO, SPLIT_ALWAYS, SPLIT_NEVER = 0, 1, 2
@@ -48,6 +49,7 @@ SIGNATURES = {
     "dsph_plan_strip_split": (ctypes.c_int, [_c_vp, _c_i64, ctypes.POINTER(_c_i32), ctypes.POINTER(_c_i32), ctypes.POINTER(_c_i32),
                                              ctypes.POINTER(_c_i64)]),
     "dsph_plan_strip_rows": (ctypes.c_int, [_c_vp, _c_i32, _c_i64, _c_i64, _c_vp, _c_vp]),
+    "dsph_plan_strip_image": (ctypes.c_int, [_c_vp, _c_i32, _c_i64, _c_vp, _c_i64, ctypes.POINTER(_c_i64)]),
     "dsph_plan_rows": (_c_i64, [_c_vp]),
     "dsph_plan_cols": (_c_i64, [_c_vp]),
     "dsph_plan_ell_width": (_c_i32, [_c_vp]),
@@ -291,6 +293,17 @@ class LaplacianPlan:
         check(lib().dsph_plan_strip_rows(self.handle, int(K), int(strip), int(xy.shape[0]), xy.ctypes.data, rows.ctypes.data),
               "dsph_plan_strip_rows")
         return rows
+
+    def strip_image(self, strip, basis=0):
+        """The packed image of L~ of K = 5 quad-strip record ``strip`` (``dsph_plan_strip_image``): a float32 array
+        [yhi - ylo + 8, 9, 16, 4] -- rows ylo - 1 .. yhi + 6, the diagonal and the eight directions, p, tile; ``basis`` 0: doubled
+        (Chebyshev), 1: as it stands (monomial)."""
+        n = _c_i64(0)
+        check(lib().dsph_plan_strip_image(self.handle, int(basis), int(strip), _c_vp(), 0, ctypes.byref(n)), "dsph_plan_strip_image")
+        out = np.zeros(int(n.value), np.float32)
+        check(lib().dsph_plan_strip_image(self.handle, int(basis), int(strip), out.ctypes.data, int(n.value), ctypes.byref(n)),
+              "dsph_plan_strip_image")
+        return out.reshape(-1, 9, 16, 4)
 
     def strip_split(self, N):
         """How a quad-strip forward of ``N`` maps cuts its work (``dsph_plan_strip_split``): (grid, pieces, workgroups per piece,

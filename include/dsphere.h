@@ -176,6 +176,17 @@ int dsph_plan_prepare_layer(dsph_plan* plan, int32_t K, int32_t Fin, int32_t Fou
  *                           f16 pairs and store y 2^-e (exact both ways); see DSPH_PREC_F16X3 for how to choose it.  Read when a
  *                           forward is enqueued: it may change between forwards (not while one is being enqueued on this plan). */
 #define DSPH_OPT_F16_XEXP 12
+/*   DSPH_OPT_QSTRIP_IMAGE   0 (default: automatic = on wherever the K = 5 quad strips run) / 1 on / 2 off: the quad-strip forward
+ *                           reads the values of L~ from an image packed once per plan and basis -- every strip's rows in the order
+ *                           the kernel's LDS ring holds them, moved in by LDS-DMA -- instead of gathering them from the
+ *                           direction-ordered copy in every step.  Same bits either way.  The image costs 2,304 bytes per strip
+ *                           row (rows ylo - 1 .. yhi + 6 of every strip): about 0.5 GB per basis at nside 1024, next to the
+ *                           0.45 GB of the direction-ordered copy that the other kernels keep using; it is built by
+ *                           dsph_plan_prepare (Chebyshev basis) or by the first forward of a basis outside a stream capture, and
+ *                           freed with the plan's tables and when this option changes.  0: a forward that finds no memory for the
+ *                           image, or is being captured before one exists, gathers; 1: no memory is an error (DSPH_E_HIP);
+ *                           2: never built (memory-tight callers, and the comparison build).  Does not drop the tables. */
+#define DSPH_OPT_QSTRIP_IMAGE 13
 int dsph_plan_set_option(dsph_plan* plan, int32_t option, int64_t value);
 
 int64_t dsph_plan_rows(const dsph_plan* plan);
@@ -230,6 +241,12 @@ int dsph_plan_strip_split(const dsph_plan* plan, int64_t N, int32_t* grid, int32
  * them; K = 5: y to [ylo - 1, yhi + 6] -- that kernel reads a row as it comes, a run of steps touches these rows of the ring
  * tiles, past the halo for nothing) into rows[i].  For the strip pairs (DSPH_OPT_STRIP_FORM 1) the plane is the virtual Z-order plane of the row index itself.) */
 int dsph_plan_strip_rows(const dsph_plan* plan, int32_t K, int64_t strip, int64_t n, const int32_t* xy, int64_t* rows);
+/* The packed image of L~ of K = 5 quad-strip record `strip` (DSPH_OPT_QSTRIP_IMAGE), for tests and tools: yhi - ylo + 8 rows, the
+ * rows y = ylo - 1 .. yhi + 6 of the strip's plane, 576 floats each: [v = 0 the diagonal, v = 1 + d direction d (W NW N NE E SE S
+ * SW)][p = 0..15][t = 0..3] = that value of L~ of the pixel (clamp(xs + 4 p + t, xlo, xhi), y), times two for
+ * basis = DSPH_BASIS_CHEBYSHEV.  *n_floats the strip's floats (also when capacity is smaller; nothing is copied then).  Builds
+ * the image of that basis if the plan has none yet; DSPH_E_UNSUPPORTED without quad strips or with the option off. */
+int dsph_plan_strip_image(const dsph_plan* plan, int32_t basis, int64_t strip, float* out, int64_t capacity, int64_t* n_floats);
 
 /* Bytes of scratch dsph_cheb_forward needs for this call shape (0 is possible). */
 size_t dsph_workspace_bytes(const dsph_plan* plan, int64_t N, int32_t Fin, int32_t Fout,

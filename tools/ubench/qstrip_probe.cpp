@@ -80,7 +80,19 @@ static double run(const Case& c, bool check, int reps) {
   int32_t* d_p;
   CK(hipMalloc(&d_p, prefix.size() * 4));
   CK(hipMemcpy(d_p, prefix.data(), prefix.size() * 4, hipMemcpyHostToDevice));
+  // the packed image of L~ (as cheb_tiles.hip lays it out: rows ylo - 1 .. yhi + 6 of every strip, back to back); QS_NOIMG=1: the
+  // kernel gathers the rows itself (the comparison build)
+  float* d_cimg = nullptr;
+  if (!getenv("QS_NOIMG")) {
+    int64_t rows = 0;
+    for (QStrip& q : strips) { q.img = (int32_t)rows; rows += qstrip_cimage_rows(q); }
+    CK(hipMemcpy(d_s, strips.data(), strips.size() * sizeof(QStrip), hipMemcpyHostToDevice));
+    CK(hipMalloc(&d_cimg, (size_t)rows * QS_CROWB));
+    if (launch_qstrip_cimage(d_s, (int)strips.size(), d_tab, d_g8, d_gd, rows, c.cheb, d_cimg, nullptr) != DSPH_OK) exit(1);
+    CK(hipDeviceSynchronize());
+  }
   QStripLaunch L;
+  L.cimg = d_cimg;
   L.prefix = d_p; L.tape_rows = prefix.back(); L.tab = d_tab;
   L.x = d_x; L.w = d_w; L.bias = d_b; L.y = d_y; L.wimg = d_img; L.strips = d_s; L.gvals8 = d_g8; L.gdiag = d_gd;
   L.x_rows = (int64_t)M; L.y_rows = (int64_t)M; L.N = N; L.nstrips = (int)strips.size(); L.Fin = F; L.Fout = F; L.act = DSPH_ACT_RELU;
@@ -148,7 +160,7 @@ static double run(const Case& c, bool check, int reps) {
     printf("check S %d N %d %s %s: max |err| %.3e of max |y| %.3e -> %.2e\n", S, N, c.cheb ? "chebyshev" : "monomial", c.f16 ? "f16x3" : "bf16x3", worst, ymax,
            worst / ymax);
   }
-  hipFree(d_g8); hipFree(d_gd); hipFree(d_x); hipFree(d_w); hipFree(d_b); hipFree(d_y); hipFree(d_img); hipFree(d_s);
+  hipFree(d_g8); hipFree(d_gd); hipFree(d_x); hipFree(d_w); hipFree(d_b); hipFree(d_y); hipFree(d_img); hipFree(d_s); hipFree(d_cimg); hipFree(d_tab); hipFree(d_p);
   return ms;
 }
 
