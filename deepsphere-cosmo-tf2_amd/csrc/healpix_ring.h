@@ -1,6 +1,7 @@
-// The RING-scheme geometry behind the neighbour searches (healpix_knn.hip, healpix_disc.hip): a ring's z, sin(theta) and phi step
-// in closed form (healpix.pix2vec), NEST id <-> (ring, position) by the (face, ix, iy) arithmetic of healpix.nest2ring / ring2nest,
-// the squared chord to a pixel centre, and the position of a ring nearest to a phi.  Host and device; float64 throughout.
+// The RING-scheme geometry behind the neighbour searches and the interpolation (healpix_knn.hip, healpix_disc.hip, healpix_interp.hip):
+// a ring's z, sin(theta) and phi step in closed form (healpix.pix2vec), NEST id <-> (ring, position) by the (face, ix, iy) arithmetic
+// of healpix.nest2ring / ring2nest, the squared chord to a pixel centre, the position of a ring nearest to a phi, and the ring above
+// a latitude.  Host and device; float64 throughout.
 #pragma once
 
 #include <cmath>
@@ -48,6 +49,23 @@ __host__ __device__ __forceinline__ KnnRing knn_ring(int32_t nside, int32_t ring
   g.step = (M_PI / 2) / (double)g.nr;
   return g;
 }
+// The ring above the latitude z (healpy's ring_above): the last ring whose centres lie at or north of z, 0 above the first ring;
+// the ring below it is that plus one, 4 nside below the last.  |z| <= 2/3: the belt's rings are equidistant in z; beyond: a cap
+// ring's z is 1 - nr^2 / (3 nside^2)
+__host__ __device__ __forceinline__ int32_t knn_ring_above(int32_t nside, double z) {
+  const double az = fabs(z);
+  if (az <= 2.0 / 3.0) return (int32_t)((double)nside * (2.0 - 1.5 * z));
+  const int32_t iring = (int32_t)((double)nside * sqrt(3.0 * (1.0 - az)));
+  return z > 0 ? iring : 4 * nside - iring - 1;
+}
+// RING index of a ring's first pixel (position 1), the `before` of healpix.nest2ring
+__host__ __device__ __forceinline__ int32_t knn_ring_first(int32_t nside, int32_t ring) {
+  if (ring < nside) return 2 * ring * (ring - 1);
+  if (ring > 3 * nside) { const int32_t nr = 4 * nside - ring; return 12 * nside * nside - 2 * (nr + 1) * nr; }
+  return 2 * nside * (nside - 1) + (ring - nside) * 4 * nside;
+}
+// healpy calls a ring "shifted" when its first centre sits half a step from phi = 0: the caps, and every other ring of the belt
+__host__ __device__ __forceinline__ int32_t knn_ring_shifted(const KnnRing& g) { return 1 - g.kshift; }
 __host__ __device__ __forceinline__ double knn_phi(const KnnRing& g, int32_t jp) {  // position jp = 1 .. 4 nr
   return ((double)jp - (double)(g.kshift + 1) * 0.5) * g.step;
 }

@@ -12,6 +12,6 @@ from . import healpix, utils  # noqa: F401
 from .gnn_layers import Bernstein, Chebyshev, GCNN_ResidualLayer, Monomial  # noqa: F401
 from .gnn_transformers import Graph_Transformer, Graph_ViT  # noqa: F401
 from .healpy_layers import (HealpyBernstein, HealpyChebyshev, HealpyMonomial, HealpyPool, HealpyPseudoConv,  # noqa: F401
-                            HealpyPseudoConv_Transpose, HealpyReorder, HealpySmoothing, Healpy_ResidualLayer,
+                            HealpyPseudoConv_Transpose, HealpyReorder, HealpyRotate, HealpySmoothing, Healpy_ResidualLayer,
                             Healpy_Transformer, Healpy_ViT)
 from .healpy_networks import HealpyGCNN  # noqa: F401

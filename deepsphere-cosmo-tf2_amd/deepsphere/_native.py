@@ -118,6 +118,8 @@ SIGNATURES = {
     "dsph_healpix_disc_count": (ctypes.c_int, [_c_i32, ctypes.c_double, _c_vp, _c_vp, _c_i64, _c_vp, _c_vp, ctypes.c_int, _c_vp]),
     "dsph_healpix_gauss_table": (ctypes.c_int, [_c_i32, _c_i32, ctypes.c_double, ctypes.c_double, _c_vp, _c_vp, _c_i64, _c_vp, _c_vp, _c_vp, _c_vp,
                                                  ctypes.c_int, _c_vp]),
+    "dsph_healpix_rotate": (ctypes.c_int, [_c_vp, _c_vp, _c_i64, _c_i32, _c_i32, _c_vp, _c_i64, _c_vp, _c_vp, _c_i64, ctypes.c_int, _c_vp]),
+    "dsph_healpix_interp_table": (ctypes.c_int, [_c_i32, _c_vp, _c_vp, _c_vp, _c_i64, _c_vp, _c_vp, ctypes.c_int, _c_vp]),
     "dsph_residual_epilogue": (ctypes.c_int, [_c_vp, _c_vp, _c_i64, ctypes.c_float, _c_i32, _c_i32, ctypes.c_int, _c_vp]),
     "dsph_nbr_attention_forward": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, _c_i64, _c_vp, _c_vp, _c_vp, _c_i32, _c_i64, _c_i64, _c_i32, _c_i32,
                                                    ctypes.c_int, _c_vp]),
@@ -797,6 +799,86 @@ def healpix_gauss_table(nside, W, sigma_rad, rho, indices=None, lut=None, device
                                         _ptr(ok), dev.index, _stream_ptr(dev))
     check(rc, "dsph_healpix_gauss_table")
     return cols, vals, raw, ok
+
+
+def _rotations(what, rot, device, n_maps):
+    """``rot`` checked: a contiguous float64 tensor [3, 3] (``n_maps`` None: only that) or [n_maps, 3, 3] on ``device`` (None: its
+    own) -> the number of rotations."""
+    import torch
+
+    ok_shape = isinstance(rot, torch.Tensor) and (tuple(rot.shape) == (3, 3)
+                                                  or (n_maps is not None and tuple(rot.shape) == (n_maps, 3, 3)))
+    if not (ok_shape and rot.dtype == torch.float64 and rot.is_contiguous()):
+        raise ValueError(f"{what}: rot must be a contiguous float64 tensor [3, 3]" + ("" if n_maps is None else f" or [N = {n_maps}, 3, 3]"))
+    if device is not None and rot.device != device:
+        raise ValueError(f"{what}: rot lives on {rot.device}, the maps on {device}")
+    return 1 if rot.dim() == 2 else int(rot.shape[0])
+
+
+def healpix_rotate(x, nside, rot, indices=None, lut=None, out=None):
+    """The NEST-ordered scalar maps ``x`` (N, M, F) rotated by bilinear interpolation (``dsph_healpix_rotate``):
+    out[n, r, :] = sum_j w_j x[n, row(p_j), :] with the four-pixel stencil of ``healpix.get_interp_weights`` at R^T v(indices[r]).
+
+    ``rot``: float64 [3, 3] (one rotation for the batch) or [N, 3, 3] (one per map), on the maps' device.  ``indices``, ``lut``: the
+    pixel set as for ``healpix_knn`` (both None: the full sky, M = 12 nside^2); a source pixel outside the set contributes zero.
+    ``out`` must not share memory with ``x``; allocated when None.  The arguments are checked before the library or the GPU is
+    touched."""
+    import torch
+
+    what = "healpix_rotate"
+    nside = int(nside)
+    if not (isinstance(x, torch.Tensor) and x.dtype == torch.float32 and x.dim() == 3 and x.is_contiguous()):
+        raise ValueError(f"{what} works on a contiguous float32 (N, M, F) tensor")
+    _, M = _disc_set(what, nside, indices, lut, None)
+    N, Mx, F = x.shape
+    if Mx != M or F < 1:
+        raise ValueError(f"{what}: a map of {Mx} pixels and {F} channels does not fit the set of {M} pixels (nside {nside}) with at "
+                         "least one channel")
+    n_rot = _rotations(what, rot, x.device, int(N))
+    if indices is not None and indices.device != x.device:
+        raise ValueError(f"{what}: indices live on {indices.device}, the maps on {x.device}")
+    if out is not None and not (isinstance(out, torch.Tensor) and out.dtype == torch.float32 and out.is_contiguous()
+                                and out.shape == x.shape and out.device == x.device):
+        raise ValueError("out must be a contiguous float32 tensor of x's shape on x's device")
+    if not x.is_cuda:
+        raise ValueError(f"{what} works on a HIP tensor")
+    require_gpu()
+    if out is None:
+        out = torch.empty_like(x)
+    if N == 0:  # (an empty tensor has no address to hand over)
+        return out
+    rc = lib().dsph_healpix_rotate(_ptr(x), _ptr(out), int(N), nside, int(F), _ptr(rot), n_rot, _ptr(lut), _ptr(indices), M,
+                                   x.device.index, _stream_ptr(x.device))
+    check(rc, "dsph_healpix_rotate")
+    return out
+
+
+def healpix_interp_table(nside, rot, indices=None, lut=None, device=None):
+    """The stencils of ``healpix_rotate`` for ONE rotation ``rot`` (float64 [3, 3] on the device) as a table
+    (``dsph_healpix_interp_table``) -> ``(cols int32 [M, 4], vals float32 [M, 4])``: ``ell_smooth(cols, vals, x)`` is the rotation,
+    on ``healpix.transpose_table(cols, vals)`` its adjoint.  A source outside the set is (col = the row itself, val = 0).  The
+    arguments are checked before the library or the GPU is touched."""
+    import torch
+
+    what = "healpix_interp_table"
+    nside = int(nside)
+    dev, M = _disc_set(what, nside, indices, lut, device)
+    if indices is None and device is None and isinstance(rot, torch.Tensor):
+        dev = rot.device  # (the full sky brings no device along; the rotation does)
+    _rotations(what, rot, None, None)
+    if dev.type != "cuda":
+        raise ValueError(f"{what} works on a HIP device")
+    require_gpu()
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    if rot.device != dev:
+        raise ValueError(f"{what}: rot lives on {rot.device}, the table on {dev}")
+    cols = torch.empty((M, 4), dtype=torch.int32, device=dev)
+    vals = torch.empty((M, 4), dtype=torch.float32, device=dev)
+    rc = lib().dsph_healpix_interp_table(nside, _ptr(rot), _ptr(lut), _ptr(indices), M, _ptr(cols), _ptr(vals), dev.index,
+                                         _stream_ptr(dev))
+    check(rc, "dsph_healpix_interp_table")
+    return cols, vals
 
 
 def rows_layout(t):

@@ -30,6 +30,14 @@ __all__ = [
     "reorder",
     "reorder_table",
     "pix2vec",
+    "ang2pix",
+    "vec2pix",
+    "pix2ang",
+    "get_interp_weights",
+    "get_interp_val",
+    "rotation_matrix",
+    "random_rotations",
+    "rotation_stencil",
     "neighbours",
     "kernel_width",
     "healpix_graph",
@@ -940,3 +948,219 @@ def transpose_table(cols, vals):
     colsT[c, slot] = r
     valsT[c, slot] = v.to(torch.float32)
     return colsT, valsT
+
+
+# ----------------------------------------------------------------------------------------------
+# From points to pixels: ang2pix / vec2pix / pix2ang and healpy's bilinear interpolation (get_interp_weights, get_interp_val),
+# numpy float64, healpy's names and conventions.  The reference of the rotation kernel (csrc/healpix_interp.hip, whose stencil
+# function is this arithmetic statement by statement) and what HealpyRotate runs on CPU tensors.
+# ----------------------------------------------------------------------------------------------
+
+_TWOPI = 2.0 * np.pi
+
+
+def _reduce_phi(phi):
+    """phi into [0, 2 pi]: a float64 phi of -1e-17 becomes exactly 2 pi (callers wrap ring positions, they do not assume < 2 pi)."""
+    phi = np.fmod(np.asarray(phi, dtype=np.float64), _TWOPI)
+    return np.where(phi < 0, phi + _TWOPI, phi)
+
+
+def _ring_info(nside, ring):
+    """Rings 1 .. 4 nside - 1 counted from the north pole: -> (nr, shifted, z, theta, first) -- pixels per quarter (the ring
+    holds 4 nr), whether the first centre sits half a step from phi = 0 (the caps, and the belt rings with (ring - nside) even),
+    z and theta of the centres (the expressions of ``pix2vec``), RING index of the first pixel."""
+    ring = np.asarray(ring, dtype=np.int64)
+    fact2 = 4.0 / (12 * nside * nside)
+    fact1 = (2 * nside) * fact2
+    north = ring < nside
+    south = ring > 3 * nside
+    nr = np.where(north, ring, np.where(south, 4 * nside - ring, nside))
+    nrf = nr.astype(np.float64)
+    z = np.where(north, 1.0 - (nrf * nrf) * fact2, np.where(south, (nrf * nrf) * fact2 - 1.0, (2 * nside - ring) * fact1))
+    shifted = np.where(north | south, 1, 1 - ((ring - nside) & 1))
+    first = np.where(north, 2 * nr * (nr - 1),
+                     np.where(south, 12 * nside * nside - 2 * (nr + 1) * nr, 2 * nside * (nside - 1) + (ring - nside) * 4 * nside))
+    theta = np.arctan2(np.sqrt(np.maximum(0.0, (1.0 - z) * (1.0 + z))), z)
+    return nr, shifted, z, theta, first
+
+
+def _ring_above(nside, z):
+    """The last ring whose centres lie at or north of z (0: above the first ring); healpy's ``ring_above``."""
+    z = np.asarray(z, dtype=np.float64)
+    az = np.abs(z)
+    belt = (nside * (2.0 - 1.5 * np.where(az <= 2.0 / 3.0, z, 0.0))).astype(np.int64)
+    iring = (nside * np.sqrt(3.0 * (1.0 - np.minimum(az, 1.0)))).astype(np.int64)
+    return np.where(az <= 2.0 / 3.0, belt, np.where(z > 0, iring, 4 * nside - iring - 1))
+
+
+def _zphi2ring(nside, z, sth, phi):
+    """RING index of the pixel that holds the direction (z = cos theta, sth = sin theta >= 0, phi)."""
+    z, sth = np.asarray(z, dtype=np.float64), np.asarray(sth, dtype=np.float64)
+    tt = np.minimum(_reduce_phi(phi), np.nextafter(_TWOPI, 0.0)) / (0.5 * np.pi)  # [0, 4)
+    za = np.abs(z)
+    # the belt: the pixel from the two edge lines through the point
+    t1 = nside * (0.5 + tt)
+    t2 = nside * z * 0.75
+    jp = np.floor(t1 - t2).astype(np.int64)
+    jm = np.floor(t1 + t2).astype(np.int64)
+    ir = nside + 1 + jp - jm  # 1 .. 2 nside + 1
+    kshift = 1 - (ir & 1)
+    ip = np.mod((jp + jm - nside + kshift + 1) // 2, 4 * nside)
+    belt = 2 * nside * (nside - 1) + (ir - 1) * 4 * nside + ip
+    # the caps (sin theta instead of sqrt(1 - |z|) close to a pole, where 1 - |z| has lost its digits)
+    tp = tt - np.floor(tt)
+    tmp = np.where(za < 0.99, nside * np.sqrt(3.0 * (1.0 - np.minimum(za, 1.0))), nside * sth / np.sqrt((1.0 + za) / 3.0))
+    jp = (tp * tmp).astype(np.int64)
+    jm = ((1.0 - tp) * tmp).astype(np.int64)
+    ir = jp + jm + 1  # ring counted from the nearer pole
+    ip = np.mod((tt * ir).astype(np.int64), 4 * ir)
+    cap = np.where(z > 0, 2 * ir * (ir - 1) + ip, 12 * nside * nside - 2 * ir * (ir + 1) + ip)
+    return np.where(za <= 2.0 / 3.0, belt, cap)
+
+
+def ang2pix(nside, theta, phi, nest=True):
+    """The pixel that holds the direction (theta, phi), like ``hp.ang2pix``: int64, NEST ids by default."""
+    nside = _check_nside(nside)
+    theta = np.asarray(theta, dtype=np.float64)
+    if np.any((theta < 0) | (theta > np.pi)):
+        raise ValueError("theta outside [0, pi]")
+    pix = _zphi2ring(nside, np.cos(theta), np.sin(theta), phi)
+    return ring2nest(nside, pix) if nest else pix
+
+
+def vec2pix(nside, x, y, z, nest=True):
+    """The pixel that holds the direction of the vector (x, y, z) (any positive length), like ``hp.vec2pix``."""
+    nside = _check_nside(nside)
+    x, y, z = (np.asarray(a, dtype=np.float64) for a in (x, y, z))
+    s = np.hypot(x, y)
+    r = np.hypot(s, z)
+    pix = _zphi2ring(nside, z / r, s / r, np.arctan2(y, x))
+    return ring2nest(nside, pix) if nest else pix
+
+
+def pix2ang(nside, pix, nest=True):
+    """(theta, phi) of pixel centres, like ``hp.pix2ang``: theta in [0, pi], phi in [0, 2 pi)."""
+    nside = _check_nside(nside)
+    pix = np.asarray(pix, dtype=np.int64)
+    ring_pix = nest2ring(nside, pix) if nest else pix
+    # the ring of a RING index: as ring2nest finds it
+    npix, ncap = 12 * nside * nside, 2 * nside * (nside - 1)
+    north, south = ring_pix < ncap, ring_pix >= npix - ncap
+    i_n = (1 + _isqrt(1 + 2 * np.where(north, ring_pix, 0))) >> 1
+    i_s = (1 + _isqrt(2 * np.where(south, npix - ring_pix, 1) - 1)) >> 1
+    ring = np.where(north, i_n, np.where(south, 4 * nside - i_s, np.where(north | south, 0, ring_pix - ncap) // (4 * nside) + nside))
+    nr, shifted, _, theta, first = _ring_info(nside, ring)
+    phi = ((ring_pix - first) + 0.5 * shifted) * ((0.5 * np.pi) / nr)
+    return theta, phi
+
+
+def get_interp_weights(nside, theta, phi=None, nest=True):
+    """The four pixels around a direction and their bilinear weights, like ``hp.get_interp_weights`` (healpy's ``get_interpol``):
+    -> (pix int64 [4, n], weights float64 [4, n]); entries 0, 1 on the ring above the point, 2, 3 on the ring below.  With
+    ``phi=None`` the first argument holds pixel ids and their centres are the directions.
+
+    On a ring of n pixels with step dphi: tmp = phi / dphi - shift / 2, i1 = floor(tmp), w1 = (phi - (i1 + shift / 2) dphi) / dphi,
+    pixels i1 and i1 + 1 both wrapped modulo n; the two rings are mixed linearly in theta (the mixing weight clamped to [0, 1]: at
+    a ring's own latitude the ring above may be named, with weight 1 up to rounding, on the ring meant).  Above the first ring its
+    weights are scaled by theta / theta_1 and the rest, (1 - wtheta) / 4 a pixel, goes to all four pixels of ring 1; below the last
+    ring likewise.  A column of the result never holds a pixel twice."""
+    nside = _check_nside(nside)
+    if phi is None:
+        theta, phi = pix2ang(nside, theta, nest)
+    theta = np.asarray(theta, dtype=np.float64)
+    shape = np.broadcast(theta, np.asarray(phi)).shape
+    theta, phi = (np.broadcast_to(np.asarray(a, dtype=np.float64), shape).reshape(-1) for a in (theta, phi))
+    if np.any((theta < 0) | (theta > np.pi)):
+        raise ValueError("theta outside [0, pi]")
+    phi = _reduce_phi(phi)
+    nl4 = 4 * nside
+    ir1 = _ring_above(nside, np.cos(theta))
+    ir2 = ir1 + 1
+    north, south = ir1 <= 0, ir2 >= nl4
+    pix = np.empty((4, theta.shape[0]), dtype=np.int64)
+    pos = np.empty((4, theta.shape[0]), dtype=np.int64)
+    w = np.empty((4, theta.shape[0]), dtype=np.float64)
+    thetas = []
+    firsts = []
+    for k, ring in enumerate((np.where(north, 1, ir1), np.where(south, nl4 - 1, ir2))):
+        nr, shifted, _, th, first = _ring_info(nside, ring)
+        n4 = 4 * nr
+        dphi = (0.5 * np.pi) / nr
+        half = 0.5 * shifted
+        fl = np.floor(phi / dphi - half)  # -1 .. n4
+        w1 = (phi - (fl + half) * dphi) / dphi
+        i1 = np.mod(fl.astype(np.int64), n4)
+        pos[2 * k], pos[2 * k + 1] = i1, np.mod(i1 + 1, n4)
+        w[2 * k], w[2 * k + 1] = 1.0 - w1, w1
+        thetas.append(th)
+        firsts.append(first)
+    th1, th2 = thetas
+    with np.errstate(divide="ignore", invalid="ignore"):
+        wt = np.where(north, theta / th2, np.where(south, (theta - th1) / (np.pi - th1), (theta - th1) / (th2 - th1)))
+    wt = np.clip(wt, 0.0, 1.0)
+    fac_n, fac_s = (1.0 - wt) * 0.25, wt * 0.25
+    upper = np.where(north, 0.0, 1.0 - wt)  # what entries 0, 1 keep of their ring weights
+    lower = np.where(south, 0.0, wt)
+    add01 = np.where(north, fac_n, np.where(south, fac_s, 0.0))
+    add23 = add01
+    w[0], w[1] = w[0] * upper + add01, w[1] * upper + add01
+    w[2], w[3] = w[2] * lower + add23, w[3] * lower + add23
+    # the pole branches: all four pixels from the polar ring, the partners two positions on
+    pos[0] = np.where(north, (pos[2] + 2) & 3, pos[0])
+    pos[1] = np.where(north, (pos[3] + 2) & 3, pos[1])
+    pos[2] = np.where(south, (pos[0] + 2) & 3, pos[2])
+    pos[3] = np.where(south, (pos[1] + 2) & 3, pos[3])
+    pix[0], pix[1] = firsts[0] + pos[0], firsts[0] + pos[1]
+    pix[2], pix[3] = firsts[1] + pos[2], firsts[1] + pos[3]
+    if nest:
+        pix = ring2nest(nside, pix)
+    return pix.reshape((4,) + shape), w.reshape((4,) + shape)
+
+
+def get_interp_val(m, theta, phi, nest=True):
+    """The map(s) ``m`` ((npix,) or (k, npix)) interpolated at the directions (theta, phi), like ``hp.get_interp_val``."""
+    m = np.asarray(m)
+    pix, w = get_interp_weights(npix2nside(m.shape[-1]), theta, phi, nest)
+    return (m[..., pix] * w).sum(axis=-1 - (pix.ndim - 1))
+
+
+def rotation_matrix(alpha, beta, gamma):
+    """The ZYZ rotation Rz(alpha) Ry(beta) Rz(gamma), float64 [3, 3]: a map rotated by R has y(v) = x(R^T v)."""
+    ca, sa, cb, sb, cg, sg = (f(float(a)) for a in (alpha, beta, gamma) for f in (np.cos, np.sin))
+    rz1 = np.array([[ca, -sa, 0.0], [sa, ca, 0.0], [0.0, 0.0, 1.0]])
+    ry = np.array([[cb, 0.0, sb], [0.0, 1.0, 0.0], [-sb, 0.0, cb]])
+    rz2 = np.array([[cg, -sg, 0.0], [sg, cg, 0.0], [0.0, 0.0, 1.0]])
+    return rz1 @ ry @ rz2
+
+
+def random_rotations(n, generator=None, device=None):
+    """``n`` rotations uniform on SO(3): float64 tensor [n, 3, 3] on ``device``.  Normalised quaternions from four normals drawn
+    from ``generator`` (a ``torch.Generator`` of that device): reproducible, and drawn on the device without a synchronisation."""
+    import torch
+
+    q = torch.randn((int(n), 4), dtype=torch.float64, generator=generator, device=device)
+    q = q / torch.linalg.norm(q, dim=1, keepdim=True)
+    a, b, c, d = q.unbind(1)
+    rows = (a * a + b * b - c * c - d * d, 2 * (b * c - a * d), 2 * (b * d + a * c),
+            2 * (b * c + a * d), a * a - b * b + c * c - d * d, 2 * (c * d - a * b),
+            2 * (b * d - a * c), 2 * (c * d + a * b), a * a - b * b - c * c + d * d)
+    return torch.stack(rows, dim=1).reshape(-1, 3, 3)
+
+
+def rotation_stencil(nside, rot, indices=None):
+    """The stencil that rotates a NEST map of the pixel set ``indices`` (None: the full sky) by the matrix ``rot`` [3, 3]:
+    -> (rows int64 [4, M], weights float64 [4, M]) with y[r] = sum_j weights[j, r] x[rows[j, r]] -- the interpolation weights at
+    R^T v(indices[r]); a source pixel outside the set has row -1 (it contributes zero, nothing is renormalised)."""
+    nside = _check_nside(nside)
+    ind = _index_set(nside, indices)
+    rot = np.asarray(rot, dtype=np.float64)
+    if rot.shape != (3, 3):
+        raise ValueError("rot must be a [3, 3] matrix")
+    u = pix2vec(nside, ind) @ rot  # rows R^T v
+    s = np.hypot(u[:, 0], u[:, 1])
+    pix, w = get_interp_weights(nside, np.arctan2(s, u[:, 2]), np.arctan2(u[:, 1], u[:, 0]))
+    if ind is not None:
+        lut = np.full(nside2npix(nside), -1, dtype=np.int64)
+        lut[ind] = np.arange(ind.shape[0], dtype=np.int64)
+        pix = lut[pix]
+    return pix, w

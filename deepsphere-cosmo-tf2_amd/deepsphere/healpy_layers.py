@@ -877,5 +877,164 @@ class HealpyReorder(torch.nn.Module):
     call = forward
 
 
+class _RotateFunction(torch.autograd.Function):
+    """``HealpyRotate``: the interpolation stencil as a gather; the input gradient is the transposed stencil applied to the
+    upstream gradient (built in the backward only, so only for an input that requires a gradient)."""
+
+    @staticmethod
+    def forward(ctx, x, layer, rot):
+        ctx.layer, ctx.rot = layer, rot
+        return layer._rotate(x, rot)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return ctx.layer._rotate_adjoint(dy.contiguous(), ctx.rot), None, None
+
+
+# THE SHAPE RULE of HealpyRotate with a FIXED rotation on a HIP map: the channel counts F for which the cached W = 4 table through
+# dsph_ell_smooth is ahead of the table-free kernel (dsph_healpix_rotate) by more than the kernel's own spread over three
+# alternating runs go to the table (tools/bench_rotate.py, DESIGN.md 4.15).  Measured on one MI355X, nside 1024 full sky, one
+# rotation for the batch, kernel / ell_smooth on the table built beforehand, ms (the kernel's spread over its three runs):
+#   N x F = 8 x 1: 0.606 / 2.038 (0.003);  4 x 4: 0.564 / 1.588 (0.001);  4 x 16: 1.286 / 5.846 (0.003);  2 x 64: 2.502 / 14.263 (0.004)
+# The table is ahead in no class, so every F runs the kernel.  (With a workgroup per sample, each computing the same stencils, the
+# kernel took 3.353 ms at 8 x 1 and 1.701 at 4 x 4 and the table was ahead in both; the launcher now walks the samples of a shared
+# rotation inside the workgroup.)  Rotations drawn per sample always run the kernel -- a table per sample and step is what the
+# kernel exists to avoid.
+def _rotate_on_table(F):
+    return False
+
+
+class HealpyRotate(torch.nn.Module):
+    """Rotates NEST-ordered scalar (batch, pixels, channels) maps by bilinear interpolation on the sphere, what
+    ``hp.Rotator.rotate_map_pixel`` does on the host: y(v) = x(R^T v) read through the four-pixel stencil of
+    ``healpix.get_interp_weights``.  The augmentation of a training loop on sky maps, on the device.  It has no ``p`` and no
+    ``Fout``: ``HealpyGCNN`` passes it through unchanged, so it can stand first in the list of layers.
+
+    :param nside: nside of the maps (at most 8192: pixel ids are int32 in the kernel)
+    :param indices: sorted NEST ids of a partial-sky map (the argument of ``HealpyGCNN``), None for the full sky.  A source pixel
+        outside the set contributes zero and nothing is renormalised: the rotated zero-padded map, read at the set
+    :param rot: "random" -- in ``train()`` mode a fresh rotation, uniform on SO(3), per sample and call
+        (``healpix.random_rotations``); in ``eval()`` mode the layer is the identity and returns its input.  Or a [3, 3] rotation
+        matrix (``healpix.rotation_matrix``), applied in both modes
+    :param generator: the ``torch.Generator`` the random rotations are drawn from (None: the default one of the maps' device)
+
+    ``forward(x, rot=None)``: an explicit [3, 3] or [N, 3, 3] ``rot`` overrides either setting.  Spin-2 fields (shear) do not
+    rotate like this; scalar maps only.
+
+    float32 maps on a HIP device run ``dsph_healpix_rotate`` (nothing is materialised; see the shape rule above for a fixed
+    rotation); CPU tensors and other dtypes ``healpix.rotation_stencil`` and ``index_select`` on the host.  Differentiable: the input
+    gradient is the transposed stencil -- on the device ``_native.healpix_interp_table`` per distinct rotation,
+    ``healpix.transpose_table`` and ``_native.ell_smooth`` on the gradient: deterministic, no atomics, and the SLOW path (a table
+    per rotation is built after all); an augmentation in front of a network needs no input gradient and never takes it."""
+
+    def __init__(self, nside, indices=None, rot="random", generator=None):
+        super().__init__()
+        self.nside = int(nside)
+        if not healpix.isnsideok(self.nside):
+            raise ValueError(f"nside = {nside} is not a power of two >= 1")
+        if self.nside > _native.DISC_MAX_NSIDE:
+            raise ValueError(f"nside = {self.nside} is beyond the int32 pixel ids of the kernel (nside <= {_native.DISC_MAX_NSIDE})")
+        self.indices = healpix._index_set(self.nside, indices)  # None: the full sky
+        self.full_sky = self.indices is None
+        self.n_pix = healpix.nside2npix(self.nside) if self.full_sky else int(self.indices.size)
+        if self.n_pix < 1:
+            raise ValueError("an empty pixel set")
+        self.generator = generator
+        if isinstance(rot, str):
+            if rot != "random":
+                raise ValueError(f'rot must be "random" or a [3, 3] rotation matrix, got <{rot}>')
+            self.rot = None
+        else:
+            r = np.asarray(rot.detach().cpu() if isinstance(rot, torch.Tensor) else rot, dtype=np.float64)
+            if r.shape != (3, 3) or not np.allclose(r.T @ r, np.eye(3), atol=1e-9) or np.linalg.det(r) < 0:
+                raise ValueError('rot must be "random" or a [3, 3] rotation matrix (orthonormal, determinant +1)')
+            self.rot = torch.as_tensor(r)
+        self._sets = {}     # device -> (indices int64, lut int32) of a partial-sky set
+        self._fixed = {}    # device -> the fixed rotation there
+        self._tables = {}   # (device, transposed) -> the fixed rotation's table there
+
+    def _set(self, device):
+        if self.full_sky:
+            return None, None
+        if str(device) not in self._sets:
+            self._sets[str(device)] = healpix._device_lut(self.nside, self.indices, device)
+        return self._sets[str(device)]
+
+    def _fixed_table(self, device, transposed):
+        key = (str(device), bool(transposed))
+        if key not in self._tables:
+            table = _native.healpix_interp_table(self.nside, self._fixed[str(device)], *self._set(device), device=device)
+            self._tables[key] = healpix.transpose_table(*table) if transposed else table
+        return self._tables[key]
+
+    def _host_stencils(self, rot):
+        r = rot.detach().cpu().numpy().reshape(-1, 3, 3)
+        return [healpix.rotation_stencil(self.nside, ri, self.indices) for ri in r]
+
+    def _rotate(self, x, rot):
+        if x.is_cuda and x.dtype == torch.float32:
+            x = x.contiguous()
+            if rot is self._fixed.get(str(x.device)) and _rotate_on_table(int(x.shape[2])):
+                return _native.ell_smooth(*self._fixed_table(x.device, False), x)
+            return _native.healpix_rotate(x, self.nside, rot, *self._set(x.device))
+        out = torch.zeros_like(x)
+        stencils = self._host_stencils(rot)
+        for n in range(x.shape[0]):
+            rows, w = stencils[n if len(stencils) > 1 else 0]
+            for j in range(4):
+                rj = torch.as_tensor(rows[j], device=x.device)
+                wj = torch.as_tensor(np.where(rows[j] >= 0, w[j], 0.0), device=x.device).to(x.dtype)
+                out[n] += x[n].index_select(0, rj.clamp(min=0)) * wj[:, None]
+        return out
+
+    def _rotate_adjoint(self, dy, rot):
+        if dy.is_cuda and dy.dtype == torch.float32:
+            if rot.dim() == 2:
+                if rot is self._fixed.get(str(dy.device)):
+                    table = self._fixed_table(dy.device, True)
+                else:
+                    table = healpix.transpose_table(*_native.healpix_interp_table(self.nside, rot, *self._set(dy.device), device=dy.device))
+                return _native.ell_smooth(*table, dy)
+            dx = torch.empty_like(dy)
+            for n in range(dy.shape[0]):
+                table = _native.healpix_interp_table(self.nside, rot[n].contiguous(), *self._set(dy.device), device=dy.device)
+                _native.ell_smooth(*healpix.transpose_table(*table), dy[n:n + 1], out=dx[n:n + 1])
+            return dx
+        dx = torch.zeros_like(dy)
+        stencils = self._host_stencils(rot)
+        for n in range(dy.shape[0]):
+            rows, w = stencils[n if len(stencils) > 1 else 0]
+            for j in range(4):
+                keep = rows[j] >= 0
+                rj = torch.as_tensor(rows[j][keep], device=dy.device)
+                wj = torch.as_tensor(w[j][keep], device=dy.device).to(dy.dtype)
+                dx[n].index_add_(0, rj, dy[n][torch.as_tensor(keep, device=dy.device)] * wj[:, None])
+        return dx
+
+    def forward(self, input_tensor, rot=None):
+        x = _as_tensor(input_tensor)
+        if x.dim() != 3 or x.shape[1] != self.n_pix:
+            raise ValueError(f"HealpyRotate: input of shape {tuple(x.shape)} has {x.shape[1] if x.dim() > 1 else 0} pixels, "
+                             f"the layer was built for {self.n_pix} (nside {self.nside})")
+        N = int(x.shape[0])
+        if rot is not None:
+            rot = rot if isinstance(rot, torch.Tensor) else torch.as_tensor(np.asarray(rot, dtype=np.float64))
+            if tuple(rot.shape) not in ((3, 3), (N, 3, 3)):
+                raise ValueError(f"HealpyRotate: rot of shape {tuple(rot.shape)}, expected [3, 3] or [N = {N}, 3, 3]")
+            rot = rot.to(device=x.device, dtype=torch.float64).contiguous()
+        elif self.rot is not None:
+            if str(x.device) not in self._fixed:
+                self._fixed[str(x.device)] = self.rot.to(x.device)
+            rot = self._fixed[str(x.device)]
+        elif not self.training:
+            return input_tensor
+        else:
+            where = x.device if self.generator is None else self.generator.device
+            rot = healpix.random_rotations(N, generator=self.generator, device=where).to(x.device)
+        return _RotateFunction.apply(x, self, rot)
+
+    call = forward
+
+
 __all__ = ["HealpyPool", "HealpyPseudoConv", "HealpyPseudoConv_Transpose", "HealpyChebyshev", "HealpyMonomial", "HealpyBernstein",
-           "Healpy_ResidualLayer", "Healpy_Transformer", "Healpy_ViT", "HealpySmoothing", "HealpyReorder"]
+           "Healpy_ResidualLayer", "Healpy_Transformer", "Healpy_ViT", "HealpySmoothing", "HealpyReorder", "HealpyRotate"]

@@ -78,7 +78,7 @@ class HealpyGCNN(torch.nn.Sequential):
                  graph_mode="knn", build="host"):
         """
         :param nside: nside of the input maps
-        :param indices: sorted NEST pixel ids of the input maps
+        :param indices: sorted NEST pixel ids of the input maps (None: the full sky)
         :param layers: list of layers / layer specs (``HealpyChebyshev`` ...)
         :param n_neighbors: neighbours of the graph, 8 (default), 20, 40 or 60
         :param max_batch_size, initial_Fin: the reference derives ``n_matmul_splits`` for TensorFlow's sparse
@@ -100,8 +100,8 @@ class HealpyGCNN(torch.nn.Sequential):
         if n_neighbors not in [8, 20, 40, 60]:
             raise NotImplementedError(
                 f"The requested number of neighbors {n_neighbors} is nor supported. Choose either 8, 20, 40 or 60.")
-        indices = np.asarray(indices)
         nside_in = int(nside)
+        indices = np.arange(healpix.nside2npix(nside_in), dtype=np.int64) if indices is None else np.asarray(indices)
         reduction_fac = 1.0
         for layer in layers:
             if isinstance(layer, (hp_nn.HealpyPool, hp_nn.HealpyPseudoConv, hp_nn.Healpy_ViT)):

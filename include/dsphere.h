@@ -490,6 +490,36 @@ int dsph_healpix_disc_count(int32_t nside, double r2, const int64_t* indices, co
 int dsph_healpix_gauss_table(int32_t nside, int32_t W, double sigma_rad, double rho, const int64_t* indices, const int32_t* lut,
                              int64_t M, int32_t* cols, float* vals, float* raw, uint8_t* ok, int device, void* hip_stream);
 
+/* Rotating scalar HEALPix maps in NEST order by bilinear interpolation (plan-free; csrc/healpix_interp.hip).
+ * Replaces: hp.Rotator.rotate_map_pixel on the host (random-rotation augmentation of a training loop), or a 4-entry-per-row sparse
+ * table per rotation (32 bytes per pixel and rotation).
+ * `indices`, `lut` and M as for dsph_healpix_knn; NULL, NULL and M = 12 nside^2: the full sky.
+ *
+ * dsph_healpix_rotate:  y[n, r, :] = sum_j w_j x[n, row(p_j), :], where (p_j, w_j), j < 4, is the interpolation stencil of healpy's
+ * get_interp_weights at the direction R^T v(indices[r]), v the pixel centre and R = rot[n] (rot[0] when n_rot == 1).
+ *   x, y     device (N, M, F) fp32, contiguous; they must not overlap
+ *   rot      device float64 [n_rot, 9], row-major 3 x 3 rotation matrices; n_rot == 1 (one for the batch) or n_rot == N
+ * A source pixel outside the set contributes zero and the other weights are not renormalised: the result is the rotated zero-padded
+ * full-sky map read at the set.  An id of `indices` outside [0, 12 nside^2) gives a row of zeros.
+ * Geometry in float64 (centre, rotation, atan2, ring above, weights); weights rounded to float32 once; w0 x0 and three fused
+ * multiply-adds in float32 in the order of the stencil: deterministic, no atomics, one writer per element.  The stencil of a pixel
+ * is computed once per (sample, pixel) -- once per pixel with n_rot == 1 -- and reused over the F channels.  F < 16: a lane per
+ * pixel; wider rows: stencils through LDS and lanes along the channels; 1, 2 or 4 floats per access by F and the alignment of x, y.
+ * Grid: blocks of 256 rows x min(N, 65535); further maps on further trips.  Every element offset is 64-bit.
+ *
+ * dsph_healpix_interp_table: the same stencils for ONE rotation as a table, cols int32 [M, 4] (rows of x) and vals float32 [M, 4];
+ * a source outside the set becomes (col = the row itself, val = 0), the padding of dsph_ell_smooth.  dsph_ell_smooth on it applies
+ * the rotation, on its transpose (entries regrouped by column) the adjoint.  No row holds a column twice but for that padding.
+ *
+ * nside a power of two, 1 <= nside <= 8192 (pixel indices are int32; DSPH_E_UNSUPPORTED beyond), F >= 1, N >= 0 (N = 0 or M = 0:
+ * DSPH_OK, no launch).  Bad arguments (a required pointer NULL, indices without lut or the reverse, nside not a power of two,
+ * M != 12 nside^2 without indices, M outside [0, 12 nside^2], F < 1, N < 0, n_rot neither 1 nor N, rot not 8-byte aligned, x
+ * overlapping y): DSPH_E_BADARG before any launch.  Both only enqueue on `hip_stream`. */
+int dsph_healpix_rotate(const float* x, float* y, int64_t N, int32_t nside, int32_t F, const double* rot, int64_t n_rot,
+                        const int32_t* lut, const int64_t* indices, int64_t M, int device, void* hip_stream);
+int dsph_healpix_interp_table(int32_t nside, const double* rot, const int32_t* lut, const int64_t* indices, int64_t M, int32_t* cols,
+                              float* vals, int device, void* hip_stream);
+
 /* Attention over the edges of the pixel graph (plan-free; csrc/nbr_attention.hip).
  * Replaces: gnn_transformers.scaled_dot_product_sparse_attention (reference gnn_transformers.py:54-106: three embedding lookups that
  * materialise q, k, v per edge, exp, two segment sums) and the split_heads transposes around it (:189-196, :225-231).
