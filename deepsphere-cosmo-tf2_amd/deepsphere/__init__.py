@@ -8,10 +8,10 @@ for gfx950, C ABI in ``include/dsphere.h``).
 
 __version__ = "0.1.0"
 
-from . import healpix, utils  # noqa: F401
+from . import healpix, sht, utils  # noqa: F401
 from .gnn_layers import Bernstein, Chebyshev, GCNN_ResidualLayer, Monomial  # noqa: F401
 from .gnn_transformers import Graph_Transformer, Graph_ViT  # noqa: F401
-from .healpy_layers import (HealpyBernstein, HealpyChebyshev, HealpyMonomial, HealpyPool, HealpyPseudoConv,  # noqa: F401
-                            HealpyPseudoConv_Transpose, HealpyReorder, HealpyRotate, HealpySmoothing, Healpy_ResidualLayer,
+from .healpy_layers import (HealpyBernstein, HealpyChebyshev, HealpyMonomial, HealpyPool, HealpyPowerSpectrum,  # noqa: F401
+                            HealpyPseudoConv, HealpyPseudoConv_Transpose, HealpyReorder, HealpyRotate, HealpySmoothing, Healpy_ResidualLayer,
                             Healpy_Transformer, Healpy_ViT)
 from .healpy_networks import HealpyGCNN  # noqa: F401

@@ -120,6 +120,10 @@ SIGNATURES = {
                                                  ctypes.c_int, _c_vp]),
     "dsph_healpix_rotate": (ctypes.c_int, [_c_vp, _c_vp, _c_i64, _c_i32, _c_i32, _c_vp, _c_i64, _c_vp, _c_vp, _c_i64, ctypes.c_int, _c_vp]),
     "dsph_healpix_interp_table": (ctypes.c_int, [_c_i32, _c_vp, _c_vp, _c_vp, _c_i64, _c_vp, _c_vp, ctypes.c_int, _c_vp]),
+    "dsph_sht_ring_analysis": (ctypes.c_int, [_c_vp, _c_vp, _c_i64, _c_i32, _c_i32, _c_i32, _c_vp, _c_vp, _c_i64, ctypes.c_int, _c_vp]),
+    "dsph_sht_legendre_analysis": (ctypes.c_int, [_c_vp, _c_vp, _c_i64, _c_i32, _c_i32, _c_i32, ctypes.c_int, _c_vp]),
+    "dsph_sht_legendre_synthesis": (ctypes.c_int, [_c_vp, _c_vp, _c_i64, _c_i32, _c_i32, _c_i32, ctypes.c_int, _c_vp]),
+    "dsph_sht_ring_synthesis": (ctypes.c_int, [_c_vp, _c_vp, _c_i64, _c_i32, _c_i32, _c_i32, _c_vp, _c_vp, _c_i64, ctypes.c_int, _c_vp]),
     "dsph_residual_epilogue": (ctypes.c_int, [_c_vp, _c_vp, _c_i64, ctypes.c_float, _c_i32, _c_i32, ctypes.c_int, _c_vp]),
     "dsph_nbr_attention_forward": (ctypes.c_int, [_c_vp, _c_vp, _c_vp, _c_i64, _c_vp, _c_vp, _c_vp, _c_i32, _c_i64, _c_i64, _c_i32, _c_i32,
                                                    ctypes.c_int, _c_vp]),
@@ -879,6 +883,230 @@ def healpix_interp_table(nside, rot, indices=None, lut=None, device=None):
                                          _stream_ptr(dev))
     check(rc, "dsph_healpix_interp_table")
     return cols, vals
+
+
+SHT_MAX_NSIDE = 2048         # dsph_sht_*: the largest nside the transform takes
+SHT_CHUNK_BYTES = 1 << 31    # the compositions' F_m scratch: at most this many bytes at a time (but always one map's worth) ...
+SHT_CHUNK_COLS = 16384       # ... and at most this many columns (maps x channels; always one map's worth)
+SHT_COL_BLOCK = 8            # columns of a workgroup of the kernels (SH_CB): a trip of whole blocks wastes no lanes
+
+
+def _sht_shape(what, nside, lmax):
+    nside, lmax = int(nside), int(lmax)
+    if nside < 1 or nside & (nside - 1):
+        raise ValueError(f"{what}: nside = {nside} is not a power of two >= 1")
+    if nside > SHT_MAX_NSIDE:
+        raise ValueError(f"{what}: nside = {nside} is beyond the transform's limit of {SHT_MAX_NSIDE}")
+    if lmax < 0 or lmax > 4 * nside - 1:
+        raise ValueError(f"{what}: lmax = {lmax} outside [0, 4 nside - 1 = {4 * nside - 1}]")
+    return nside, lmax
+
+
+def _sht_lmax_of(what, nalm):
+    lmax = (int(np.sqrt(8 * int(nalm) + 1)) - 3) // 2
+    if (lmax + 1) * (lmax + 2) // 2 != int(nalm):
+        raise ValueError(f"{what}: {nalm} coefficients are not (lmax + 1)(lmax + 2) / 2 for any lmax")
+    return lmax
+
+
+def _sht_map(what, x, nside, indices, lut, name="x"):
+    """A map argument checked: contiguous float32 (N, M, F) that fits the pixel set -> (N, M, F)."""
+    import torch
+
+    if not (isinstance(x, torch.Tensor) and x.dtype == torch.float32 and x.dim() == 3 and x.is_contiguous()):
+        raise ValueError(f"{what}: {name} must be a contiguous float32 (N, M, F) tensor")
+    _, M = _disc_set(what, nside, indices, lut, None)
+    N, Mx, F = (int(v) for v in x.shape)
+    if Mx != M or F < 1:
+        raise ValueError(f"{what}: a map of {Mx} pixels and {F} channels does not fit the set of {M} pixels (nside {nside}) with at "
+                         "least one channel")
+    if indices is not None and indices.device != x.device:
+        raise ValueError(f"{what}: indices live on {indices.device}, the maps on {x.device}")
+    return N, M, F
+
+
+def _sht_out(what, out, src, dtype, shape, name):
+    """``out`` (or a fresh tensor) of ``dtype`` and ``shape`` on the device of ``src``, sharing no memory with it."""
+    import torch
+
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=src.device)
+    if not (isinstance(out, torch.Tensor) and out.dtype == dtype and tuple(out.shape) == tuple(shape) and out.is_contiguous()
+            and out.device == src.device):
+        raise ValueError(f"{what}: out must be a contiguous {dtype} tensor of shape {tuple(shape)} on {src.device} ({name})")
+    a0, b0 = src.data_ptr(), out.data_ptr()
+    if src.numel() and out.numel() and a0 < b0 + _nbytes(out) and b0 < a0 + _nbytes(src):
+        raise ValueError(f"{what}: out shares memory with the input; the transform cannot run in place")
+    return out
+
+
+def _sht_hip(what, t):
+    if not t.is_cuda:
+        raise ValueError(f"{what} works on a HIP tensor")
+    require_gpu()
+
+
+def sht_fm_shape(nside, lmax, N, F):
+    """Shape of the float64 F_m array of ``N`` maps of ``F`` channels: [lmax + 1, 4 nside - 1, N F, 2]."""
+    return (int(lmax) + 1, 4 * int(nside) - 1, int(N) * int(F), 2)
+
+
+def sht_alm_size(lmax):
+    return (int(lmax) + 1) * (int(lmax) + 2) // 2
+
+
+def sht_ring_analysis(x, nside, lmax, indices=None, lut=None, out=None):
+    """F_m(ring) = sum_j x[ring, j] e^{-i m phi_j}, m <= lmax, of the NEST maps ``x`` (N, M, F) float32 (``dsph_sht_ring_analysis``) ->
+    float64 [lmax + 1, 4 nside - 1, N F, 2].  ``indices``, ``lut``: the footprint as for ``healpix_rotate``; pixels outside it count
+    as zero.  The arguments are checked before the library or the GPU is touched."""
+    import torch
+
+    what = "sht_ring_analysis"
+    nside, lmax = _sht_shape(what, nside, lmax)
+    N, M, F = _sht_map(what, x, nside, indices, lut)
+    out = _sht_out(what, out, x, torch.float64, sht_fm_shape(nside, lmax, N, F), "F_m")
+    _sht_hip(what, x)
+    if N == 0:
+        return out
+    rc = lib().dsph_sht_ring_analysis(_ptr(x), _ptr(out), N, nside, F, lmax, _ptr(lut), _ptr(indices), M, x.device.index,
+                                      _stream_ptr(x.device))
+    check(rc, "dsph_sht_ring_analysis")
+    return out
+
+
+def _sht_fm(what, fm, nside, lmax, N, F):
+    import torch
+
+    shape = sht_fm_shape(nside, lmax, N, F)
+    if not (isinstance(fm, torch.Tensor) and fm.dtype == torch.float64 and tuple(fm.shape) == shape and fm.is_contiguous()):
+        raise ValueError(f"{what}: fm must be a contiguous float64 tensor of shape {shape}")
+
+
+def _sht_alm(what, alm, nside):
+    import torch
+
+    if not (isinstance(alm, torch.Tensor) and alm.dtype == torch.complex128 and alm.dim() == 3 and alm.is_contiguous()
+            and alm.shape[2] >= 1):
+        raise ValueError(f"{what}: alm must be a contiguous complex128 (N, nalm, F) tensor with at least one channel")
+    lmax = _sht_lmax_of(what, alm.shape[1])
+    _sht_shape(what, nside, lmax)
+    return int(alm.shape[0]), lmax, int(alm.shape[2])
+
+
+def sht_legendre_analysis(fm, nside, lmax, N, F, out=None):
+    """a_lm = w sum_rings lambda_lm(theta_ring) F_m(ring), w = 4 pi / npix (``dsph_sht_legendre_analysis``): ``fm`` as
+    ``sht_ring_analysis`` returns it -> complex128 (N, nalm, F) in healpy's packed layout."""
+    import torch
+
+    what = "sht_legendre_analysis"
+    nside, lmax = _sht_shape(what, nside, lmax)
+    N, F = int(N), int(F)
+    if N < 0 or F < 1:
+        raise ValueError(f"{what}: N = {N} maps of F = {F} channels")
+    _sht_fm(what, fm, nside, lmax, N, F)
+    out = _sht_out(what, out, fm, torch.complex128, (N, sht_alm_size(lmax), F), "alm")
+    _sht_hip(what, fm)
+    if N == 0:
+        return out
+    rc = lib().dsph_sht_legendre_analysis(_ptr(fm), _ptr(out), N, nside, F, lmax, fm.device.index, _stream_ptr(fm.device))
+    check(rc, "dsph_sht_legendre_analysis")
+    return out
+
+
+def sht_legendre_synthesis(alm, nside, out=None):
+    """F_m(ring) = sum_l a_lm lambda_lm(theta_ring) (``dsph_sht_legendre_synthesis``): ``alm`` complex128 (N, nalm, F) ->
+    float64 [lmax + 1, 4 nside - 1, N F, 2]."""
+    import torch
+
+    what = "sht_legendre_synthesis"
+    N, lmax, F = _sht_alm(what, alm, int(nside))
+    nside = int(nside)
+    out = _sht_out(what, out, alm, torch.float64, sht_fm_shape(nside, lmax, N, F), "F_m")
+    _sht_hip(what, alm)
+    if N == 0:
+        return out
+    rc = lib().dsph_sht_legendre_synthesis(_ptr(alm), _ptr(out), N, nside, F, lmax, alm.device.index, _stream_ptr(alm.device))
+    check(rc, "dsph_sht_legendre_synthesis")
+    return out
+
+
+def sht_ring_synthesis(fm, nside, lmax, N, F, indices=None, lut=None, out=None):
+    """map[ring, j] = Re sum_m c_m F_m(ring) e^{+i m phi_j}, c_0 = 1, c_m = 2 (``dsph_sht_ring_synthesis``) -> float32 (N, M, F) in
+    NEST order; on a footprint only its rows are written."""
+    import torch
+
+    what = "sht_ring_synthesis"
+    nside, lmax = _sht_shape(what, nside, lmax)
+    N, F = int(N), int(F)
+    if N < 0 or F < 1:
+        raise ValueError(f"{what}: N = {N} maps of F = {F} channels")
+    _sht_fm(what, fm, nside, lmax, N, F)
+    _, M = _disc_set(what, nside, indices, lut, None)
+    if indices is not None and indices.device != fm.device:
+        raise ValueError(f"{what}: indices live on {indices.device}, F_m on {fm.device}")
+    out = _sht_out(what, out, fm, torch.float32, (N, M, F), "the maps")
+    _sht_hip(what, fm)
+    if N == 0:
+        return out
+    rc = lib().dsph_sht_ring_synthesis(_ptr(fm), _ptr(out), N, nside, F, lmax, _ptr(lut), _ptr(indices), M, fm.device.index,
+                                       _stream_ptr(fm.device))
+    check(rc, "dsph_sht_ring_synthesis")
+    return out
+
+
+def sht_chunk_maps(nside, lmax, F):
+    """Maps per trip of the compositions: the F_m scratch of a trip stays within ``SHT_CHUNK_BYTES`` and ``SHT_CHUNK_COLS`` columns,
+    but a trip always holds one whole map; where the limits allow, a count whose columns are a multiple of ``SHT_COL_BLOCK``."""
+    per_map = 16 * (int(lmax) + 1) * (4 * int(nside) - 1) * int(F)
+    step = max(1, min(SHT_CHUNK_BYTES // per_map, SHT_CHUNK_COLS // int(F)))
+    whole = [s for s in range(step, max(step - SHT_COL_BLOCK, 0), -1) if s * int(F) % SHT_COL_BLOCK == 0]
+    return whole[0] if whole else step  # (the largest count within the limits whose columns fill the kernels' blocks of 8)
+
+
+def sht_analysis(x, nside, lmax, indices=None, lut=None, out=None):
+    """``sht_legendre_analysis(sht_ring_analysis(x))``, the maps taken ``sht_chunk_maps`` at a time through one scratch array:
+    NEST maps (N, M, F) float32 -> complex128 (N, nalm, F), the quadrature with equal weights (healpy's map2alm with iter=0,
+    use_weights=False)."""
+    import torch
+
+    what = "sht_analysis"
+    nside, lmax = _sht_shape(what, nside, lmax)
+    N, M, F = _sht_map(what, x, nside, indices, lut)
+    out = _sht_out(what, out, x, torch.complex128, (N, sht_alm_size(lmax), F), "alm")
+    _sht_hip(what, x)
+    step = sht_chunk_maps(nside, lmax, F)
+    fm = None
+    for n0 in range(0, N, step):
+        n1 = min(n0 + step, N)
+        if fm is None or n1 - n0 != step:
+            fm = torch.empty(sht_fm_shape(nside, lmax, n1 - n0, F), dtype=torch.float64, device=x.device)
+        sht_ring_analysis(x[n0:n1], nside, lmax, indices, lut, out=fm)
+        sht_legendre_analysis(fm, nside, lmax, n1 - n0, F, out=out[n0:n1])
+    return out
+
+
+def sht_synthesis(alm, nside, indices=None, lut=None, out=None):
+    """``sht_ring_synthesis(sht_legendre_synthesis(alm))``, chunked like ``sht_analysis``: complex128 (N, nalm, F) -> NEST maps
+    (N, M, F) float32 (healpy's alm2map).  On a footprint only its rows exist."""
+    import torch
+
+    what = "sht_synthesis"
+    nside = int(nside)
+    N, lmax, F = _sht_alm(what, alm, nside)
+    _, M = _disc_set(what, nside, indices, lut, None)
+    if indices is not None and indices.device != alm.device:
+        raise ValueError(f"{what}: indices live on {indices.device}, alm on {alm.device}")
+    out = _sht_out(what, out, alm, torch.float32, (N, M, F), "the maps")
+    _sht_hip(what, alm)
+    step = sht_chunk_maps(nside, lmax, F)
+    fm = None
+    for n0 in range(0, N, step):
+        n1 = min(n0 + step, N)
+        if fm is None or n1 - n0 != step:
+            fm = torch.empty(sht_fm_shape(nside, lmax, n1 - n0, F), dtype=torch.float64, device=alm.device)
+        sht_legendre_synthesis(alm[n0:n1], nside, out=fm)
+        sht_ring_synthesis(fm, nside, lmax, n1 - n0, F, indices, lut, out=out[n0:n1])
+    return out
 
 
 def rows_layout(t):

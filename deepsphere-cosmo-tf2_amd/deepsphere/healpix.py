@@ -38,6 +38,14 @@ __all__ = [
     "rotation_matrix",
     "random_rotations",
     "rotation_stencil",
+    "alm_size",
+    "alm_index",
+    "legendre_lambda",
+    "map2alm",
+    "alm2map",
+    "alm2cl",
+    "anafast",
+    "almxfl",
     "neighbours",
     "kernel_width",
     "healpix_graph",
@@ -1164,3 +1172,204 @@ def rotation_stencil(nside, rot, indices=None):
         lut[ind] = np.arange(ind.shape[0], dtype=np.int64)
         pix = lut[pix]
     return pix, w
+
+
+# ----------------------------------------------------------------------------------------------
+# Spherical harmonic transforms, numpy, healpy's names (map2alm, alm2map, alm2cl, anafast, almxfl): the reference of the kernels
+# of csrc/healpix_sht.hip and what deepsphere/sht.py runs on CPU tensors.  Equal pixel weights (healpy with use_weights=False).
+# The Legendre functions come from the plain three-term recurrence in np.longdouble, whose exponent range (the 80-bit x87 format:
+# smallest normal 3e-4932) holds sin^m theta without the rescaling the kernel needs, so the two share no trick; sums over pixels,
+# rings and l run in float64.  NOTE: nest=True is this module's default everywhere; healpy's is nest=False.
+# ----------------------------------------------------------------------------------------------
+
+def alm_size(lmax):
+    """Number of coefficients of healpy's packed layout with mmax = lmax: (lmax + 1)(lmax + 2) / 2, like ``hp.Alm.getsize``."""
+    lmax = int(lmax)
+    if lmax < 0:
+        raise ValueError(f"lmax = {lmax} is negative")
+    return (lmax + 1) * (lmax + 2) // 2
+
+
+def alm_index(lmax, l, m):
+    """Index of a_lm (0 <= m <= l <= lmax) in healpy's packed layout, m-major: m (2 lmax + 1 - m) / 2 + l, like ``hp.Alm.getidx``."""
+    l, m = np.asarray(l, dtype=np.int64), np.asarray(m, dtype=np.int64)
+    return m * (2 * int(lmax) + 1 - m) // 2 + l
+
+
+def _alm_lmax(nalm):
+    lmax = (int(np.sqrt(8 * int(nalm) + 1)) - 3) // 2
+    if alm_size(lmax) != int(nalm):
+        raise ValueError(f"{nalm} coefficients are not (lmax + 1)(lmax + 2) / 2 for any lmax")
+    return lmax
+
+
+def _sht_lmax(nside, lmax):
+    lmax = 3 * nside - 1 if lmax is None else int(lmax)
+    if lmax < 0 or lmax > 4 * nside - 1:
+        raise ValueError(f"lmax = {lmax} outside [0, 4 nside - 1 = {4 * nside - 1}]")
+    return lmax
+
+
+def legendre_lambda(nside, m, lmax, dtype=np.float64):
+    """The normalised associated Legendre functions lambda_lm(cos theta) (Y_lm = lambda_lm e^{i m phi}) at the 4 nside - 1 rings of
+    ``nside`` for l = m .. lmax: -> [lmax + 1 - m, 4 nside - 1] in ``dtype``, computed in np.longdouble by
+    lambda_mm = (-1)^m sqrt((2 m + 1) / (4 pi) prod_{k <= m} (2 k - 1) / (2 k)) sin^m theta, lambda_{m+1,m} = x sqrt(2 m + 3) lambda_mm,
+    lambda_lm = a_lm (x lambda_{l-1,m} - lambda_{l-2,m} / a_{l-1,m}), a_lm = sqrt((4 l^2 - 1) / (l^2 - m^2)).  The northern rings and
+    the equator are computed, the southern ones follow from lambda_lm(pi - theta) = (-1)^(l + m) lambda_lm(theta)."""
+    nside, m, lmax = _check_nside(nside), int(m), int(lmax)
+    if not 0 <= m <= lmax:
+        raise ValueError(f"m = {m} outside [0, lmax = {lmax}]")
+    ld = np.longdouble
+    _, _, z, _, _ = _ring_info(nside, np.arange(1, 2 * nside + 1))
+    x = z.astype(ld)
+    st = np.sqrt(np.maximum(ld(0), (ld(1) - x) * (ld(1) + x)))
+    k = np.arange(1, m + 1, dtype=ld)
+    pref = np.sqrt(ld(2 * m + 1) / (ld(4) * ld(np.pi)) * np.prod((2 * k - 1) / (2 * k)))
+    out = np.empty((lmax + 1 - m, 4 * nside - 1), dtype=dtype)
+    sign = np.where((np.arange(m, lmax + 1) - m) & 1, -1.0, 1.0)
+    lam2 = np.zeros_like(x)
+    with np.errstate(under="ignore"):
+        lam1 = (ld(-1) if m & 1 else ld(1)) * pref * st ** m
+        a1 = ld(0)
+        for l in range(m, lmax + 1):
+            if l > m:
+                a = np.sqrt(ld(4 * l * l - 1) / ld(l * l - m * m))
+                lam1, lam2 = a * (x * lam1 - (lam2 / a1 if l > m + 1 else ld(0))), lam1
+                a1 = a
+            row = lam1.astype(dtype)
+            out[l - m, :2 * nside] = row
+            out[l - m, 2 * nside:] = sign[l - m] * row[2 * nside - 2::-1]
+    return out
+
+
+def _ring_phase0(nside):
+    """Per ring 1 .. 4 nside - 1: (nr, first RING index, e^{-i phi_0 m} as a function of m) ingredients: phi of the first pixel is
+    (1 - kshift) / (8 nr) of a turn, kshift = 1 - shifted."""
+    nr, shifted, _, _, first = _ring_info(nside, np.arange(1, 4 * nside))
+    return nr, 1 - shifted, first
+
+
+def _ring_transform(ringmaps, nside, lmax):
+    """F_m(ring) = sum_j x[ring, j] e^{-i m phi_j} of RING-ordered float64 maps [npix, F], m <= lmax: -> complex128 [lmax + 1, 4 nside - 1, F].
+    One FFT per ring; m at or above the ring's length folds onto m mod 4 nr; the phase of the ring's first pixel, m (1 - kshift) of
+    8 nr-ths of a turn, is reduced in integers."""
+    nr, kshift, first = _ring_phase0(nside)
+    m = np.arange(lmax + 1, dtype=np.int64)
+    F = ringmaps.shape[1]
+    out = np.empty((lmax + 1, 4 * nside - 1, F), dtype=np.complex128)
+    for r in range(4 * nside - 1):
+        n4 = 4 * int(nr[r])
+        f = np.fft.fft(ringmaps[first[r]:first[r] + n4], axis=0)
+        k0 = (m * (1 - int(kshift[r]))) % (2 * n4)
+        out[:, r] = f[m % n4] * np.exp(-2j * np.pi * (k0 / (2.0 * n4)))[:, None]
+    return out
+
+
+def _ring_synthesis(fm, nside):
+    """The transpose: RING-ordered float64 maps [npix, F] = Re sum_m c_m F_m(ring) e^{+i m phi_j}, c_0 = 1, c_m = 2."""
+    nr, kshift, first = _ring_phase0(nside)
+    lmax, F = fm.shape[0] - 1, fm.shape[2]
+    m = np.arange(lmax + 1, dtype=np.int64)
+    mult = np.where(m == 0, 1.0, 2.0)[:, None]
+    out = np.empty((12 * nside * nside, F), dtype=np.float64)
+    for r in range(4 * nside - 1):
+        n4 = 4 * int(nr[r])
+        k0 = (m * (1 - int(kshift[r]))) % (2 * n4)
+        g = np.zeros((n4, F), dtype=np.complex128)
+        np.add.at(g, m % n4, fm[:, r] * mult * np.exp(2j * np.pi * (k0 / (2.0 * n4)))[:, None])
+        out[first[r]:first[r] + n4] = np.fft.ifft(g, axis=0).real * n4
+    return out
+
+
+def _as_maps(maps, nest):
+    maps = np.asarray(maps, dtype=np.float64)
+    one = maps.ndim == 1
+    m2 = maps.reshape(maps.shape[0], -1) if not one else maps[:, None]
+    if maps.ndim > 2:
+        raise ValueError("maps must be (npix,) or (npix, F)")
+    nside = _check_nside(npix2nside(m2.shape[0]))
+    if nest:
+        m2 = m2[ring2nest(nside, np.arange(m2.shape[0], dtype=np.int64))]
+    return m2, nside, one
+
+
+def _analysis(ringmaps, nside, lmax):
+    """Plain quadrature with w = 4 pi / npix of RING-ordered [npix, F] maps -> complex128 [nalm, F]."""
+    fm = _ring_transform(ringmaps, nside, lmax)
+    w = 4.0 * np.pi / (12 * nside * nside)
+    alm = np.empty((alm_size(lmax), ringmaps.shape[1]), dtype=np.complex128)
+    for m in range(lmax + 1):
+        i0 = int(alm_index(lmax, m, m))
+        alm[i0:i0 + lmax + 1 - m] = w * (legendre_lambda(nside, m, lmax) @ fm[m])
+    return alm
+
+
+def _synthesis(alm, nside, lmax):
+    """RING-ordered float64 [npix, F] maps of complex128 [nalm, F] coefficients."""
+    fm = np.empty((lmax + 1, 4 * nside - 1, alm.shape[1]), dtype=np.complex128)
+    for m in range(lmax + 1):
+        i0 = int(alm_index(lmax, m, m))
+        fm[m] = legendre_lambda(nside, m, lmax).T @ alm[i0:i0 + lmax + 1 - m]
+    return _ring_synthesis(fm, nside)
+
+
+def map2alm(maps, lmax=None, iter=3, nest=True):  # noqa: A002  (healpy's argument name)
+    """The spherical harmonic coefficients of the map(s) ``maps`` ((npix,) or (npix, F)), like ``hp.map2alm(use_weights=False)``:
+    -> complex128 (nalm,) or (nalm, F) in healpy's packed layout (``alm_index``), mmax = lmax, lmax = 3 nside - 1 by default.
+    ``iter = 0``: the quadrature a_lm = w sum_p Y*_lm(p) x_p with equal weights w = 4 pi / npix; ``iter > 0`` adds healpy's Jacobi
+    steps alm += map2alm(map - alm2map(alm), iter=0).  ``nest=True`` (NEST-ordered input) is the default here and is NOT healpy's."""
+    m2, nside, one = _as_maps(maps, nest)
+    lmax = _sht_lmax(nside, lmax)
+    alm = _analysis(m2, nside, lmax)
+    for _ in range(int(iter)):
+        alm += _analysis(m2 - _synthesis(alm, nside, lmax), nside, lmax)
+    return alm[:, 0] if one else alm
+
+
+def alm2map(alm, nside, nest=True):
+    """The map(s) of the coefficients ``alm`` ((nalm,) or (nalm, F), packed, mmax = lmax), like ``hp.alm2map``: float64 (npix,) or
+    (npix, F); the m = 0 terms count once, the m > 0 terms as 2 Re.  ``nest=True`` (NEST-ordered output) is the default here and
+    is NOT healpy's."""
+    nside = _check_nside(nside)
+    alm = np.asarray(alm, dtype=np.complex128)
+    one = alm.ndim == 1
+    if alm.ndim > 2:
+        raise ValueError("alm must be (nalm,) or (nalm, F)")
+    a2 = alm[:, None] if one else alm
+    lmax = _alm_lmax(a2.shape[0])
+    _sht_lmax(nside, lmax)
+    out = _synthesis(a2, nside, lmax)
+    if nest:
+        out = out[nest2ring(nside, np.arange(out.shape[0], dtype=np.int64))]
+    return out[:, 0] if one else out
+
+
+def alm2cl(alm):
+    """The auto power spectrum C_l = (|a_l0|^2 + 2 sum_{m > 0} |a_lm|^2) / (2 l + 1) of packed ``alm`` ((nalm,) or (nalm, F)), like
+    ``hp.alm2cl``: float64 (lmax + 1,) or (lmax + 1, F)."""
+    alm = np.asarray(alm, dtype=np.complex128)
+    lmax = _alm_lmax(alm.shape[0])
+    p = alm.real ** 2 + alm.imag ** 2
+    cl = np.zeros((lmax + 1,) + alm.shape[1:], dtype=np.float64)
+    for m in range(lmax + 1):
+        i0 = int(alm_index(lmax, m, m))
+        cl[m:] += (1.0 if m == 0 else 2.0) * p[i0:i0 + lmax + 1 - m]
+    return cl / (2.0 * np.arange(lmax + 1).reshape((-1,) + (1,) * (alm.ndim - 1)) + 1.0)
+
+
+def anafast(maps, lmax=None, iter=3, nest=True):  # noqa: A002
+    """The auto power spectrum of the map(s), ``alm2cl(map2alm(maps, lmax, iter, nest))``, like ``hp.anafast(use_weights=False)`` for
+    one map.  ``nest=True`` is the default here and is NOT healpy's."""
+    return alm2cl(map2alm(maps, lmax=lmax, iter=iter, nest=nest))
+
+
+def almxfl(alm, fl):
+    """``alm`` ((nalm,) or (nalm, F)) with every a_lm multiplied by ``fl[l]`` (l beyond len(fl): by zero), like ``hp.almxfl``."""
+    alm = np.asarray(alm, dtype=np.complex128)
+    lmax = _alm_lmax(alm.shape[0])
+    fl = np.asarray(fl)
+    full = np.zeros(lmax + 1, dtype=fl.dtype)
+    n = min(lmax + 1, fl.shape[0])
+    full[:n] = fl[:n]
+    ls = np.concatenate([np.arange(m, lmax + 1) for m in range(lmax + 1)])
+    return alm * full[ls].reshape((-1,) + (1,) * (alm.ndim - 1))

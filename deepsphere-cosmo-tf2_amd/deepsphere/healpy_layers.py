@@ -1036,5 +1036,55 @@ class HealpyRotate(torch.nn.Module):
     call = forward
 
 
+class HealpyPowerSpectrum(torch.nn.Module):
+    """The angular auto power spectrum of NEST-ordered (batch, pixels, channels) maps, what ``hp.anafast`` computes on the host:
+    (N, M, F) -> (N, lmax + 1, F), C_l = (|a_l0|^2 + 2 sum_{m > 0} |a_lm|^2) / (2 l + 1) of every map and channel, in the input's
+    dtype.  A summary statistic, a loss term or the last layer of a ``HealpyGCNN`` (it has no ``p`` and no ``Fout``: the network
+    passes it through unchanged).
+
+    :param nside: nside of the maps (at most 2048)
+    :param indices: sorted NEST ids of a partial-sky map, None for the full sky.  On a footprint the result is the pseudo-C_l of
+        the zero-filled map: nothing is corrected for the mask
+    :param lmax: the largest multipole, 3 nside - 1 by default, at most 4 nside - 1
+    :param iter: healpy's Jacobi iterations of ``map2alm`` (0 here by default: the plain quadrature with equal pixel weights)
+
+    float32 maps on a HIP device run the kernels of ``csrc/healpix_sht.hip`` in float64 (``sht.map2alm``); other HIP dtypes are
+    converted to float32 first; CPU tensors run the numpy reference without autograd.  Differentiable on the device: at
+    ``iter = 0`` the backward is one synthesis, dx = w alm2map(b) with b_lm = 2 gC_l a_lm / (2 l + 1) and w = 4 pi / npix; with
+    ``iter > 0`` the composition of the transforms differentiates by itself."""
+
+    def __init__(self, nside, indices=None, lmax=None, iter=0):  # noqa: A002  (healpy's argument name)
+        super().__init__()
+        self.nside = int(nside)
+        if not healpix.isnsideok(self.nside):
+            raise ValueError(f"nside = {nside} is not a power of two >= 1")
+        if self.nside > _native.SHT_MAX_NSIDE:
+            raise ValueError(f"nside = {self.nside} is beyond the transform's limit of {_native.SHT_MAX_NSIDE}")
+        self.indices = healpix._index_set(self.nside, indices)  # None: the full sky
+        self.n_pix = healpix.nside2npix(self.nside) if self.indices is None else int(self.indices.size)
+        if self.n_pix < 1:
+            raise ValueError("an empty pixel set")
+        self.lmax = healpix._sht_lmax(self.nside, lmax)
+        self.iter = int(iter)
+        if self.iter < 0:
+            raise ValueError(f"iter = {iter} is negative")
+        self._footprint = None  # sht.Footprint of the set, with its device tables: built on first use
+
+    def forward(self, input_tensor):
+        from . import sht
+
+        x = _as_tensor(input_tensor)
+        if x.dim() != 3 or x.shape[1] != self.n_pix:
+            raise ValueError(f"HealpyPowerSpectrum: input of shape {tuple(x.shape)} has {x.shape[1] if x.dim() > 1 else 0} pixels, "
+                             f"the layer was built for {self.n_pix} (nside {self.nside})")
+        if self._footprint is None:
+            self._footprint = sht.Footprint(self.nside, self.indices)
+        x32 = x.to(torch.float32) if x.is_cuda else x
+        return sht.anafast(x32, self.nside, lmax=self.lmax, iter=self.iter, indices=self._footprint).to(x.dtype)
+
+    call = forward
+
+
 __all__ = ["HealpyPool", "HealpyPseudoConv", "HealpyPseudoConv_Transpose", "HealpyChebyshev", "HealpyMonomial", "HealpyBernstein",
-           "Healpy_ResidualLayer", "Healpy_Transformer", "Healpy_ViT", "HealpySmoothing", "HealpyReorder", "HealpyRotate"]
+           "Healpy_ResidualLayer", "Healpy_Transformer", "Healpy_ViT", "HealpySmoothing", "HealpyReorder", "HealpyRotate",
+           "HealpyPowerSpectrum"]

@@ -520,6 +520,45 @@ int dsph_healpix_rotate(const float* x, float* y, int64_t N, int32_t nside, int3
 int dsph_healpix_interp_table(int32_t nside, const double* rot, const int32_t* lut, const int64_t* indices, int64_t M, int32_t* cols,
                               float* vals, int device, void* hip_stream);
 
+/* Spherical harmonic transforms of scalar HEALPix maps in NEST order (plan-free; csrc/healpix_sht.hip).
+ * Replaces: hp.map2alm / hp.alm2map / hp.anafast on the host (copy, reorder to RING, seconds per map at nside 1024, no gradient).
+ * Equal pixel weights w = 4 pi / (12 nside^2) (healpy with use_weights=False), no iteration: healpy's `iter` is a composition of
+ * the two transforms and belongs to the caller.  Two stages each way, each an entry point of its own:
+ *   dsph_sht_ring_analysis       fm[m, ring, c]  = sum_j x[ring, j, c] e^{-i m phi_j}
+ *   dsph_sht_legendre_analysis   alm[n, (l, m), f] = w sum_ring lambda_lm(theta_ring) fm[m, ring, c]
+ *   dsph_sht_legendre_synthesis  fm[m, ring, c]  = sum_{l >= m} alm[n, (l, m), f] lambda_lm(theta_ring)
+ *   dsph_sht_ring_synthesis      y[ring, j, c]   = Re sum_m c_m fm[m, ring, c] e^{+i m phi_j},  c_0 = 1, c_m = 2 (m > 0)
+ * with c = n F + f the C = N F columns (map x channel), ring = 1 .. 4 nside - 1 from the north pole, lambda_lm the normalised
+ * associated Legendre functions (Y_lm = lambda_lm e^{i m phi}), mmax = lmax.
+ *   x, y   device (N, M, F) fp32, contiguous, any 4-byte alignment (read and written a float at a time)
+ *   fm     device float64 [mmax + 1][4 nside - 1][C][2], (re, im) pairs: 16 (mmax + 1)(4 nside - 1) bytes per column, 200 MB at
+ *          nside 1024 and mmax 3071 -- the caller's scratch, and the caller's to chunk over the maps
+ *   alm    device float64 [N][nalm][F][2], healpy's packed layout: index m (2 lmax + 1 - m) / 2 + l, nalm = (lmax + 1)(lmax + 2) / 2
+ *          (a torch complex128 tensor (N, nalm, F))
+ *   lut, indices, M   the footprint as for dsph_healpix_rotate; NULL, NULL and M = 12 nside^2: the full sky.  Analysis counts a
+ *          pixel outside the footprint as zero; synthesis writes the footprint's rows and nothing else.  `indices` itself is not
+ *          read (the rings are walked through lut)
+ * float64 throughout: the ring phase m phi_j is reduced exactly in integers (m (2 j - 1 - kshift) mod 8 nr) before the sine and
+ * cosine, every 16th term; the terms between by a rotation with the equally reduced step.  A direct DFT: m above a ring's Nyquist
+ * needs no folding.  The Legendre recurrence in l carries an integer scale beside its value (steps of 2^480), so that
+ * lambda_mm = O(sin^m theta) may start hundreds of orders below float64's range; a term on a negative scale (below 2^-240 of a
+ * function of order 1) is dropped.  lambda_lm(pi - theta) = (-1)^(l + m) lambda_lm(theta) halves the recurrences.  Deterministic:
+ * no atomics, one writer per element, the sums over rings and over l in a fixed order.  Grids: (ring, blocks of m or of pixels,
+ * min(blocks of 8 columns, 4096)) and (m, min(blocks of 8 columns, 4096)); further columns on further trips; 64-bit offsets.
+ *
+ * nside a power of two, 1 <= nside <= 2048 (DSPH_E_UNSUPPORTED beyond), 0 <= lmax = mmax <= 4 nside - 1, F >= 1, N >= 0 (N = 0:
+ * DSPH_OK, no launch).  Bad arguments (a required pointer NULL, fm or alm not 8-byte aligned, indices without lut or the reverse,
+ * M != 12 nside^2 without indices, M outside [0, 12 nside^2], nside not a power of two, lmax out of range, F < 1, N < 0, input
+ * overlapping output): DSPH_E_BADARG before any launch.  All four only enqueue on `hip_stream`. */
+int dsph_sht_ring_analysis(const float* x, double* fm, int64_t N, int32_t nside, int32_t F, int32_t mmax, const int32_t* lut,
+                           const int64_t* indices, int64_t M, int device, void* hip_stream);
+int dsph_sht_legendre_analysis(const double* fm, double* alm, int64_t N, int32_t nside, int32_t F, int32_t lmax, int device,
+                               void* hip_stream);
+int dsph_sht_legendre_synthesis(const double* alm, double* fm, int64_t N, int32_t nside, int32_t F, int32_t lmax, int device,
+                                void* hip_stream);
+int dsph_sht_ring_synthesis(const double* fm, float* y, int64_t N, int32_t nside, int32_t F, int32_t mmax, const int32_t* lut,
+                            const int64_t* indices, int64_t M, int device, void* hip_stream);
+
 /* Attention over the edges of the pixel graph (plan-free; csrc/nbr_attention.hip).
  * Replaces: gnn_transformers.scaled_dot_product_sparse_attention (reference gnn_transformers.py:54-106: three embedding lookups that
  * materialise q, k, v per edge, exp, two segment sums) and the split_heads transposes around it (:189-196, :225-231).
