@@ -332,6 +332,8 @@ static int istrip_nseg(const dsph_plan* plan, const FusedTiles& ft, int64_t N, i
 // forked: this launch is one half of a forked forward.
 static Route make_route(const dsph_plan* plan, const FusedTiles& ft, const FusedRequest& q, bool forked) {
   const bool fwd = q.mode == Mode::forward, y_aligned = (reinterpret_cast<uintptr_t>(q.y) & 15) == 0;
+  // (both quad-strip kernels load their four bias values per lane as one 16-byte piece; every other kernel reads bias by the element)
+  const bool bias_aligned = (reinterpret_cast<uintptr_t>(q.bias) & 15) == 0;
   const bool plain_epilogue = q.act == DSPH_ACT_NONE || q.act == DSPH_ACT_RELU;
   Route rt{ft};
   rt.has_struct = fwd && has_struct_tiles(ft);
@@ -340,14 +342,14 @@ static Route make_route(const dsph_plan* plan, const FusedTiles& ft, const Fused
   // and x with the same channel count; all of them store y in 16-byte pieces); the class-R list shrinks to the rest
   const bool quad = use_qstrips(plan, ft, q);
   rt.strips = Strips::none;
-  if (fwd && strips_apply(plan, ft, q, quad) && q.Fin_w == q.Fin && y_aligned) rt.strips = quad ? Strips::quad : Strips::pairs;
+  if (fwd && strips_apply(plan, ft, q, quad) && q.Fin_w == q.Fin && y_aligned && (!quad || bias_aligned)) rt.strips = quad ? Strips::quad : Strips::pairs;
   else if (fwd && istrips_apply(plan, ft, q) && y_aligned) rt.strips = Strips::input;
   rt.run_strips = rt.strips != Strips::none && q.part != 2;
   // (the quad strips took class-T tiles too: their own rest lists)
   rt.r = rt.strips == Strips::quad ? &ft.qrrest : (rt.strips != Strips::none ? &ft.rrest : &ft.r);
   rt.t = rt.strips == Strips::quad ? &ft.qt : &ft.t;
   // K = 8, 32 -> 32: the rectangles of depth-7 regular tiles on the quad strips, the rest of the tiles on the BFS-tile kernel
-  rt.q8 = fwd && q.part != 2 && !q.pool && !forked && q.Fin_w == q.Fin && q.beta_rest != 0.f && plain_epilogue && y_aligned && q8_applies(plan, ft, q);
+  rt.q8 = fwd && q.part != 2 && !q.pool && !forked && q.Fin_w == q.Fin && q.beta_rest != 0.f && plain_epilogue && y_aligned && bias_aligned && q8_applies(plan, ft, q);
   // part: 0 all tiles, 1 interior tiles (no row of another rank in their region), 2 boundary tiles
   // the BFS-tile kernel handles the tiles of ft.part (every tile of a full table, the class-G ones otherwise)
   rt.bfs_tiles = q.part == 0 && ft.part.n == ft.ntiles ? nullptr : ft.part.ptr(q.part);
@@ -485,6 +487,13 @@ static int32_t bfs_arithmetic(int32_t precision) {
   return struct_arithmetic(precision) == DSPH_PREC_BF16X6 ? DSPH_PREC_FP32 : precision;
 }
 
+// The refusal of a pointer that the fused kernels would load or store in 16-byte pieces: it names the pointer and the requirement.
+static bool misaligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
+static int refuse_misaligned(const char* who) {
+  set_error("cheb_fused: %s must be 16-byte aligned (the fused kernels access it in 16-byte pieces; DSPH_ALGO_UNFUSED takes any 4-byte-aligned pointer)", who);
+  return DSPH_E_BADARG;
+}
+
 // What every launch checks first: the shape runs on these tables (ft: tiles_for), the block's images fit, the pointers the
 // kernels load and store in 16-byte pieces are aligned (out: the planes, or the slabs of the weight gradient).
 static int check_request(const FusedRequest& rq, const FusedTiles* ft, size_t ws_bytes, size_t ws_need, const void* out) {
@@ -496,10 +505,8 @@ static int check_request(const FusedRequest& rq, const FusedTiles* ft, size_t ws
     set_error("cheb_fused: workspace %zu < %zu", ws_bytes, ws_need);
     return DSPH_E_WORKSPACE;
   }
-  if ((reinterpret_cast<uintptr_t>(rq.x) & 15) || (reinterpret_cast<uintptr_t>(rq.ws) & 15) || (reinterpret_cast<uintptr_t>(out) & 15)) {
-    set_error("cheb_fused: x, workspace and planes must be 16-byte aligned");
-    return DSPH_E_BADARG;
-  }
+  const char* who = misaligned(rq.x) ? "x" : misaligned(rq.ws) ? "the workspace" : misaligned(out) ? (rq.mode == Mode::planes ? "planes" : "the workspace") : nullptr;
+  if (who) return refuse_misaligned(who);
   return DSPH_OK;
 }
 
@@ -766,16 +773,21 @@ int launch_cheb_fused(const dsph_plan* plan, const float* x, const float* w, con
                       float* y, int64_t N, int32_t Fin, int32_t Fout, int32_t K, int32_t act,
                       int32_t precision, float alpha_rest, float beta_rest, void* workspace,
                       size_t workspace_bytes, hipStream_t stream, int32_t part, bool keep_weights, const FusedPool* pool) {
-  if (pool != nullptr && !(part == 0 && fused_pool_ok(plan, N, Fin, Fout, K, act) && pool->y != nullptr && (pool->type == 1 || pool->type == 2) &&
-                           ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(pool->y)) & 15) == 0)) {
+  if (pool != nullptr && !(part == 0 && fused_pool_ok(plan, N, Fin, Fout, K, act) && pool->y != nullptr && (pool->type == 1 || pool->type == 2))) {
     set_error("cheb_fused: this plan / shape has no fused pooling (whole unsharded maps, no or ReLU activation, not the Clenshaw strips' shape)");
     return DSPH_E_UNSUPPORTED;
   }
+  // (the pooled stores are 16 bytes wide in every kernel, and the route is that of an aligned y)
+  if (pool != nullptr && misaligned(pool->y)) return refuse_misaligned("y_pooled");
+  if (pool != nullptr && misaligned(y)) return refuse_misaligned("y_scratch");
   const LayerWorkspace lw(plan, N, Fin, Fout, K);
   if (!workspace || workspace_bytes < lw.total) {
     set_error("cheb_fused: workspace %zu < %zu", workspace_bytes, lw.total);
     return DSPH_E_WORKSPACE;
   }
+  // before the first launch (the padded copy of x below is stored in 16-byte pieces; an x with Fin % 4 != 0 is read by the element)
+  if (misaligned(workspace)) return refuse_misaligned("the workspace");
+  if (Fin == pad4(Fin) && misaligned(x)) return refuse_misaligned("x");
   unsigned char* ws = static_cast<unsigned char*>(workspace);
   // Fin not a multiple of four: a zero-padded copy of x behind the weight images in the workspace (with a two-part
   // launch both parts copy: the halo rows arrive between them)

@@ -191,6 +191,10 @@ int launch_split_forward(const dsph_plan* p, const float* x, const float* w, con
   if (!split_layout(p, N, Fin, Fout, K, precision, &s, &lay)) { set_error("split_forward: K = %d does not split", K); return DSPH_E_UNSUPPORTED; }
   if (!workspace || workspace_bytes < lay.total) { set_error("split_forward: workspace %zu bytes, need %zu", workspace_bytes, lay.total); return DSPH_E_WORKSPACE; }
   if (reinterpret_cast<uintptr_t>(workspace) & 15) { set_error("split_forward: the workspace must be 16-byte aligned"); return DSPH_E_BADARG; }
+  if (Fin % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15)) {  // (said before the weight kernels below run: the deepest pass would refuse it)
+    set_error("split_forward: x must be 16-byte aligned (the fused kernels access it in 16-byte pieces; DSPH_ALGO_UNFUSED takes any 4-byte-aligned pointer)");
+    return DSPH_E_BADARG;
+  }
   unsigned char* ws = static_cast<unsigned char*>(workspace);
   const bool cheb = basis == DSPH_BASIS_CHEBYSHEV;
   const float alpha_rest = cheb ? 2.f : 1.f, beta_rest = cheb ? 1.f : 0.f;

@@ -486,7 +486,10 @@ int dsph_cheb_planes(const dsph_plan* p, const float* x, float* planes, int64_t 
     set_error("cheb_planes: fused kernel cannot run this plan/shape (Fin=%d K=%d)", Fin, K);
     return DSPH_E_UNSUPPORTED;
   }
-  if (can_fuse && algo != DSPH_ALGO_UNFUSED)
+  // (the fused kernel loads x and stores the planes in 16-byte pieces: DSPH_ALGO_AUTO takes the step kernels below, which choose
+  // their scalar form per pointer, when either is off 16-byte alignment -- no workspace depends on the choice; DSPH_ALGO_FUSED is refused)
+  const bool aligned = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(planes)) & 15) == 0;
+  if (can_fuse && algo != DSPH_ALGO_UNFUSED && (aligned || algo == DSPH_ALGO_FUSED))
     return launch_cheb_fused_planes(p, x, planes, N, Fin, K, alpha_rest, beta_rest, stream);
   // one gather launch per step (any L, any Fin)
   const size_t plane = (size_t)N * (size_t)p->n_cols * (size_t)Fin;
@@ -555,6 +558,16 @@ int dsph_cheb_backward_weights(const dsph_plan* p, const float* x, const float* 
   if (can_fuse && algo != DSPH_ALGO_UNFUSED) {
     DeviceGuard guard(p->device);
     const size_t slab_bytes = align_up(fused_wgrad_workspace_bytes(p, Fp, Fout, K), 256);
+    // before the first launch: the slabs and the padded copy of x are stored, an x of whole groups of four channels is loaded, in
+    // 16-byte pieces (the workspace query has no pointers: the route cannot follow them, so this is a refusal)
+    if (reinterpret_cast<uintptr_t>(workspace) & 15) {
+      set_error("backward_weights: the workspace must be 16-byte aligned (the fused kernels access it in 16-byte pieces)");
+      return DSPH_E_BADARG;
+    }
+    if (Fp == Fin && (reinterpret_cast<uintptr_t>(x) & 15)) {
+      set_error("backward_weights: x must be 16-byte aligned (the fused kernels access it in 16-byte pieces; DSPH_ALGO_UNFUSED takes any 4-byte-aligned pointer)");
+      return DSPH_E_BADARG;
+    }
     if (Fp != Fin) {
       float* xp = reinterpret_cast<float*>(static_cast<char*>(workspace) + slab_bytes);
       const int rc = launch_fused_pad(x, xp, N * p->n_cols, Fin, Fp, stream);
@@ -563,7 +576,9 @@ int dsph_cheb_backward_weights(const dsph_plan* p, const float* x, const float* 
     }
     // K = 5, 64 -> 64 j in the three-term arithmetic on a map the forward runs on the quad strips: their pixels on the
     // quad-strip weight-gradient kernel (cheb_qwgrad.hip), the other tiles on the BFS-tile kernel
-    if (Fp == Fin && fused_qwgrad_applies(p, N, Fin, Fout, K, precision))
+    // (that kernel loads dy, too, in 16-byte pieces, Fout % 64 == 0: a dy off alignment goes to the BFS-tile kernel on every tile,
+    // which reads dy by the element -- the workspace holds its slabs either way)
+    if (Fp == Fin && (reinterpret_cast<uintptr_t>(dy) & 15) == 0 && fused_qwgrad_applies(p, N, Fin, Fout, K, precision))
       return launch_cheb_fused_qwgrad(p, x, dy, dw, N, Fin, Fout, K, alpha_rest, beta_rest, workspace, slab_bytes, stream);
     return launch_cheb_fused_wgrad(p, x, dy, dw, N, Fp, Fout, K, precision, alpha_rest, beta_rest, workspace, slab_bytes, stream, Fin);
   }

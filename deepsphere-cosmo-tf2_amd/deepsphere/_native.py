@@ -358,6 +358,35 @@ def _nbytes(t):
     return t.numel() * t.element_size()
 
 
+def _aligned16(t):
+    """``t`` itself when its first element sits on a 16-byte boundary, else a copy in an allocation of its own (which does).
+    The fused Chebyshev kernels load x -- and the quad-strip weight gradient dy -- in 16-byte pieces and the C ABI refuses
+    such a pointer off alignment (the workspace query has no pointers, so it cannot change the route for one)."""
+    import torch
+
+    if t.data_ptr() % 16 == 0:
+        return t
+    c = torch.empty(t.shape, dtype=t.dtype, device=t.device)
+    c.copy_(t)
+    assert c.data_ptr() % 16 == 0
+    return c
+
+
+def _fused_x(plan, x, Fin, Fout, K, algo):
+    """x for a forward: an aligned copy (``_aligned16``) only where the call takes the fused kernels and they read x itself -- not
+    with ALGO_UNFUSED or on a plan / shape the unfused kernels run (they have scalar forms), and not with Fin % 4 != 0, where the
+    kernels read a padded copy in the workspace."""
+    if algo == ALGO_UNFUSED or Fin % 4 != 0 or x.data_ptr() % 16 == 0 or not plan.fused_ok(Fin, Fout, K):
+        return x
+    return _aligned16(x)
+
+
+def _check_out(out, plan, shape, name="out"):
+    _check_dev(out, plan, name)
+    if tuple(out.shape) != tuple(shape):
+        raise ValueError(f"{name} has the wrong shape: {tuple(out.shape)}, expected {tuple(shape)}")
+
+
 def _ensure_workspace(need, device, workspace, floor=0, same_device=False):
     """The caller's scratch buffer when it holds ``need`` bytes (``same_device``: and lives on ``device``), else a new one of
     max(need, floor) bytes: -> (buffer, whether it was replaced)."""
@@ -374,7 +403,9 @@ def cheb_forward(plan, x, w, bias, K, act=ACT_NONE, precision=PREC_FP32, algo=AL
     ``part``: PART_ALL, or PART_INTERIOR / PART_BOUNDARY (fused kernel only) to write only the tiles that do not /
     do touch halo rows -- pass the same ``out`` to both calls.
     ``keep_weights``: the caller vouches that ``workspace`` was last used by a call with the same weight values, shape,
-    basis and precision (DSPH_FWD_KEEP_WEIGHTS: no weight-preparation launches); dropped when the workspace is replaced."""
+    basis and precision (DSPH_FWD_KEEP_WEIGHTS: no weight-preparation launches); dropped when the workspace is replaced.
+    Every contiguous float32 tensor is accepted: an ``x`` off 16-byte alignment is replaced by an aligned copy where -- and only
+    where -- the call runs on the fused kernels, which the C ABI would refuse (``_fused_x``); w, bias and out need 4 bytes only."""
     import torch
 
     _check_dev(x, plan, "x")
@@ -385,6 +416,7 @@ def cheb_forward(plan, x, w, bias, K, act=ACT_NONE, precision=PREC_FP32, algo=AL
     if w.shape[0] != Fin * K:
         raise ValueError(f"w has {w.shape[0]} rows, expected Fin*K = {Fin * K}")
     Fout = int(w.shape[1])
+    x = _fused_x(plan, x, int(Fin), Fout, int(K), algo)
     if bias is not None:
         _check_dev(bias, plan, "bias")
         if bias.numel() != Fout:
@@ -397,9 +429,7 @@ def cheb_forward(plan, x, w, bias, K, act=ACT_NONE, precision=PREC_FP32, algo=AL
     if out is None:
         out = torch.empty((N, orows, Fout), dtype=torch.float32, device=x.device)
     else:
-        _check_dev(out, plan, "out")
-        if tuple(out.shape) != (N, orows, Fout):
-            raise ValueError("out has the wrong shape")
+        _check_out(out, plan, (N, orows, Fout))
     rc = lib().dsph_poly_forward_ex(
         plan.handle, _ptr(x), _ptr(w), _ptr(bias), _ptr(out), int(N), int(Fin), Fout, int(K), int(basis), int(act),
         int(precision), int(algo), int(part), FWD_KEEP_WEIGHTS if (keep_weights and need > 0) else 0,
@@ -416,20 +446,26 @@ def pool_fusable(plan, N, Fin, Fout, K, act=ACT_NONE):
 
 
 def cheb_forward_pool(plan, x, w, bias, K, pool_type=POOL_MAX, act=ACT_NONE, precision=PREC_FP32, workspace=None,
-                      basis=BASIS_CHEBYSHEV, keep_weights=False):
+                      basis=BASIS_CHEBYSHEV, keep_weights=False, out=None):
     """pool(act(conv(x) + bias)) with HealpyPool(p = 1) reduced in the kernels' store step (``dsph_poly_forward_pool``):
-    -> (y_pooled (N, rows / 4, Fout), workspace).  The full-resolution output is never written."""
+    -> (y_pooled (N, rows / 4, Fout), workspace).  The full-resolution output is never written.
+    An ``x`` off 16-byte alignment is replaced by an aligned copy (``_fused_x``: this call is the fused kernels' only);
+    ``out``: the pooled map's tensor, 16-byte aligned (the pooled stores are 16 bytes wide: the C ABI refuses another)."""
     import torch
 
     _check_dev(x, plan, "x")
     _check_dev(w, plan, "w")
     N, rows, Fin = x.shape
     Fout = int(w.shape[1])
+    x = _fused_x(plan, x, int(Fin), Fout, int(K), ALGO_FUSED)
     need = plan.workspace_bytes(N, Fin, Fout, K, precision, ALGO_FUSED)
     if need > 0:
         workspace, replaced = _ensure_workspace(need, x.device, workspace)
         keep_weights = keep_weights and not replaced
-    out = torch.empty((N, rows // 4, Fout), dtype=torch.float32, device=x.device)
+    if out is None:
+        out = torch.empty((N, rows // 4, Fout), dtype=torch.float32, device=x.device)
+    else:
+        _check_out(out, plan, (N, rows // 4, Fout))
     rc = lib().dsph_poly_forward_pool(
         plan.handle, _ptr(x), _ptr(w), _ptr(bias), _c_vp(), _ptr(out), int(N), int(Fin), Fout, int(K), int(basis), int(act),
         int(precision), int(pool_type), FWD_KEEP_WEIGHTS if (keep_weights and need > 0) else 0,
@@ -458,15 +494,19 @@ def cheb_step(plan, inp, prev, alpha, beta, rows=0, out=None):
     return out
 
 
-def cheb_contract(planes, w, bias, rows, K, act=ACT_NONE, precision=PREC_FP32):
-    """Contraction over a list of K (N, plane_rows, Fin) planes -> (N, rows, Fout)."""
+def cheb_contract(planes, w, bias, rows, K, act=ACT_NONE, precision=PREC_FP32, out=None):
+    """Contraction over a list of K (N, plane_rows, Fin) planes -> (N, rows, Fout).  Planes, w, bias and ``out`` (the result's
+    tensor) may sit at any 4-byte alignment: the launch picks the kernels' scalar forms per pointer."""
     import torch
 
     p0 = planes[0]
     N, plane_rows, Fin = p0.shape
     Fout = int(w.shape[1])
     arr = (_c_vp * K)(*[p.data_ptr() for p in planes])
-    out = torch.empty((N, rows, Fout), dtype=torch.float32, device=p0.device)
+    if out is None:
+        out = torch.empty((N, rows, Fout), dtype=torch.float32, device=p0.device)
+    elif tuple(out.shape) != (N, rows, Fout) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != p0.device:
+        raise ValueError(f"out must be a contiguous float32 ({N}, {rows}, {Fout}) tensor on {p0.device}")
     rc = lib().dsph_cheb_contract(ctypes.cast(arr, _c_vp), int(plane_rows), _ptr(w), _ptr(bias), _ptr(out), int(N),
                                   int(rows), int(Fin), Fout, int(K), int(act), int(precision), p0.device.index,
                                   _stream_ptr(p0.device))
@@ -474,9 +514,12 @@ def cheb_contract(planes, w, bias, rows, K, act=ACT_NONE, precision=PREC_FP32):
     return out
 
 
-def cheb_planes(plan, x, K, basis=BASIS_CHEBYSHEV, algo=ALGO_AUTO):
+def cheb_planes(plan, x, K, basis=BASIS_CHEBYSHEV, algo=ALGO_AUTO, out=None):
     """[x, T_1 x, ..., T_{K-1} x]: the recurrence without the contraction (``dsph_cheb_planes``).
-    Every plane has x's shape (N, n_cols, Fin) and is valid on the plan's output rows."""
+    Every plane has x's shape (N, n_cols, Fin) and is valid on the plan's output rows.
+    ``out``: the (K - 1, N, n_cols, Fin) tensor the planes 1 .. K - 1 are written to.  With ALGO_AUTO an ``x`` or ``out`` off
+    16-byte alignment runs on the step kernels (the C ABI's choice: no workspace depends on it); with ALGO_FUSED an ``x`` off
+    alignment is replaced by an aligned copy and such an ``out`` is refused."""
     import torch
 
     _check_dev(x, plan, "x")
@@ -485,16 +528,25 @@ def cheb_planes(plan, x, K, basis=BASIS_CHEBYSHEV, algo=ALGO_AUTO):
     N, M, Fin = x.shape
     if K <= 1:
         return [x]
-    out = torch.empty((K - 1, N, M, Fin), dtype=torch.float32, device=x.device)
+    if out is None:
+        out = torch.empty((K - 1, N, M, Fin), dtype=torch.float32, device=x.device)
+    else:
+        _check_out(out, plan, (K - 1, N, M, Fin))
+    x0 = x
+    if algo == ALGO_FUSED:
+        x = _aligned16(x)
     rc = lib().dsph_cheb_planes(plan.handle, _ptr(x), _ptr(out), int(N), int(Fin), int(K), int(basis), int(algo),
                                 _stream_ptr(x.device))
     check(rc, "dsph_cheb_planes")
-    return [x] + [out[k] for k in range(K - 1)]
+    return [x0] + [out[k] for k in range(K - 1)]
 
 
-def cheb_backward_weights(plan, x, dy, K, basis=BASIS_CHEBYSHEV, algo=ALGO_AUTO, workspace=None, precision=PREC_FP32):
+def cheb_backward_weights(plan, x, dy, K, basis=BASIS_CHEBYSHEV, algo=ALGO_AUTO, workspace=None, precision=PREC_FP32, out=None):
     """dkernel[f*K + k, o] = sum_{n,m} (T_k x)[n,m,f] dy[n,m,o] (``dsph_cheb_backward_weights``).
-    Returns (dkernel, workspace)."""
+    Returns (dkernel, workspace).  ``out``: the (Fin*K, Fout) tensor dkernel is written to (any 4-byte alignment).
+    Unless ALGO_UNFUSED is asked for, an ``x`` with Fin % 4 == 0 off 16-byte alignment is replaced by an aligned copy (the fused
+    kernels, where the plan has them, would refuse it), and so is such a ``dy`` of the quad-strip gradient's shape (K = 5,
+    64 -> 64 j, three-term bf16), which the C ABI would otherwise hand to the slower BFS-tile kernel."""
     import torch
 
     _check_dev(x, plan, "x")
@@ -503,9 +555,18 @@ def cheb_backward_weights(plan, x, dy, K, basis=BASIS_CHEBYSHEV, algo=ALGO_AUTO,
     if M != plan.n_cols or dy.dim() != 3 or dy.shape[0] != N or dy.shape[1] != plan.out_rows:
         raise ValueError(f"x must be (N, {plan.n_cols}, Fin) and dy (N, {plan.out_rows}, Fout)")
     Fout = int(dy.shape[2])
+    if algo != ALGO_UNFUSED:
+        if Fin % 4 == 0:
+            x = _aligned16(x)
+        if K == 5 and Fin == 64 and Fout % 64 == 0 and precision == PREC_BF16X3:
+            dy = _aligned16(dy)
     need = int(lib().dsph_backward_weights_workspace_bytes(plan.handle, int(N), int(Fin), Fout, int(K), int(algo)))
     workspace, _ = _ensure_workspace(need, x.device, workspace, floor=16, same_device=True)
-    dw = torch.empty((Fin * K, Fout), dtype=torch.float32, device=x.device)
+    if out is None:
+        dw = torch.empty((Fin * K, Fout), dtype=torch.float32, device=x.device)
+    else:
+        _check_out(out, plan, (Fin * K, Fout))
+        dw = out
     rc = lib().dsph_cheb_backward_weights(plan.handle, _ptr(x), _ptr(dy), _ptr(dw), int(N), int(Fin), Fout, int(K),
                                           int(basis), int(precision), int(algo), _ptr(workspace),
                                           _nbytes(workspace), _stream_ptr(x.device))
@@ -513,8 +574,9 @@ def cheb_backward_weights(plan, x, dy, K, basis=BASIS_CHEBYSHEV, algo=ALGO_AUTO,
     return dw, workspace
 
 
-def cheb_wgrad(planes, dy, rows=None, workspace=None):
-    """dw[f*K + k, o] = sum_{n,m} planes[k][n,m,f] * dy[n,m,o] for a list of K (N, plane_rows, Fin) planes."""
+def cheb_wgrad(planes, dy, rows=None, workspace=None, out=None):
+    """dw[f*K + k, o] = sum_{n,m} planes[k][n,m,f] * dy[n,m,o] for a list of K (N, plane_rows, Fin) planes.
+    Every pointer may sit at any 4-byte alignment (the kernels read and write by the element); ``out``: dw's tensor."""
     import torch
 
     p0 = planes[0]
@@ -524,7 +586,12 @@ def cheb_wgrad(planes, dy, rows=None, workspace=None):
     Fout = int(dy.shape[2])
     need = int(lib().dsph_wgrad_workspace_bytes(int(N), rows, int(Fin), Fout, K))
     workspace, _ = _ensure_workspace(need, p0.device, workspace)
-    dw = torch.empty((Fin * K, Fout), dtype=torch.float32, device=p0.device)
+    if out is None:
+        dw = torch.empty((Fin * K, Fout), dtype=torch.float32, device=p0.device)
+    elif tuple(out.shape) != (Fin * K, Fout) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != p0.device:
+        raise ValueError(f"out must be a contiguous float32 ({Fin * K}, {Fout}) tensor on {p0.device}")
+    else:
+        dw = out
     arr = (_c_vp * K)(*[p.data_ptr() for p in planes])
     rc = lib().dsph_cheb_wgrad(ctypes.cast(arr, _c_vp), int(plane_rows), _ptr(dy), _ptr(dw), int(N), rows, int(Fin),
                                Fout, K, _ptr(workspace), _nbytes(workspace),

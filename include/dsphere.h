@@ -248,7 +248,34 @@ int dsph_plan_strip_rows(const dsph_plan* plan, int32_t K, int64_t strip, int64_
  * the image of that basis if the plan has none yet; DSPH_E_UNSUPPORTED without quad strips or with the option off. */
 int dsph_plan_strip_image(const dsph_plan* plan, int32_t basis, int64_t strip, float* out, int64_t capacity, int64_t* n_floats);
 
-/* Bytes of scratch dsph_cheb_forward needs for this call shape (0 is possible). */
+/* Pointer and workspace contract of the Chebyshev family (dsph_cheb_forward / dsph_poly_forward*, dsph_poly_forward_pool,
+ * dsph_cheb_planes, dsph_cheb_step, dsph_cheb_contract, dsph_cheb_backward_weights, dsph_cheb_wgrad).  Every device pointer is a
+ * contiguous fp32 array, 4-byte aligned at least.  A pointer that a kernel of the call would access in 16-byte pieces is
+ * checked on the host first: the call then either takes a kernel that accesses it by the element (same values, to rounding where
+ * the other kernel sums in another order) or returns DSPH_E_BADARG before anything is launched, with a message that names the
+ * pointer and the requirement.  Per entry point, "any" = any 4-byte alignment:
+ *   unfused route (DSPH_ALGO_UNFUSED, or DSPH_ALGO_AUTO on a plan / shape without fused kernels), dsph_cheb_step,
+ *   dsph_cheb_contract, dsph_cheb_wgrad: x / in / prev / out / planes[k] / w / bias / y / dy / dw any (16-byte accesses where the
+ *       channel count is a multiple of four and the pointer aligned, chosen per launch; a y off alignment with Fout % 4 == 0 is
+ *       contracted by the exact-fp32 kernels instead of the MFMA one); the workspace any.
+ *   fused route (DSPH_ALGO_FUSED, or DSPH_ALGO_AUTO where dsph_plan_fused_ok, the chain of passes of K > 5 included):
+ *       x      16-byte aligned when Fin % 4 == 0 (refused otherwise: DSPH_ALGO_AUTO resolves the route from plan and shape alone,
+ *              as dsph_workspace_bytes must, and does not fall back); any when Fin % 4 != 0 (the kernels read a padded copy)
+ *       w      any (read by the element into the packed weight images)
+ *       bias   any; off 16-byte alignment the tiles of the quad-strip kernels (K = 5, 64 -> 64 j; K = 8, 32 -> 32) run on the tile kernels
+ *       y      any; off 16-byte alignment the tiles of every strip kernel run on the tile kernels, which then store by the element
+ *       y_pooled, y_scratch (dsph_poly_forward_pool)  16-byte aligned (refused otherwise; y_scratch may be NULL)
+ *       planes (dsph_cheb_planes)  16-byte aligned, as x; DSPH_ALGO_AUTO runs the dsph_cheb_step kernels when x or planes is not
+ *              (no workspace depends on the choice), DSPH_ALGO_FUSED refuses
+ *       dy     any; off 16-byte alignment the quad-strip weight gradient's pixels go to the tile kernel (same workspace)
+ *       dw     any
+ *       workspace  16-byte aligned (refused otherwise), at least the bytes of the size query: weight images, the padded copy of x,
+ *              the buffers of the chain of passes, the slabs of the weight gradient all lie inside them.
+ * No call writes to x, w, bias or dy, or outside y / y_pooled / planes / dw and the queried bytes of the workspace
+ * (tests/test_gpu_cheb_memory.py holds every route to this with guard bands and checksums). */
+
+/* Bytes of scratch dsph_cheb_forward needs for this call shape (0 is possible).  It has no pointers to look at: the route it sizes
+ * is a function of plan, shape and algo alone, and the forward keeps to that route. */
 size_t dsph_workspace_bytes(const dsph_plan* plan, int64_t N, int32_t Fin, int32_t Fout,
                             int32_t K, int32_t precision, int32_t algo);
 
@@ -265,7 +292,10 @@ size_t dsph_workspace_bytes(const dsph_plan* plan, int64_t N, int32_t Fin, int32
  * act(BN(conv) + bias) from this one call (deepsphere/gnn_layers.py does, keyed on the versions of the statistics); with
  * batch statistics (training) a layer calls this with bias=NULL, act=NONE and finishes with dsph_bn_stats and dsph_bn_apply.
  * Asynchronous on `hip_stream` (a hipStream_t; NULL = the default stream).  (Part of a large fused forward may run on a
- * stream the plan owns, forked from and joined back into `hip_stream` inside the call: invisible to the caller, capturable.) */
+ * stream the plan owns, forked from and joined back into `hip_stream` inside the call: invisible to the caller, capturable.)
+ * Alignment (the family's contract above): on the fused route x (Fin % 4 == 0) and the workspace must be 16-byte aligned --
+ * DSPH_E_BADARG "x must be 16-byte aligned" otherwise, also under DSPH_ALGO_AUTO --, w, bias and y may sit at any 4-byte
+ * alignment (a misaligned y or bias moves tiles from the strip kernels to the tile kernels); the unfused route takes any pointer. */
 int dsph_cheb_forward(const dsph_plan* plan, const float* x, const float* w, const float* bias,
                       float* y, int64_t N, int32_t Fin, int32_t Fout, int32_t K, int32_t act,
                       int32_t precision, int32_t algo, void* workspace, size_t workspace_bytes,
@@ -319,7 +349,9 @@ int dsph_poly_forward_ex(const dsph_plan* plan, const float* x, const float* w, 
  * children in the same order).  pool_type: DSPH_POOL_MAX | DSPH_POOL_AVG.  Availability: dsph_plan_pool_fusable (whole
  * unsharded maps of whole tiles, a width that is a multiple of four, activation none or ReLU, not the 64 -> 64 shape where the
  * Clenshaw strip kernel takes tiles); DSPH_E_UNSUPPORTED otherwise -- run
- * dsph_poly_forward and dsph_healpix_pool then.  Workspace and flags as dsph_poly_forward_ex. */
+ * dsph_poly_forward and dsph_healpix_pool then.  Workspace and flags as dsph_poly_forward_ex.
+ * Alignment: x (Fin % 4 == 0), y_pooled, y_scratch (unless NULL) and the workspace 16-byte aligned -- every kernel stores the pooled
+ * map in 16-byte pieces; DSPH_E_BADARG naming the pointer otherwise --, w and bias any 4-byte alignment. */
 int dsph_plan_pool_fusable(const dsph_plan* plan, int64_t N, int32_t Fin, int32_t Fout, int32_t K, int32_t act);
 int dsph_poly_forward_pool(const dsph_plan* plan, const float* x, const float* w, const float* bias, float* y_scratch,
                            float* y_pooled, int64_t N, int32_t Fin, int32_t Fout, int32_t K, int32_t basis, int32_t act,
@@ -330,7 +362,9 @@ int dsph_poly_forward_pool(const dsph_plan* plan, const float* x, const float* w
  * for rows [0, rows) of every map (rows <= n_rows; rows <= 0 means n_rows); prev may be NULL
  * when beta == 0.  Replaces one utils.split_sparse_dense_matmul call plus the `2*... - x0`
  * temporaries (gnn_layers.py:138,141).  Exposed for the one-ring-halo-per-step sharded mode,
- * where the host exchanges boundary rows between steps, and for tests. */
+ * where the host exchanges boundary rows between steps, and for tests.
+ * Alignment: in, prev and out at any 4-byte alignment; float4 accesses when F % 4 == 0 and all three are 16-byte aligned, else
+ * the kernels' scalar form (the same additions in the same order: the same bits). */
 int dsph_cheb_step(const dsph_plan* plan, const float* in, const float* prev, float* out,
                    int64_t N, int32_t F, float alpha, float beta, int64_t rows, void* hip_stream);
 /* Note on plans with halo columns (n_cols > n_rows): a step writes rows [0, rows) only, so a SECOND step would
@@ -344,7 +378,10 @@ int dsph_cheb_step(const dsph_plan* plan, const float* in, const float* prev, fl
  *   y[n,m,o] = act( sum_k sum_f planes[k][n,m,f] * w[f*K + k, o] + bias[o] ),  m < rows.
  * Replaces tf.stack/reshape/transpose/matmul (gnn_layers.py:144-150).
  * Where the plain contraction kernel runs (the batch is a grid dimension there) N is at most 65535: DSPH_E_UNSUPPORTED beyond,
- * reported after the device has been selected. */
+ * reported after the device has been selected.
+ * Alignment: every plane, w, bias and y at any 4-byte alignment.  Planes are loaded in 16-byte pieces only when Fin % 4 == 0 and
+ * all K are aligned; a y off alignment with Fout % 4 == 0 is written by the exact-fp32 kernels (by the element) instead of the
+ * MFMA kernel, whatever `precision` asks for. */
 int dsph_cheb_contract(const float* const* planes, int64_t plane_rows, const float* w,
                        const float* bias, float* y, int64_t N, int64_t rows, int32_t Fin,
                        int32_t Fout, int32_t K, int32_t act, int32_t precision, int device,
@@ -355,7 +392,10 @@ int dsph_cheb_contract(const float* const* planes, int64_t plane_rows, const flo
  * operand of the weight gradient, rebuilt in the backward pass: the same recurrence as
  * gnn_layers.py:134-143, run by the fused tile kernel (no MFMA, the tile rows of every plane are
  * stored from LDS) when the plan/shape allows, else by K-1 dsph_cheb_step launches.
- * `algo`: DSPH_ALGO_AUTO | UNFUSED | FUSED as in dsph_cheb_forward. */
+ * `algo`: DSPH_ALGO_AUTO | UNFUSED | FUSED as in dsph_cheb_forward.
+ * Alignment: the fused kernel loads x and stores the planes in 16-byte pieces.  DSPH_ALGO_AUTO runs the step kernels instead when
+ * x or planes is off 16-byte alignment (this call has no workspace whose size would depend on it); DSPH_ALGO_FUSED returns
+ * DSPH_E_BADARG naming x or planes; DSPH_ALGO_UNFUSED takes any 4-byte alignment. */
 int dsph_cheb_planes(const dsph_plan* plan, const float* x, float* planes, int64_t N, int32_t Fin,
                      int32_t K, int32_t basis, int32_t algo, void* hip_stream);
 
@@ -376,7 +416,12 @@ int dsph_cheb_planes(const dsph_plan* plan, const float* x, float* planes, int64
  * or DSPH_PREC_FP32 keep every tile on the tile kernel.
  * In the bf16 arithmetic every second workgroup of both kernels contracts against -dy and its partial sum is subtracted: the
  * matrix pipe's fp32 accumulation of long sums is biased towards minus infinity (1 - 2e-5 of max |dw| at configs[2]) and the
- * mirror cancels it. */
+ * mirror cancels it.
+ * Alignment: on the fused route the workspace and x (Fin % 4 == 0; otherwise a padded copy behind the slabs is read) must be 16-byte
+ * aligned: DSPH_E_BADARG naming the pointer, before any launch.  dy at any 4-byte alignment: the quad-strip kernel reads it in
+ * 16-byte pieces, so a dy off alignment sends every tile to the tile kernel (the workspace holds its slabs either way).  dw any.
+ * The unfused route takes any pointer.  The workspace query's bytes cover the slabs of both kernels, the padded copy of x, or the
+ * planes and dsph_cheb_wgrad's slabs. */
 size_t dsph_backward_weights_workspace_bytes(const dsph_plan* plan, int64_t N, int32_t Fin, int32_t Fout,
                                              int32_t K, int32_t algo);
 int dsph_cheb_backward_weights(const dsph_plan* plan, const float* x, const float* dy, float* dw, int64_t N,
@@ -387,7 +432,8 @@ int dsph_cheb_backward_weights(const dsph_plan* plan, const float* x, const floa
  * for K planes T_k x of shape (N, plane_rows, Fin) (HOST array of K device pointers, e.g. x and the
  * outputs of dsph_cheb_step) and an upstream gradient dy (N, rows, Fout).  The reference has no
  * counterpart of its own: TensorFlow differentiates tf.matmul (gnn_layers.py:149).  Deterministic
- * (fixed-order reduction of per-workgroup partial sums held in `workspace`). */
+ * (fixed-order reduction of per-workgroup partial sums held in `workspace`).
+ * Alignment: planes, dy, dw and the workspace at any 4-byte alignment (read and written by the element). */
 size_t dsph_wgrad_workspace_bytes(int64_t N, int64_t rows, int32_t Fin, int32_t Fout, int32_t K);
 int dsph_cheb_wgrad(const float* const* planes, int64_t plane_rows, const float* dy, float* dw,
                     int64_t N, int64_t rows, int32_t Fin, int32_t Fout, int32_t K, void* workspace,
